@@ -11,9 +11,18 @@ Prints ONE JSON line on rank 0 (contract in the task statement).  WHICH MODE IS 
 the step with the reference's reversible ACTIVATION RECOMPUTE (``--recompute full``, the default): only each stack's output
 and the LSH sort permutations survive the forward; the backward reconstructs the streams by subtraction and re-runs
 LayerNorm, projections, attention and feed-forward of every block, as ``reformer_tts/model/reversible.py:69-98`` does and as
-BASELINE.json's north_star words it.  The memory-for-time mode this package also offers (every activation the backward
-needs kept in HBM, ~1 GB of 288 GB, same gradients to 3e-4: DESIGN.md section 4) is timed in the same run and reported
-under the top-level key ``stash`` (its own value / ms_per_step / peak memory) -- never mixed into ``value``.  Also:
+BASELINE.json's north_star words it.
+
+A plain run does only what the headline needs: set-up (model, trainer, graph capture), ``--warmup`` steps, ``--steps`` timed
+steps, the outputs of the last timed step if ``--dump-outputs DIR`` is given, the result line.  ``--dump-outputs DIR`` writes
+float32 ``DIR/<name>.npy``: ``loss``, ``raw_pred_loss``, ``post_pred_loss``, ``stop_loss`` (what ``Trainer.replay`` returns)
+and ``grad_sample`` / ``param_sample``, the flat gradient buffer and the parameters after the optimizer step at the same fixed,
+seeded 4 Mi positions (34 MB in all; at the baseline config the whole buffers are 108 MB each).  The inputs are seeded: the
+same arguments give the same inputs in every run.
+
+Everything else is measured with ``--full`` only.  The memory-for-time mode this package also offers (every activation the
+backward needs kept in HBM, ~1 GB of 288 GB, same gradients to 3e-4: DESIGN.md section 4) is timed in the same run and
+reported under the top-level key ``stash`` (its own value / ms_per_step / peak memory) -- never mixed into ``value``.  Also:
   roofline        the dominant kernel (LSH chunk-attention backward, MFMA-bound): algorithmic FLOP per launch / its average
                   duration measured with HIP events on the launch stream; ``traffic`` = HBM bytes per launch from the
                   committed rocprofv3 PMC passes (profiles/<round>_pmc_traffic.json) IF that file names the kernel and
@@ -54,8 +63,13 @@ def parse():
     ap.add_argument("--config", default="baseline", choices=["baseline", "long"],
                     help="baseline = config/baseline.yml (BASELINE.json configs[1]); long = config/bucket-size-64-18-06.yml at "
                          "mel 4096 (configs[3])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the full-recompute leg and the peak probes")
+    ap.add_argument("--full", action="store_true",
+                    help="also the other recompute mode, the roofline legs, the peak probes and the CPU baseline (a plain run times the "
+                         "headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other recompute mode's leg and the peak probes")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying a hipGraph")
     ap.add_argument("--cpu-budget-s", type=float, default=25.0)
     ap.add_argument("--strict", action="store_true", help="raise when the committed PMC traffic file does not match the kernel / shape of this run")
@@ -66,7 +80,7 @@ def parse():
                          "'projection-stash' = and the projections, streams still reconstructed by subtraction; 'stash' (the "
                          "package's own default for training, the secondary number reported here) = and the streams: every sublayer's "
                          "LayerNorm input / output and projections stay in HBM (~1 GB of 288 GB), the backward recomputes nothing.  "
-                         "The other end of the range is timed in the same run (top-level key 'stash' or 'full_recompute')")
+                         "With --full the other end of the range is timed in the same run (top-level key 'stash' or 'full_recompute')")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 12 if args.config == "baseline" else 4
@@ -139,6 +153,26 @@ def measure_peaks(dev):
     torch.cuda.synchronize()
     mfma_tf = wgs * 8 * iters * 8 * 16384.0 / (a.elapsed_time(b) * 1e-3) / 1e12
     return round(copy_gbs, 1), round(mfma_tf, 1)
+
+
+DUMP_SAMPLE = 1 << 22      # positions of the flat gradient / parameter buffers written by --dump-outputs (16 MB each)
+
+
+def dump_outputs(path, trainer, step_out):
+    """--dump-outputs: the four losses the last timed step returned, and its gradients and the parameters it left at a fixed,
+    seeded sample of flat-buffer positions (the same for every run with the same arguments), as float32 .npy files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = trainer.flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    else:
+        idx = torch.arange(n)
+    idx = idx.to(trainer.flat_p.device)
+    arrays = dict(zip(("loss", "raw_pred_loss", "post_pred_loss", "stop_loss"), step_out))
+    arrays.update(grad_sample=trainer.flat_g[idx], param_sample=trainer.flat_p[idx])
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def main():
@@ -227,7 +261,7 @@ def main():
         t0 = time.perf_counter()
         try:
             for _ in range(steps):
-                last = step_fn()[0]
+                last = step_fn()
             torch.cuda.synchronize()
         finally:
             gc.enable()
@@ -274,28 +308,33 @@ def main():
     for i in range(args.warmup):          # back to back, like the timed steps: the region starts from a busy chip, not from an idle one
         step_fn()
     note(f"{args.warmup} warm-up step(s) launched")
-    elapsed, loss = timed(step_fn, args.steps)
+    elapsed, last_out = timed(step_fn, args.steps)
+    loss = last_out[0]
     note(f"timed region done: {1e3 * elapsed / args.steps:.2f} ms/step")
-
-    # HIP events cannot be read back from inside a replayed graph: time the roofline kernels on the same stream over eager
-    # steps of the same workload, directly after the timed region
-    n_eager = min(args.steps, 10)
-    ops.TIMING.enable(*tags.values())
-    for _ in range(n_eager):
-        trainer.train_step(batch)
-    torch.cuda.synchronize()
-    timing = {k: ops.TIMING.summary(t) for k, t in tags.items()}
-    gemm_shapes = {k.split("/")[1]: ops.TIMING.summary(k) for k in ops.TIMING.records if k.startswith("rtts_gemm_nt/")}
-    ops.TIMING.disable()
     if not (float(loss) == float(loss)):
         raise RuntimeError("training loss is not finite")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, last_out)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    if args.full:
+        # HIP events cannot be read back from inside a replayed graph: time the roofline kernels on the same stream over eager
+        # steps of the same workload, directly after the timed region
+        n_eager = min(args.steps, 10)
+        ops.TIMING.enable(*tags.values())
+        for _ in range(n_eager):
+            trainer.train_step(batch)
+        torch.cuda.synchronize()
+        timing = {k: ops.TIMING.summary(t) for k, t in tags.items()}
+        gemm_shapes = {k.split("/")[1]: ops.TIMING.summary(k) for k in ops.TIMING.records if k.startswith("rtts_gemm_nt/")}
+        ops.TIMING.disable()
+    peak_mem_gb = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)
 
     # the other end of the recompute range, in the same run (a second capture on the same trainer): the memory-for-time
     # mode when the headline is the reference's full recompute, and the other way round
-    peak_mem_gb = round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)
     other_mode = "stash" if args.recompute != "stash" else "full"
     other = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         torch.cuda.reset_peak_memory_stats(dev)
         set_mode(other_mode)
         ok = capture() if use_graph else True
@@ -315,7 +354,7 @@ def main():
         set_mode(args.recompute)
         note(f"{other_mode} mode: {other['ms_per_step']} ms/step")
     peaks = (None, None)
-    if rank == 0 and not args.no_extra:
+    if rank == 0 and args.full and not args.no_extra:
         peaks = measure_peaks(dev)
         note(f"measured on this box: stream copy {peaks[0]} GB/s, bf16 MFMA loop {peaks[1]} TFLOP/s")
 
@@ -354,107 +393,108 @@ def main():
         }
         if other is not None:
             out["stash" if other_mode == "stash" else "full_recompute"] = other
-        rooflines = []
-        from reformer_tts_amd import _lib
-        shape_key = {"BH": args.batch * heads_dec, "T": t_dec, "bucket": dec_bucket, "rounds": n_hashes_dec}
+        if args.full:
+            rooflines = []
+            from reformer_tts_amd import _lib
+            shape_key = {"BH": args.batch * heads_dec, "T": t_dec, "bucket": dec_bucket, "rounds": n_hashes_dec}
 
-        def pmc_traffic(kernel_prefix):
-            """HBM bytes per launch of ``kernel_prefix`` at ``shape_key`` from the newest committed profiles/*_pmc_traffic.json
-            (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, collected outside this process; scripts/pmc_summary.py), or
-            (None, reason) when no entry names this kernel at this shape -- a changed kernel must not inherit old counters."""
-            import glob
-            files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
-            if not files:
-                return None, "no profiles/*_pmc_traffic.json committed"
-            with open(files[-1]) as fh:
-                doc = json.load(fh)
-            for e in doc.get("entries", []):
-                if e["kernel"].startswith(kernel_prefix) and e.get("shape") == shape_key:
-                    return int(e["traffic_bytes"]), os.path.basename(files[-1])
-            return None, (f"{os.path.basename(files[-1])} has no entry for {kernel_prefix}* at {shape_key} "
-                          f"(it holds: {[e['kernel'] for e in doc.get('entries', [])]})")
+            def pmc_traffic(kernel_prefix):
+                """HBM bytes per launch of ``kernel_prefix`` at ``shape_key`` from the newest committed profiles/*_pmc_traffic.json
+                (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, collected outside this process; scripts/pmc_summary.py), or
+                (None, reason) when no entry names this kernel at this shape -- a changed kernel must not inherit old counters."""
+                import glob
+                files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
+                if not files:
+                    return None, "no profiles/*_pmc_traffic.json committed"
+                with open(files[-1]) as fh:
+                    doc = json.load(fh)
+                for e in doc.get("entries", []):
+                    if e["kernel"].startswith(kernel_prefix) and e.get("shape") == shape_key:
+                        return int(e["traffic_bytes"]), os.path.basename(files[-1])
+                return None, (f"{os.path.basename(files[-1])} has no entry for {kernel_prefix}* at {shape_key} "
+                              f"(it holds: {[e['kernel'] for e in doc.get('entries', [])]})")
 
-        def mfma_entry(kernel, avg_ms, launches, flops, extra=None):
-            ach = flops / (avg_ms * 1e-3) / 1e12
-            traffic, src = pmc_traffic(kernel)
-            if traffic is None:
-                if args.strict:
-                    raise RuntimeError(f"roofline.traffic: {src}")
-                note(f"ROOFLINE TRAFFIC NOT REPORTED for {kernel}: {src}")
-            e = {"kernel": kernel, "bound": "mfma", "achieved": round(ach, 2), "peak": BF16_DENSE_PEAK_TFLOPS,
-                 "unit": "TFLOP/s", "frac": round(ach / BF16_DENSE_PEAK_TFLOPS, 4), "traffic": traffic,
-                 ("traffic_source" if traffic is not None else "traffic_stale"): src,
-                 "algorithmic_flop_per_launch": flops, "avg_launch_ms": round(avg_ms, 4), "launches_timed": launches,
-                 "peak_measured": peaks[1], "frac_of_measured": (round(ach / peaks[1], 4) if peaks[1] else None)}
-            e.update(extra or {})
-            return e
+            def mfma_entry(kernel, avg_ms, launches, flops, extra=None):
+                ach = flops / (avg_ms * 1e-3) / 1e12
+                traffic, src = pmc_traffic(kernel)
+                if traffic is None:
+                    if args.strict:
+                        raise RuntimeError(f"roofline.traffic: {src}")
+                    note(f"ROOFLINE TRAFFIC NOT REPORTED for {kernel}: {src}")
+                e = {"kernel": kernel, "bound": "mfma", "achieved": round(ach, 2), "peak": BF16_DENSE_PEAK_TFLOPS,
+                     "unit": "TFLOP/s", "frac": round(ach / BF16_DENSE_PEAK_TFLOPS, 4), "traffic": traffic,
+                     ("traffic_source" if traffic is not None else "traffic_stale"): src,
+                     "algorithmic_flop_per_launch": flops, "avg_launch_ms": round(avg_ms, 4), "launches_timed": launches,
+                     "peak_measured": peaks[1], "frac_of_measured": (round(ach / peaks[1], 4) if peaks[1] else None)}
+                e.update(extra or {})
+                return e
 
-        avg_ms, launches, flops = timing["bwd"]
-        if launches:
-            run = _lib.load().rtts_lsh_attn_bwd_run_length(args.batch, heads_dec, t_dec, n_hashes_dec, dec_bucket)
-            entry = mfma_entry(f"lsh_attn_bwd_walk_kernel<{dec_bucket}" if run > 0 else f"lsh_attn_bwd_kernel<{dec_bucket}",
-                               avg_ms, launches, flops, {"chunks_per_workgroup": max(run, 1)})
-            out["roofline"] = entry
-            rooflines.append(entry)
-        avg_ms, launches, flops = timing["fwd"]
-        if launches:
-            run = _lib.load().rtts_lsh_attn_fwd_run_length(args.batch, heads_dec, t_dec, n_hashes_dec, dec_bucket)
-            rooflines.append(mfma_entry(f"lsh_attn_fwd_walk_kernel<{dec_bucket}" if run > 0 else f"lsh_attn_fwd_kernel<{dec_bucket}",
-                                        avg_ms, launches, flops, {"chunks_per_workgroup": max(run, 1)}))
-        avg_ms, launches, nbytes = timing["hash"]
-        if launches:
-            # a 10-15 us launch is host-bound when launched eagerly (Python + ctypes per call): its device time comes from a
-            # hipGraph of 20 calls at the same shape, replayed, with HIP events on the replay stream
-            # ... over a ROTATION of distinct inputs: 24 qk buffers of 12.6 MB + their 3 MB outputs = 0.38 GB per pass, more than the
-            # 256 MB Infinity Cache holds, so every call fetches its rows from HBM (one buffer re-hashed 200 times -- round 3 -- is an
-            # Infinity-Cache figure; it is reported beside this one as `achieved_cached`)
-            n_rot = 24
-            rot_probe = torch.randn(1, 64, n_hashes_dec, t_dec // dec_bucket // 2, device=dev)
-            qk_probes = [torch.randn(args.batch, t_dec, heads_dec * 64, device=dev).bfloat16() for _ in range(n_rot)]
-            it = [0]
+            avg_ms, launches, flops = timing["bwd"]
+            if launches:
+                run = _lib.load().rtts_lsh_attn_bwd_run_length(args.batch, heads_dec, t_dec, n_hashes_dec, dec_bucket)
+                entry = mfma_entry(f"lsh_attn_bwd_walk_kernel<{dec_bucket}" if run > 0 else f"lsh_attn_bwd_kernel<{dec_bucket}",
+                                   avg_ms, launches, flops, {"chunks_per_workgroup": max(run, 1)})
+                out["roofline"] = entry
+                rooflines.append(entry)
+            avg_ms, launches, flops = timing["fwd"]
+            if launches:
+                run = _lib.load().rtts_lsh_attn_fwd_run_length(args.batch, heads_dec, t_dec, n_hashes_dec, dec_bucket)
+                rooflines.append(mfma_entry(f"lsh_attn_fwd_walk_kernel<{dec_bucket}" if run > 0 else f"lsh_attn_fwd_kernel<{dec_bucket}",
+                                            avg_ms, launches, flops, {"chunks_per_workgroup": max(run, 1)}))
+            avg_ms, launches, nbytes = timing["hash"]
+            if launches:
+                # a 10-15 us launch is host-bound when launched eagerly (Python + ctypes per call): its device time comes from a
+                # hipGraph of 20 calls at the same shape, replayed, with HIP events on the replay stream
+                # ... over a ROTATION of distinct inputs: 24 qk buffers of 12.6 MB + their 3 MB outputs = 0.38 GB per pass, more than the
+                # 256 MB Infinity Cache holds, so every call fetches its rows from HBM (one buffer re-hashed 200 times -- round 3 -- is an
+                # Infinity-Cache figure; it is reported beside this one as `achieved_cached`)
+                n_rot = 24
+                rot_probe = torch.randn(1, 64, n_hashes_dec, t_dec // dec_bucket // 2, device=dev)
+                qk_probes = [torch.randn(args.batch, t_dec, heads_dec * 64, device=dev).bfloat16() for _ in range(n_rot)]
+                it = [0]
 
-            def hash_next():
-                ops.lsh_hash_sort(qk_probes[it[0] % n_rot], rot_probe, heads_dec, dec_bucket)
-                it[0] += 1
-            avg_ms, launches = graph_timed(hash_next, 2 * n_rot, 5)
-            cached_ms, _ = graph_timed(lambda: ops.lsh_hash_sort(qk_probes[0], rot_probe, heads_dec, dec_bucket), 20, 10)
-            del qk_probes
-            two = _lib.load().rtts_lsh_hash_sort_launches(t_dec) == 2
-            ach = nbytes / (avg_ms * 1e-3) / 1e9
-            # counters of the launch(es) one call makes (the hash of all rounds and the sorts are two kernels from T = 1024 on)
-            parts = [pmc_traffic(k) for k in (("lsh_hash_rounds_kernel", "lsh_sort_ids_kernel") if two else ("lsh_hash_sort_kernel",))]
-            h_traffic = sum(p[0] for p in parts) if all(p[0] is not None for p in parts) else None
-            rooflines.append({"kernel": "lsh_hash_rounds_kernel + lsh_sort_ids_kernel" if two else "lsh_hash_sort_kernel", "bound": "hbm",
-                              "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": h_traffic,
-                              ("traffic_source" if h_traffic is not None else "traffic_stale"): parts[0][1] if h_traffic is not None
-                              else next(p[1] for p in parts if p[0] is None),
-                              "avg_launch_ms": round(avg_ms, 4),
-                              "launches_timed": launches, "timed": f"hipGraph of {2 * n_rot} calls over a rotation of {n_rot} distinct inputs "
-                              "(0.38 GB per pass: beyond the 256 MB Infinity Cache, so the rows come from HBM), replayed 5 times (device time; "
-                              "eager launches of a kernel this short are host-bound)",
-                              "achieved_cached": round(nbytes / (cached_ms * 1e-3) / 1e9, 1), "avg_launch_ms_cached": round(cached_ms, 4),
-                              "peak_measured": peaks[0],
-                              "frac_of_measured": (round(ach / peaks[0], 4) if peaks[0] else None),
-                              "algorithmic_bytes_per_launch": int(nbytes),
-                              "note": "SURVEY.md 8(d): 224 B per token and head (hash 128 + 32, sort 64); decoder shape; one rtts_lsh_hash_sort "
-                                      "call = " + ("two launches (hash of all rounds, then the sorts)" if two else "one launch")})
-        avg_ms, launches, flops = timing["gemm"]
-        if launches:
-            ach = flops / (avg_ms * 1e-3) / 1e12
-            big = max(gemm_shapes.items(), key=lambda kv: kv[1][2]) if gemm_shapes else None
-            e = {"kernel": "gemm_nt_kernel (all shapes of the step)", "bound": "mfma", "achieved": round(ach, 2),
-                 "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / BF16_DENSE_PEAK_TFLOPS, 4), "traffic": None,
-                 "avg_launch_ms": round(avg_ms, 4), "launches_timed": launches, "peak_measured": peaks[1],
-                 "frac_of_measured": (round(ach / peaks[1], 4) if peaks[1] else None)}
-            if big is not None:
-                bms, bn, bfl = big[1]
-                e["largest_shape"] = {"MxNxK": big[0], "avg_launch_ms": round(bms, 4), "launches_timed": bn,
-                                      "achieved": round(bfl / (bms * 1e-3) / 1e12, 2)}
-            rooflines.append(e)
-        out["rooflines"] = rooflines
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(model_cfg, args.mel_len, args.text_len, args.cpu_budget_s)
+                def hash_next():
+                    ops.lsh_hash_sort(qk_probes[it[0] % n_rot], rot_probe, heads_dec, dec_bucket)
+                    it[0] += 1
+                avg_ms, launches = graph_timed(hash_next, 2 * n_rot, 5)
+                cached_ms, _ = graph_timed(lambda: ops.lsh_hash_sort(qk_probes[0], rot_probe, heads_dec, dec_bucket), 20, 10)
+                del qk_probes
+                two = _lib.load().rtts_lsh_hash_sort_launches(t_dec) == 2
+                ach = nbytes / (avg_ms * 1e-3) / 1e9
+                # counters of the launch(es) one call makes (the hash of all rounds and the sorts are two kernels from T = 1024 on)
+                parts = [pmc_traffic(k) for k in (("lsh_hash_rounds_kernel", "lsh_sort_ids_kernel") if two else ("lsh_hash_sort_kernel",))]
+                h_traffic = sum(p[0] for p in parts) if all(p[0] is not None for p in parts) else None
+                rooflines.append({"kernel": "lsh_hash_rounds_kernel + lsh_sort_ids_kernel" if two else "lsh_hash_sort_kernel", "bound": "hbm",
+                                  "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": h_traffic,
+                                  ("traffic_source" if h_traffic is not None else "traffic_stale"): parts[0][1] if h_traffic is not None
+                                  else next(p[1] for p in parts if p[0] is None),
+                                  "avg_launch_ms": round(avg_ms, 4),
+                                  "launches_timed": launches, "timed": f"hipGraph of {2 * n_rot} calls over a rotation of {n_rot} distinct inputs "
+                                  "(0.38 GB per pass: beyond the 256 MB Infinity Cache, so the rows come from HBM), replayed 5 times (device time; "
+                                  "eager launches of a kernel this short are host-bound)",
+                                  "achieved_cached": round(nbytes / (cached_ms * 1e-3) / 1e9, 1), "avg_launch_ms_cached": round(cached_ms, 4),
+                                  "peak_measured": peaks[0],
+                                  "frac_of_measured": (round(ach / peaks[0], 4) if peaks[0] else None),
+                                  "algorithmic_bytes_per_launch": int(nbytes),
+                                  "note": "SURVEY.md 8(d): 224 B per token and head (hash 128 + 32, sort 64); decoder shape; one rtts_lsh_hash_sort "
+                                          "call = " + ("two launches (hash of all rounds, then the sorts)" if two else "one launch")})
+            avg_ms, launches, flops = timing["gemm"]
+            if launches:
+                ach = flops / (avg_ms * 1e-3) / 1e12
+                big = max(gemm_shapes.items(), key=lambda kv: kv[1][2]) if gemm_shapes else None
+                e = {"kernel": "gemm_nt_kernel (all shapes of the step)", "bound": "mfma", "achieved": round(ach, 2),
+                     "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(ach / BF16_DENSE_PEAK_TFLOPS, 4), "traffic": None,
+                     "avg_launch_ms": round(avg_ms, 4), "launches_timed": launches, "peak_measured": peaks[1],
+                     "frac_of_measured": (round(ach / peaks[1], 4) if peaks[1] else None)}
+                if big is not None:
+                    bms, bn, bfl = big[1]
+                    e["largest_shape"] = {"MxNxK": big[0], "avg_launch_ms": round(bms, 4), "launches_timed": bn,
+                                          "achieved": round(bfl / (bms * 1e-3) / 1e12, 2)}
+                rooflines.append(e)
+            out["rooflines"] = rooflines
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(model_cfg, args.mel_len, args.text_len, args.cpu_budget_s)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

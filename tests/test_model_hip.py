@@ -1,5 +1,6 @@
 """GPU parity of the whole forward / loss / backward (HIP LSH attention inside the model mirror)
 against the golden recorded from the reference's wiring, and of the optimizer kernels."""
+import gc
 import os
 
 import numpy as np
@@ -727,12 +728,19 @@ def test_attention_stash_matches_pure_recompute(gpu, attn_dropout):
             tr = Trainer(model, TTSTrainingConfig(batch_size=2, recompute=mode), gpu)
             model.train()
             tr.zero_grad()
-            torch.cuda.synchronize()
-            base = torch.cuda.memory_allocated(gpu)
-            loss = tr.forward_loss(batch)[0]
-            assert engine.recompute_mode() == mode              # the trainer installed its configuration, nobody poked a global
-            torch.cuda.synchronize()
-            held[mode] = torch.cuda.memory_allocated(gpu) - base
+            # the previous mode's model and trainer are cyclic garbage: free them now, and keep the collector off while the forward
+            # is measured -- a collection inside it would free their buffers and make `held` negative
+            gc.collect()
+            gc.disable()
+            try:
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated(gpu)
+                loss = tr.forward_loss(batch)[0]
+                assert engine.recompute_mode() == mode          # the trainer installed its configuration, nobody poked a global
+                torch.cuda.synchronize()
+                held[mode] = torch.cuda.memory_allocated(gpu) - base
+            finally:
+                gc.enable()
             loss.backward()
             torch.cuda.synchronize()
             grads[mode] = tr.flat_g.clone()
