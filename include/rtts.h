@@ -186,7 +186,8 @@ int rtts_colsum_bf16(void* dh, const void* h, int64_t ld, float* dbias, float* p
 /* Deferred finalisation of the column sums: rtts_ln_bwd (dgamma = dbeta = NULL), rtts_cast_colsum / rtts_colsum_bf16
  * (dbias = NULL) then only write their partial rows -- rtts_colsum_partial_rows(M) rows of d floats; rtts_ln_bwd writes two
  * such blocks, the second 256*d floats after the first -- and ONE grouped launch adds the sums of up to
- * RTTS_COLSUM_MAX_GROUP partial buffers into their outputs (same fixed summation order: deterministic). */
+ * RTTS_COLSUM_MAX_GROUP partial buffers into their outputs (same fixed summation order: deterministic).  The outputs of one
+ * call must not overlap (refused: two jobs adding into one element would race). */
 #define RTTS_COLSUM_MAX_GROUP 48
 typedef struct {
     const float* partial;   /* (nrows, n) fp32, row stride ld */
@@ -289,7 +290,7 @@ typedef struct {
 } rtts_conv_perm_job;
 int rtts_conv_w_perm_grouped(const rtts_conv_perm_job* jobs, int n, void* stream);
 /* The adjoint for the gradients, likewise grouped: jobs[i].w = dwp (Co_pad, 5*CP) fp32, jobs[i].wp = dw (Co, Ci, 5) fp32,
- * dw[co][ci][k] += dwp[co][k][ci]. */
+ * dw[co][ci][k] += dwp[co][k][ci].  Two jobs of one call may not add into overlapping dw (refused: they would race). */
 int rtts_conv_dw_unperm_grouped(const rtts_conv_perm_job* jobs, int n, void* stream);
 /* The convolution in front of a BatchNorm (reference modules.py:19-54,103-169: Conv1d -> BatchNorm1d): y (M, C_out) fp32 = the forward
  * of rtts_conv1d_k5 (no bias: BatchNorm cancels it) AND, from the same accumulators, the per-channel sums of y and y^2 over the rows that
@@ -392,7 +393,12 @@ int rtts_gemm_tn(const void* a, int64_t lda, const void* b, int64_t ldb, int M, 
 
 /* Up to RTTS_GEMM_TN_MAX_GROUP independent weight gradients in ONE pair of launches (the deferred gradients of a
  * reversible layer): the grid holds every problem's tiles, so the split factor -- and with it the slab traffic --
- * drops to what the whole group needs to fill the chip.  Same arithmetic per problem as rtts_gemm_tn. */
+ * drops to what the whole group needs to fill the chip.  A problem's result agrees with its single launch up to the fp32
+ * summation order, not bit for bit: the tile size (128 or 256) and each problem's split factor depend on the whole group
+ * (its tile count and GFLOP, what is left of slab_ws), and split decides how the token range is summed.  Every group is
+ * deterministic run to run.  No two problems of one call may write a common element of C (their workgroups would race on
+ * it and lose a contribution): such a call is refused; problems of one ldc that write disjoint column blocks of one matrix
+ * are fine, spans of different ldc that interleave are refused too.  Launch overlapping problems one call after the other. */
 #define RTTS_GEMM_TN_MAX_GROUP 16
 typedef struct {
     const void* a; int64_t lda;    /* dY (M x N) bf16 */
@@ -428,8 +434,9 @@ int rtts_gemm_nt_partial_rows(int M, int N);
  *   epilogue 5: [K][N] weights only -- the input gradient of to_out / out_proj (c = dout, bf16) AND delta[b*H + h][t] =
  *                sum over the 64 columns of head h of aux[m][.] * dout[m][.] (aux = the attention output, bf16 (M, N) stride
  *                ld_aux; rows m = b*T + t; delta f32 (B*H, T)), i.e. rtts_lsh_bwd_delta folded into the product that makes dout.
- * Epilogues 0, 1, 4 in a group (each problem its own); 0, 1, 4, 5 alone.  Shapes: as rtts_gemm_nt (a group needs one tile shape that tiles every
- * problem: 192x128, 96x64 or 128x64).  Tested in tests/test_gemm_hip.py against float64 on the same bf16 operands. */
+ * Epilogues 0, 1, 4 in a group (each problem its own); 0, 1, 4, 5 alone; epilogue 0 with a bias is refused (a group would add it).
+ * Shapes: as rtts_gemm_nt (a group needs one tile shape that tiles every problem: 192x128, 96x64 or 128x64).
+ * Tested in tests/test_gemm_hip.py against float64 on the same bf16 operands. */
 typedef struct {
     const void* a; int64_t lda;
     const void* w; int64_t ldw;

@@ -854,6 +854,12 @@ extern "C" int rtts_conv_dw_unperm_grouped(const rtts_conv_perm_job* jobs, int n
         g.blk_start[i] = blk;
         blk += (int)ed_grid((size_t)jobs[i].Co * jobs[i].Ci);
     }
+    // dw += ...: two jobs of one launch that add into one element of dw would lose a contribution
+    for (int i = 1; i < n; ++i)
+        for (int k = 0; k < i; ++k)
+            RTTS_REQUIRE((const float*)jobs[i].wp >= (const float*)jobs[k].wp + (size_t)jobs[k].Co * jobs[k].Ci * 5 ||
+                             (const float*)jobs[k].wp >= (const float*)jobs[i].wp + (size_t)jobs[i].Co * jobs[i].Ci * 5,
+                         "rtts_conv_dw_unperm_grouped: jobs %d and %d add into overlapping gradients (launch them one after the other)", k, i);
     for (int i = n; i <= RTTS_CONV_PERM_MAX_GROUP; ++i) g.blk_start[i] = blk;
     hipLaunchKernelGGL(conv_dw_unperm_grouped_kernel, dim3(blk), dim3(ED_THREADS), 0, (hipStream_t)stream, g);
     RTTS_LAUNCH_CHECK("rtts_conv_dw_unperm_grouped");

@@ -660,6 +660,11 @@ extern "C" int rtts_colsum_final_grouped(const rtts_colsum_job* jobs, int n, voi
         grp.j[i].blk_start = blk;
         blk += (jobs[i].n + 63) / 64;
     }
+    // the jobs' blocks run side by side: two that add into one output element (out[c] += t) would lose a contribution
+    for (int i = 1; i < n; ++i)
+        for (int k = 0; k < i; ++k)
+            RTTS_REQUIRE(jobs[i].out >= jobs[k].out + jobs[k].n || jobs[k].out >= jobs[i].out + jobs[i].n,
+                         "rtts_colsum_final_grouped: jobs %d and %d add into overlapping outputs (launch them one after the other)", k, i);
     hipLaunchKernelGGL(colsum_final_grouped_kernel, dim3(blk), dim3(64 * CS_WAVES), 0, (hipStream_t)stream, grp);
     RTTS_LAUNCH_CHECK("rtts_colsum_final_grouped");
     return 0;

@@ -842,6 +842,8 @@ static int gn_fill(GnArgs& P, const rtts_gemm_nt_problem& q, int w_is_kn, int i)
                  "rtts_gemm_nt_grouped: problem %d: bad leading dimensions", i);
     RTTS_REQUIRE(q.epilogue == 0 || q.epilogue == 1 || q.epilogue == 4 || q.epilogue == 5, "rtts_gemm_nt_grouped: problem %d: epilogue 0, 1, 4 or 5", i);
     RTTS_REQUIRE(q.epilogue != 1 || q.bias, "rtts_gemm_nt_grouped: problem %d: epilogue 1 needs a bias", i);
+    // (a group runs epilogues 0 and 1 as one form that adds any bias it is given, a single problem would ignore it)
+    RTTS_REQUIRE(q.epilogue != 0 || !q.bias, "rtts_gemm_nt_grouped: problem %d: epilogue 0 takes no bias (epilogue 1 adds one)", i);
     RTTS_REQUIRE(!q.accumulate || q.epilogue == 4, "rtts_gemm_nt_grouped: problem %d: accumulate goes with the fp32 epilogue (4)", i);
     RTTS_REQUIRE((((uintptr_t)q.a | (uintptr_t)q.w | (uintptr_t)q.bias) & 15) == 0 && ((uintptr_t)q.c & (q.epilogue == 4 ? 15 : 7)) == 0,
                  "rtts_gemm_nt_grouped: problem %d: misaligned buffer", i);

@@ -421,6 +421,22 @@ static int gt_launch(const GtGroup& grp, int wg, hipStream_t s) {
     return 0;
 }
 
+// Do two problems write a common element of C?  (Element-exact for one ldc -- the five tap problems of a convolution write
+// column blocks of one matrix; spans of different ldc that interleave count as overlapping.)  c is 16-byte aligned.
+static bool gt_c_overlap(const rtts_gemm_tn_problem& p, const rtts_gemm_tn_problem& q) {
+    const uintptr_t bp = (uintptr_t)p.c, bq = (uintptr_t)q.c;
+    const uintptr_t ep = bp + ((uintptr_t)(p.N - 1) * (uintptr_t)p.ldc + (uintptr_t)p.K) * sizeof(float);
+    const uintptr_t eq = bq + ((uintptr_t)(q.N - 1) * (uintptr_t)q.ldc + (uintptr_t)q.K) * sizeof(float);
+    if (bq >= ep || bp >= eq) return false;
+    if (p.ldc != q.ldc) return true;
+    const rtts_gemm_tn_problem& lo = bp <= bq ? p : q;
+    const rtts_gemm_tn_problem& hi = bp <= bq ? q : p;
+    const int64_t d = (int64_t)(((uintptr_t)hi.c - (uintptr_t)lo.c) / sizeof(float));
+    const int64_t r = d / lo.ldc, s = d % lo.ldc;            // hi starts in row r (< lo.N: the spans overlap), column s of lo
+    if (s < lo.K) return true;                               // hi's rows run through lo's columns
+    return s + hi.K > lo.ldc && r + 1 < lo.N;                // hi's rows wrap round into column 0 of lo's next rows
+}
+
 extern "C" int rtts_gemm_tn_grouped(const rtts_gemm_tn_problem* problems, int n, float* slab_ws, int64_t slab_ws_floats, void* stream) {
     RTTS_ENTER(stream);
     RTTS_REQUIRE(problems && n > 0 && n <= RTTS_GEMM_TN_MAX_GROUP, "rtts_gemm_tn_grouped: 1..%d problems", RTTS_GEMM_TN_MAX_GROUP);
@@ -439,6 +455,12 @@ extern "C" int rtts_gemm_tn_grouped(const rtts_gemm_tn_problem* problems, int n,
         big = big && q.N % 256 == 0 && q.K % 256 == 0;
         flops += 2LL * q.M * q.N * q.K;
     }
+    // the workgroups of one grid are unordered: two problems adding into one element of C (the direct epilogue's *p + acc,
+    // slab_reduce's read-add-write) would lose one contribution
+    for (int i = 1; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            RTTS_REQUIRE(!gt_c_overlap(problems[j], problems[i]),
+                         "rtts_gemm_tn_grouped: problems %d and %d write overlapping parts of C (launch them one after the other)", j, i);
     // small groups cannot fill 256 CUs with 256 x 256 tiles without splitting the token range very finely
     // (measured: one 25.8 GFLOP problem 45 us with 128-tiles / 50 us with 256-tiles; the 87 GFLOP group of a decoder
     // layer 143 us / 127 us)

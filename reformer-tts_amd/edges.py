@@ -102,10 +102,11 @@ def flush_conv_dw(queue=None) -> None:
     """dw[co][ci][k] += dwp[co][k][ci] for every convolution whose backward has run since the last flush (one launch)."""
     queue = _engine._queue() if queue is None else queue
     flush_conv_wgrad(queue)
-    pending = queue.conv_items
-    while pending:
-        chunk = pending[:_lib.CONV_PERM_MAX_GROUP]
-        del pending[:len(chunk)]
+    pending = list(queue.conv_items)
+    del queue.conv_items[:]
+    # one convolution run twice before a flush queues its gradient twice: never in one launch (engine.launch_groups)
+    for chunk in _engine.launch_groups(pending, _lib.CONV_PERM_MAX_GROUP,
+                                       lambda a, b: _engine.spans_overlap(a[4].data_ptr(), 20 * a[1] * a[2], b[4].data_ptr(), 20 * b[1] * b[2])):
         jobs = (_lib.ConvPermJob * len(chunk))()
         for j, (dwp, co, ci, cp, gw) in zip(jobs, chunk):
             j.w, j.wp, j.Co, j.Ci, j.CP = dwp.data_ptr(), gw.data_ptr(), co, ci, cp

@@ -241,12 +241,32 @@ def _queue_colsum(partial: torch.Tensor, offset_floats: int, rows: int, d: int, 
     _queue_final_flush()
 
 
+def launch_groups(items, cap: int, overlap):
+    """Cut ``items``, in order, into runs of at most ``cap`` of which no two overlap (``overlap(a, b)``) -- the jobs of one grouped
+    launch run side by side, and two that add into one output would lose a contribution (one parameter queued twice before a
+    flush: a backward through two forwards of one model).  Launching the runs in order keeps the queue's order."""
+    groups, cur = [], []
+    for it in items:
+        if len(cur) == cap or any(overlap(it, c) for c in cur):
+            groups.append(cur)
+            cur = []
+        cur.append(it)
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def spans_overlap(p1: int, n1: int, p2: int, n2: int) -> bool:
+    """Do the byte ranges [p1, p1 + n1) and [p2, p2 + n2) intersect?"""
+    return p1 < p2 + n2 and p2 < p1 + n1
+
+
 def flush_colsum(q: Optional[_Queue] = None):
     for q in ([q] if q is not None else _all_queues()):
-        pending = q.colsums
-        while pending:
-            group = pending[:_lib.COLSUM_MAX_GROUP]
-            del pending[:len(group)]
+        pending = list(q.colsums)
+        del q.colsums[:]
+        for group in launch_groups(pending, _lib.COLSUM_MAX_GROUP,
+                                   lambda a, b: spans_overlap(a[4].data_ptr(), 4 * a[3], b[4].data_ptr(), 4 * b[3])):
             arr = (_lib.ColsumJob * len(group))()
             for j, (partial, off, rows, d, out, ld) in zip(arr, group):
                 j.partial, j.out, j.nrows, j.n, j.ld = partial.data_ptr() + 4 * off, out.data_ptr(), rows, d, ld
@@ -528,19 +548,38 @@ def run_handed_over(steal) -> int:
         for gv, dy, x in entries:
             dy.record_stream(main)
             x.record_stream(main)
-        pending = list(entries)
-        while pending:
-            group = pending[:_lib.GEMM_TN_MAX_GROUP]
-            del pending[:len(group)]
-            arr = (_lib.GemmTnProblem * len(group))()
-            for e, (gv, dy, x) in zip(arr, group):
-                e.a, e.lda, e.b, e.ldb, e.c, e.ldc = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), gv.data_ptr(), gv.stride(0)
-                e.M, e.N, e.K, e.accumulate = dy.shape[0], dy.shape[1], x.shape[1], 1
-            ws = _slab_ws(group[0][1].device)
-            _lib.call("rtts_gemm_tn_grouped", arr, len(group), ws.data_ptr(), ws.numel(), _s())
-            n += 1
+        n += _launch_wgrads(entries, _s())
     del steal["pending"][:]
     return n
+
+
+def _c_overlap(g1: torch.Tensor, g2: torch.Tensor) -> bool:
+    """Do two (N, K) fp32 gradient views with unit column stride share an element?  The rule rtts_gemm_tn_grouped refuses
+    (csrc/gemm_tn.hip gt_c_overlap): element-exact for one row stride, interleaving spans of different strides count as overlapping."""
+    b1, b2 = g1.data_ptr(), g2.data_ptr()
+    e1 = b1 + ((g1.shape[0] - 1) * g1.stride(0) + g1.shape[1]) * 4
+    e2 = b2 + ((g2.shape[0] - 1) * g2.stride(0) + g2.shape[1]) * 4
+    if b2 >= e1 or b1 >= e2:
+        return False
+    if g1.stride(0) != g2.stride(0):
+        return True
+    lo, hi = (g1, g2) if b1 <= b2 else (g2, g1)
+    r, s = divmod((hi.data_ptr() - lo.data_ptr()) // 4, lo.stride(0))
+    return s < lo.shape[1] or (s + hi.shape[1] > lo.stride(0) and r + 1 < lo.shape[0])
+
+
+def _launch_wgrads(entries, stream: int) -> int:
+    """Launch queued (grad, dy, x) entries, in order, as rtts_gemm_tn_grouped calls on ``stream`` (see launch_groups: a new call
+    wherever an entry's gradient overlaps one already in the call).  -> launches made."""
+    groups = launch_groups(entries, _lib.GEMM_TN_MAX_GROUP, lambda a, b: _c_overlap(a[0], b[0]))
+    for group in groups:
+        arr = (_lib.GemmTnProblem * len(group))()
+        for e, (gv, dy, x) in zip(arr, group):
+            e.a, e.lda, e.b, e.ldb, e.c, e.ldc = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), gv.data_ptr(), gv.stride(0)
+            e.M, e.N, e.K, e.accumulate = dy.shape[0], dy.shape[1], x.shape[1], 1
+        ws = _slab_ws(group[0][1].device, stream)
+        _lib.call("rtts_gemm_tn_grouped", arr, len(group), ws.data_ptr(), ws.numel(), stream)
+    return len(groups)
 
 
 def _final_flush():
@@ -591,15 +630,10 @@ def flush_wgrad(colsums: bool = True, keys=None):
                 ev.record(steal["src_stream"])            # everything this stream has been given so far: the operands' producers
                 steal["pending"].append((ev, list(pending)))
                 del pending[:]
-            while pending:
-                group = pending[:_lib.GEMM_TN_MAX_GROUP]
-                del pending[:len(group)]
-                arr = (_lib.GemmTnProblem * len(group))()
-                for e, (gv, dy, x) in zip(arr, group):
-                    e.a, e.lda, e.b, e.ldb, e.c, e.ldc = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), gv.data_ptr(), gv.stride(0)
-                    e.M, e.N, e.K, e.accumulate = dy.shape[0], dy.shape[1], x.shape[1], 1
-                ws = _slab_ws(group[0][1].device, q.stream)
-                _lib.call("rtts_gemm_tn_grouped", arr, len(group), ws.data_ptr(), ws.numel(), q.stream)
+            if pending:
+                entries = list(pending)
+                del pending[:]
+                _launch_wgrads(entries, q.stream)
             for hook in FLUSH_HOOKS:       # other deferred gradient work (edges.py: the convolutions' dW re-layout)
                 hook(q)
 

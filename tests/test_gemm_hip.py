@@ -269,6 +269,39 @@ def test_grouped_launch_vs_float64(gpu):
         engine.gemm_group([dict(a=a1, w=w1)] * 5)
 
 
+def test_grouped_descriptor_alone_and_in_a_pair(gpu):
+    """One rtts_gemm_nt_grouped descriptor computes the same bits alone (n = 1) and in a group of two, with and without a bias;
+    epilogue 0 with a bias -- which a group (one run-time epilogue form for 0, 1 and 4) would add and a single problem would
+    ignore -- is refused in either form."""
+    from reformer_tts_amd import _lib, engine
+    g = torch.Generator(device=gpu).manual_seed(9)
+    a1, w1 = torch.randn(1536, 512, device=gpu, generator=g).bfloat16(), (torch.randn(256, 512, device=gpu, generator=g) * 0.05).bfloat16()
+    a2, w2 = torch.randn(768, 512, device=gpu, generator=g).bfloat16(), (torch.randn(128, 512, device=gpu, generator=g) * 0.05).bfloat16()
+    b1, b2 = torch.randn(256, device=gpu, generator=g), torch.randn(128, device=gpu, generator=g)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def run(descs):
+        outs = [torch.empty(a.shape[0], w.shape[0], dtype=torch.bfloat16, device=gpu) for a, w, _, _ in descs]
+        arr = (_lib.GemmNtProblem * len(descs))()
+        for e, (a, w, bias, epi), c in zip(arr, descs, outs):
+            engine._nt_problem(e, a, w, False, c, bias, epi)
+        _lib.call("rtts_gemm_nt_grouped", arr, len(descs), 0, s)
+        torch.cuda.synchronize()
+        return outs
+    plain, biased = (a1, w1, None, 0), (a2, w2, b2, 1)
+    alone = run([plain]) + run([biased])
+    pair = run([plain, biased])
+    for name, x, y, ref in (("plain", alone[0], pair[0], a1.double() @ w1.double().t()),
+                            ("bias", alone[1], pair[1], a2.double() @ w2.double().t() + b2.double())):
+        emax, _ = _rel(y, ref)
+        print(f"\n[gemm_nt descriptor {name}] alone == in a pair: {torch.equal(x, y)}; max err {emax:.2e} (tol {1.02 * BF16_HALF_ULP:.2e})")
+        assert torch.equal(x, y), name
+        assert emax <= 1.02 * BF16_HALF_ULP, (name, emax)
+    for descs in ([(a1, w1, b1, 0)], [(a1, w1, b1, 0), biased]):
+        with pytest.raises(_lib.RttsError, match="takes no bias"):
+            run(descs)
+
+
 @pytest.mark.parametrize("m,n,k,epi", [(12288, 2048, 512, "bias+relu"), (12288, 1024, 512, "plain"), (12288, 2048, 512, "kn+gate"),
                                        (12288, 1024, 512, "kn"), (6144, 2048, 256, "plain"), (12288, 4096, 512, "bias")])
 def test_persistent_tiles_are_bit_identical_to_one_tile_per_workgroup(gpu, m, n, k, epi):

@@ -464,6 +464,20 @@ def test_c_abi_rejects_bad_arguments_with_a_message(ops):
     qk = torch.zeros(1, 256, 128, dtype=torch.bfloat16, device="cuda")
     rot = torch.zeros(1, 64, 2, 2, device="cuda")
     st = torch.zeros(2, 2, 256, dtype=torch.int32, device="cuda")
+    # two weight gradients of one grouped launch that write the same C (buffers of the full size: refused before any launch)
+    c_tn = torch.zeros(128, 128, device="cuda")
+    twice = (_lib.GemmTnProblem * 2)()
+    for e in twice:
+        e.a, e.lda, e.b, e.ldb, e.c, e.ldc = qk.data_ptr(), 128, qk.data_ptr(), 128, c_tn.data_ptr(), 128
+        e.M, e.N, e.K, e.accumulate = 256, 128, 128, 1
+    # likewise two deferred column sums into one output, and two convolution weight-gradient re-layouts into one dw
+    cs_twice = (_lib.ColsumJob * 2)()
+    for j in cs_twice:
+        j.partial, j.out, j.nrows, j.n, j.ld = c_tn.data_ptr(), c_tn.data_ptr() + 4 * 128 * 127, 8, 128, 0
+    dwp, dw = torch.zeros(128, 5 * 128, device="cuda"), torch.zeros(128, 128, 5, device="cuda")
+    cv_twice = (_lib.ConvPermJob * 2)()
+    for j in cv_twice:
+        j.w, j.wp, j.Co, j.Ci, j.CP = dwp.data_ptr(), dw.data_ptr(), 128, 128, 128
     cases = [
         # dh != 64
         (("rtts_lsh_hash_sort", qk.data_ptr(), 128, rot.data_ptr(), 1, 1, 4, 256, 32, 2, 64, None, st.data_ptr(), None, s), "dh=32 unsupported"),
@@ -479,6 +493,10 @@ def test_c_abi_rejects_bad_arguments_with_a_message(ops):
         (("rtts_lsh_attn_fwd", qk.data_ptr(), qk.data_ptr(), 128, st.data_ptr(), None, 1, 2, 256, 64, 2, 64, 0, qk.data_ptr(), st.data_ptr(), 1.0, 0, None, s), "drop_p"),
         # weight-gradient GEMM: N not a multiple of 128
         (("rtts_gemm_tn", qk.data_ptr(), 96, qk.data_ptr(), 128, 256, 96, 128, st.data_ptr(), 128, 1, st.data_ptr(), 1 << 20, s), "128"),
+        # grouped weight-gradient GEMM: two problems writing overlapping parts of C would race
+        (("rtts_gemm_tn_grouped", twice, 2, None, 0, s), "overlapping"),
+        (("rtts_colsum_final_grouped", cs_twice, 2, s), "overlapping"),
+        (("rtts_conv_dw_unperm_grouped", cv_twice, 2, s), "overlapping"),
         # AdamW: n not a multiple of 4
         (("rtts_adamw_step", st.data_ptr(), st.data_ptr(), st.data_ptr(), st.data_ptr(), st.data_ptr(), 1022, None, st.data_ptr(), 0.9, 0.999, 1e-6,
           0.0, None, s), "multiple of 4"),

@@ -1000,6 +1000,52 @@ def test_two_forwards_before_the_first_backward_keep_their_own_state(gpu):
     assert rel <= 1e-6
 
 
+def test_one_backward_through_two_forwards_equals_two_backwards(gpu):
+    """``(run(b1) + run(b2)).backward()`` -- one backward through two forwards of one model, so the weight gradients of both
+    calls can be queued before one flush, one weight twice -- gives the gradients of ``run(b1).backward(); run(b2).backward()``
+    with the same randomness (up to the fp32 order in which the two contributions are summed)."""
+    from reformer_tts_amd.model.config import model_config_from_dict
+    from reformer_tts_amd.training import build_model, synthetic_batch
+    from reformer_tts_amd.model.loss import TTSLoss
+    from reformer_tts_amd import _seeds
+    from reformer_tts_amd.model.lsh_attention import LSHSelfAttention
+    cfg = model_ref.small_cfg()
+    cfg["enc_reformer_kwargs"]["attn_kwargs"]["implementation"] = "hip"
+    cfg["dec_reformer_kwargs"]["self_attn_kwargs"]["implementation"] = "hip"
+    torch.manual_seed(3)
+    model = build_model(model_config_from_dict(cfg), gpu).train()
+    b1 = synthetic_batch(2, 100, 256, seed=1, device=gpu)
+    b2 = synthetic_batch(2, 120, 256, seed=2, device=gpu)
+    loss_fn = TTSLoss(torch.tensor(5.0, device=gpu))
+
+    def run(batch):
+        out = model(batch["phonemes"], batch["spectrogram"][:, :-1])
+        return loss_fn(out[0].clone(), out[1].clone(), out[2], batch["spectrogram"][:, 1:], batch["stop_tokens"].unsqueeze(-1),
+                       batch["loss_mask"])[0]
+
+    def grads():
+        return torch.cat([p.grad.flatten() for p in model.parameters() if p.grad is not None]).clone()
+
+    def restart_randomness():
+        _seeds.reset(0)
+        torch.manual_seed(11)
+        for mm in model.modules():
+            if isinstance(mm, LSHSelfAttention):
+                mm._gen = None
+        model.zero_grad(set_to_none=True)
+
+    restart_randomness()
+    run(b1).backward()
+    run(b2).backward()
+    want = grads()
+    restart_randomness()
+    (run(b1) + run(b2)).backward()
+    got = grads()
+    rel = float((got - want).norm() / want.norm())
+    print(f"\n[one backward through two forwards] rel-L2 difference from two backwards {rel:.3e} (tol 1e-6)")
+    assert rel <= 1e-6
+
+
 def test_dropout_masks_of_neighbouring_sites_and_ranks_are_unrelated(gpu):
     """Per-site seeds are consecutive multiples of 2654435761 (= the hash's index multiplier) and per-rank step seeds
     differ by a constant: neither may turn one site's (rank's) mask into a shifted copy of another's.  Independent masks
