@@ -233,6 +233,14 @@ int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, c
 /* drop_p = nn.MultiheadAttention's dropout on the normalised attention probabilities (config #4: 0.15); the keep
  * decision of (head, query, key) is hash(seed + *seed_dev, index), identical in the forward and the backward. */
 int rtts_sum_slabs(const void* part, int nslabs, int64_t n, void* out, void* stream);
+/* Head-averaged attention probabilities of the same call (eval mode): a[b, i, j] = (1/H) sum_h exp(s_h(i, j) - lse_h(i)),
+ * s_h = q_h . k_h / sqrt(dh), exactly 0 where kvalid == 0; a f32 (B,Tq,Tk) row stride ld_a (>= Tk, % 4 == 0, 16-byte
+ * aligned).  lse = what rtts_xattn_fwd wrote for the same q / kv / kvalid, so every head's row sums to 1 as in its o.
+ * The weights nn.MultiheadAttention returns and MultiheadAttentionWrapper appends to the decoder's attention_matrices_
+ * in eval mode (reference reformer_tts/model/reformer.py:161-186, returned by ReformerDec.forward :139-158 and
+ * ReformerTTS.forward reformer_tts.py:103-143).  Envelope of rtts_xattn_fwd. */
+int rtts_xattn_probs_mean(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
+                          const float* lse, int B, int H, int Tq, int Tk, int dh, float* a, int64_t ld_a, void* stream);
 
 /* ---- convolutional edges (prenet / postnet) and the loss ------------------------------------------
  * Reference reformer_tts/model/modules.py:8-61 (EncoderPreNet), :103-169 (PostConvNet); loss.py:28-53.

@@ -566,6 +566,106 @@ extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64
     return 0;
 }
 
+// ------------------------------------------------------------------------------ head-averaged probabilities (eval)
+// a[b, i, j] = (1/H) sum_h exp(s_h(i, j) - lse_h(i)), s_h = q_h . k_h / sqrt(dh); masked keys exactly 0.  What
+// nn.MultiheadAttention returns as its (head-averaged, fp32) weights and MultiheadAttentionWrapper collects in eval mode
+// (reference reformer_tts/model/reformer.py:161-186).  The forward's lse (full-key log-normaliser) makes every key chunk
+// independent: workgroup = (b, 128-query block, 128-key chunk), four waves of 32 queries, the H heads walked inside so the head
+// sum stays in registers (no atomics, no cross-workgroup reduction).  K of head h + 1 arrives in LDS (DMA, double buffer) while
+// head h is worked; Q fragments and lse come straight from global (each wave reads only its own queries).
+// Layout as the forward's S^T = K Q^T: lane (r, hh) = query r, register 4 g + j = key 8 g + 4 hh + j of a 32-key tile, so a
+// register group is 4 consecutive keys of one row of `a` = one 16-byte store; the 4 groups of a tile complete 32 rows x 128 B.
+#define XP_KC 128     // keys per workgroup
+__global__ __launch_bounds__(256) void xattn_probs_mean_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
+                                                               int64_t ld_kv, const uint8_t* __restrict__ kvalid, const float* __restrict__ lse,
+                                                               int H, int Tq, int Tk, float* __restrict__ a, int64_t ld_a) {
+    constexpr int NKT = XP_KC / 32;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x [XP_KC][128 B] swizzled (xa_off), kval
+    const int nqb = Tq / XA_QB, nkc = Tk / XP_KC;
+    const uint32_t wi = xcd_remap(blockIdx.x, gridDim.x);       // (b, query block, key chunk), key chunk fastest: the chunks of a
+    const int kc = wi % nkc, qb = (wi / nkc) % nqb, b = wi / (nkc * nqb);   // query block share its Q rows in one XCD's L2
+    const int c0 = kc * XP_KC;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, hh = lane >> 5;
+    const int qrow = qb * XA_QB + wave * 32 + r;
+    const bf16_t* kbase = kv + ((size_t)b * Tk + c0) * ld_kv;
+
+    auto stage_k = [&](int h, unsigned char* dst) {
+        constexpr int ITERS = XP_KC * 8 / 256;
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int rowb = it * 32 + wave * 8;
+            const int row = rowb + (lane >> 3);
+            const int lp = (lane & 7) ^ xa_sw(row);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + (size_t)row * ld_kv + h * XA_DH + lp * 8),
+                                             (RTTS_LDS void*)(dst + rowb * 128), 16, 0, 0);
+        }
+    };
+    stage_k(0, smem);
+
+    int* kval = reinterpret_cast<int*>(smem + 2 * XP_KC * 128);  // key validity of the chunk (the head loop's first barrier publishes it)
+    for (int j = tid; j < XP_KC; j += 256) kval[j] = kvalid ? (int)kvalid[(size_t)b * Tk + c0 + j] : 1;
+
+    constexpr float kLog2e = 1.4426950408889634f;
+    const float c = 0.125f * kLog2e;                            // 1 / sqrt(64), in the exp2 domain
+    f32x16 acc[NKT];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) acc[kt] = f32x16{0};
+    const bf16_t* qptr = q + ((size_t)b * Tq + qrow) * ld_q;
+#pragma unroll 1
+    for (int h = 0; h < H; ++h) {
+        bf16x8 qf[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qptr + h * XA_DH + ks * 16 + 8 * hh);
+        const float l2 = lse[((size_t)b * H + h) * Tq + qrow] * kLog2e;
+        __syncthreads();            // K of head h is in LDS, and every wave is done with the buffer head h - 1 read
+        if (h + 1 < H) stage_k(h + 1, smem + ((h + 1) & 1) * (XP_KC * 128));
+        const unsigned char* Ks = smem + (h & 1) * (XP_KC * 128);
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            f32x16 s = {0};
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + xa_off(kt * 32 + r, ks * 2 + hh));
+                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s, 0, 0, 0);
+            }
+            // exp(s / 8 - lse) as one fma and v_exp_f32 (2^x); masked keys are zeroed at the store, whatever they sum to here
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[kt][i] += __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, -l2));
+        }
+    }
+
+    const float inv_h = 1.f / (float)H;
+    float* arow = a + ((size_t)b * Tq + qrow) * ld_a + c0 + 4 * hh;
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int4 vv = *reinterpret_cast<const int4*>(kval + kt * 32 + 8 * g + 4 * hh);
+            uint4 v;
+            v.x = __float_as_uint(vv.x ? acc[kt][4 * g] * inv_h : 0.f);
+            v.y = __float_as_uint(vv.y ? acc[kt][4 * g + 1] * inv_h : 0.f);
+            v.z = __float_as_uint(vv.z ? acc[kt][4 * g + 2] * inv_h : 0.f);
+            v.w = __float_as_uint(vv.w ? acc[kt][4 * g + 3] * inv_h : 0.f);
+            rtts_store16_out(arow + kt * 32 + 8 * g, v);
+        }
+}
+
+extern "C" int rtts_xattn_probs_mean(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const float* lse,
+                                     int B, int H, int Tq, int Tk, int dh, float* a, int64_t ld_a, void* stream) {
+    RTTS_ENTER(stream);
+    RTTS_REQUIRE(q && kv && lse && a, "rtts_xattn_probs_mean: q, kv, lse and a must not be NULL");
+    if (xa_check("rtts_xattn_probs_mean", B, H, Tq, Tk, dh, ld_q, ld_kv)) return -1;
+    RTTS_REQUIRE(ld_a >= Tk && ld_a % 4 == 0, "rtts_xattn_probs_mean: ld_a=%lld must be >= T_k=%d and a multiple of 4", (long long)ld_a, Tk);
+    RTTS_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)a) & 15) == 0, "rtts_xattn_probs_mean: q, kv and a must be 16-byte aligned");
+    const size_t nwg = (size_t)B * (Tq / XA_QB) * (Tk / XP_KC);
+    RTTS_REQUIRE(nwg <= 0x7fffffff, "rtts_xattn_probs_mean: grid too large");
+    hipLaunchKernelGGL(xattn_probs_mean_kernel, dim3((unsigned)nwg), dim3(256), 2 * XP_KC * 128 + XP_KC * 4, (hipStream_t)stream, (const bf16_t*)q, ld_q,
+                       (const bf16_t*)kv, ld_kv, kvalid, lse, H, Tq, Tk, a, ld_a);
+    RTTS_LAUNCH_CHECK("rtts_xattn_probs_mean");
+    return 0;
+}
+
 extern "C" int rtts_sum_slabs(const void* part, int nslabs, int64_t n, void* out, void* stream) {
     RTTS_ENTER(stream);
     RTTS_REQUIRE(part && out && nslabs > 0 && n > 0 && n % 8 == 0, "rtts_sum_slabs: n must be a positive multiple of 8");

@@ -876,12 +876,26 @@ class FFNExec:
         return post, ln_bwd(dxn, inp, mean, rstd, self.norm, d_inp, next_cast, dx_in=d_src, join=join)
 
 
+def xattn_probs_mean(q, kv, kvalid, lse, b, h, t, tk, out=None):
+    """Head-averaged attention probabilities of one ``rtts_xattn_fwd`` call (its q, kv, kvalid and lse): (b, t, tk) fp32,
+    exactly 0 at padded keys -- the weights ``nn.MultiheadAttention`` returns (``reformer.py:161-186``).  ``out``: a
+    (b, t, >= tk) fp32 view with unit column stride to write into instead."""
+    e = q.shape[-1]
+    a = torch.empty(b, t, tk, dtype=torch.float32, device=q.device) if out is None else out
+    _lib.call("rtts_xattn_probs_mean", q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0),
+              None if kvalid is None else kvalid.data_ptr(), lse.data_ptr(), b, h, t, tk, e // h, a.data_ptr(), a.stride(1), _s())
+    return a
+
+
 class XAttnExec:
-    """WithNorm(LayerNorm, MultiheadAttentionWrapper): acc += out_proj(MHA(q=LN(inp), k=v=keys))."""
+    """WithNorm(LayerNorm, MultiheadAttentionWrapper): acc += out_proj(MHA(q=LN(inp), k=v=keys)).  In eval mode with
+    ``collect_attention`` (``ReformerDec.collect_attention``) the head-averaged probabilities go to the wrapper's
+    ``attention_matrices_``, as on the general path."""
 
     def __init__(self, withnorm):
         self.norm = withnorm.norm
         self.mha = withnorm.fn.layer
+        self.wrapper = withnorm.fn
         self._own_slot = {}   # per-call keys: stash ((o, lse)), g (f(x)), pdrop ((p, seed) of the dropout on the attention
         #                       probabilities -- NOT an output dropout)
 
@@ -916,11 +930,14 @@ class XAttnExec:
         return xn, mean, rstd, w, q, kv, o, lse, g, tk
 
     def forward(self, acc, inp, b, t, keys_bf16=None, kvalid=None, pre=None, next_norm=None, slot=None, keep_streams=False,
-                fresh_acc=False, **_):
+                fresh_acc=False, collect_attention=False, **_):
         slot = self._own_slot if slot is None else slot
         p = self.mha.dropout if self.mha.training else 0.0
         pdrop = (p, next_seed()) if p > 0.0 else None
-        xn, mean, rstd, _, q, kv, o, lse, g, _ = self._internals(inp, b, t, keys_bf16, kvalid, pre=pre, drop=pdrop)
+        xn, mean, rstd, _, q, kv, o, lse, g, tk = self._internals(inp, b, t, keys_bf16, kvalid, pre=pre, drop=pdrop)
+        mats = self.wrapper.attention_matrices_
+        if collect_attention and not self.wrapper.training and mats is not None:
+            mats.append(xattn_probs_mean(q, kv, kvalid, lse, b, self.mha.num_heads, t, tk))
         slot.clear()
         slot.update(stash=(o, lse) if STASH_ATTENTION else None, g=g if STASH_BLOCK_OUTPUT else None, pdrop=pdrop,
                     proj=(q, kv) if STASH_PROJECTIONS else None)
@@ -1085,6 +1102,8 @@ def _step_kwargs(kind, kwargs, extra, cache):
         out["mask"] = _mask_u8(kwargs["input_mask"], cache)
     if "key" in kwargs:
         out.update(extra)
+        if kwargs.get("collect_attention"):
+            out["collect_attention"] = True
     return out, None
 
 

@@ -124,7 +124,13 @@ class ReformerEnc(nn.Module):
 
 
 class ReformerDec(nn.Module):
-    """``reformer.py:98-158``: per layer [LSH self-attn, swap, cross-attn, swap, FFN, swap]."""
+    """``reformer.py:98-158``: per layer [LSH self-attn, swap, cross-attn, swap, FFN, swap].  Returns the output and
+    ``attention_matrices_``: in eval mode one head-averaged (B, T, T_k) fp32 matrix per layer, as the reference.
+    ``collect_attention = False`` switches the collection off on the explicit executor's eval path (``fused_in_eval``),
+    where it costs one kernel launch per layer; generation and the default validation do so.  The general eval path
+    always collects, as the reference does."""
+
+    collect_attention = True
 
     def __init__(self, dim: int, depth: int, ff_chunks: int, attn_kwargs: Dict, self_attn_kwargs: Dict, ff_kwargs: Dict):
         super().__init__()
@@ -152,6 +158,7 @@ class ReformerDec(nn.Module):
             kwargs["key"] = keys
             kwargs["value"] = keys
             kwargs["key_padding_mask"] = key_padding_mask
+            kwargs["collect_attention"] = self.collect_attention
         for kwargs in kwargs_list[::6]:
             kwargs["input_mask"] = input_mask
         self.attention_matrices_.clear()

@@ -218,6 +218,8 @@ class ReformerTTS(nn.Module):
         for st_ in stacks:
             st_.fused_in_eval = True         # the stacks' forward through the explicit executor: with the no-grad edges
             #                                  (edges.py) a generation step runs no library GEMM at all
+        was_collect = self.dec.reformer.collect_attention
+        self.dec.reformer.collect_attention = False          # the alignments of a frame are discarded: no launch for them
         try:
             dev = self.dec.mel_linear.weight.device
             phonemes = phonemes.to(dev)
@@ -274,6 +276,7 @@ class ReformerTTS(nn.Module):
         finally:
             for st_, f in zip(stacks, was_fused):
                 st_.fused_in_eval = f
+            self.dec.reformer.collect_attention = was_collect
             self.train(was_training)
 
     @torch.no_grad()
@@ -296,6 +299,8 @@ class ReformerTTS(nn.Module):
         stacks = (self.enc.reformer.layers, self.dec.reformer.layers)
         for st_ in stacks:
             st_.fused_in_eval = True                                 # executor forward: ~half the launches per frame
+        was_collect = self.dec.reformer.collect_attention
+        self.dec.reformer.collect_attention = False                  # nothing of the alignments is captured into the graphs
         try:
             dev = self.dec.mel_linear.weight.device
             phonemes = phonemes.to(dev)
@@ -379,4 +384,5 @@ class ReformerTTS(nn.Module):
         finally:
             for st_ in stacks:
                 st_.fused_in_eval = False
+            self.dec.reformer.collect_attention = was_collect
             self.train(was_training)

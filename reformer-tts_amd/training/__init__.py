@@ -1,1 +1,1 @@
-from .trainer import Trainer, build_model, synthetic_batch  # noqa: F401
+from .trainer import Trainer, build_model, synthetic_batch, trim_attention_matrices  # noqa: F401

@@ -50,6 +50,18 @@ def synthetic_batch(batch: int, text_len: int, mel_len: int, n_mels: int = 80, d
     return {k: v.to(device) for k, v in out.items()} if device is not None else out
 
 
+def trim_attention_matrices(attention_matrices: List[torch.Tensor], stop_tokens: torch.Tensor) -> List[List[torch.Tensor]]:
+    """``LitReformerTTS.trim_attention_matrices`` (``wrappers.py:316-325``): for sample i, every layer's (B, T, T_k) matrix cut to
+    its first ``argmax(stop_tokens[i])`` rows -> [[layer matrix (stop_i, T_k)] per sample].  The columns keep the padded text
+    length; the slices are views of the matrices, where they are.  A slice length is a host integer: the stop indices are
+    read to the host once for the whole batch (the reference reads them once per sample)."""
+    stop_indexes = stop_tokens.argmax(dim=1)
+    result = []
+    for i, stop_index in enumerate(stop_indexes.tolist()):
+        result.append([matrix[i, :stop_index, :] for matrix in attention_matrices])
+    return result
+
+
 def stop_mae(stop_logits: torch.Tensor, stop_tokens: torch.Tensor) -> torch.Tensor:
     """Mean absolute error, in frames, of the predicted end of the utterance (``wrappers.py:74-80``): the first frame whose
     stop logit is positive -- frame 0 when there is none -- against the frame of the one-hot stop token."""
@@ -603,24 +615,34 @@ class Trainer:
         return total / n
 
     @torch.no_grad()
-    def validate(self, batch):
+    def validate(self, batch, return_attention: bool = False):
         """``LitReformerTTS.validation_step`` (``wrappers.py:107-140``): teacher-forced forward in eval mode (BatchNorm
         running statistics, no dropout), the four losses; the stacks run through the explicit executor's forward.
-        -> (total, raw, post, stop, stop_mae) device scalars.  Parameters and optimizer state are untouched."""
+        -> (total, raw, post, stop, stop_mae) device scalars.  Parameters and optimizer state are untouched.
+
+        ``return_attention=True``: also the decoder's encoder-decoder alignments, trimmed as ``validation_step`` trims them
+        (``trim_attention_matrices``): -> (total, raw, post, stop, stop_mae, per-sample lists of per-layer (stop index, T_k
+        padded) fp32 matrices), all on the device.  The five scalars are the same bits either way."""
         was_training = self.model.training
         stacks = (self.model.enc.reformer.layers, self.model.dec.reformer.layers)
+        dec = self.model.dec.reformer
+        was_collect = dec.collect_attention
         self.model.eval()
         for st in stacks:
             st.fused_in_eval = True
+        dec.collect_attention = bool(return_attention)
         try:
             spec = batch["spectrogram"]
-            raw, post, stop, _ = self.model(batch["phonemes"], spec[:, :-1], spectrogram_mask=batch["loss_mask"].mean(dim=-1))
+            raw, post, stop, mats = self.model(batch["phonemes"], spec[:, :-1], spectrogram_mask=batch["loss_mask"].mean(dim=-1))
             stop2 = stop.view(stop.shape[0], -1)
-            return (*self.loss(raw, post, stop2, spec[:, 1:], batch["stop_tokens"], batch["loss_mask"]),
-                    stop_mae(stop2, batch["stop_tokens"]))
+            out = (*self.loss(raw, post, stop2, spec[:, 1:], batch["stop_tokens"], batch["loss_mask"]), stop_mae(stop2, batch["stop_tokens"]))
+            if return_attention:
+                out = (*out, trim_attention_matrices(list(mats), batch["stop_tokens"]))
+            return out
         finally:
             for st in stacks:
                 st.fused_in_eval = False
+            dec.collect_attention = was_collect
             self.model.train(was_training)
 
     # ------------------------------------------------------------------ checkpoint / resume
