@@ -33,13 +33,19 @@ class _LossFn(torch.autograd.Function):
         grads = torch.empty(2 * rows * nm + rows, **f32)
         d_raw, d_post, d_stop = grads[:rows * nm], grads[rows * nm:2 * rows * nm], grads[2 * rows * nm:]
         losses, ws = torch.empty(4, **f32), torch.empty(1536, **f32)
+        # the kernel stores the gradients of sum(kw * part): a part whose weight is 0 is stored at weight 1 instead, so that a
+        # backward through that part alone still finds its gradient (w * g would be 0 and g could not be recovered)
+        kw = tuple(float(w) if w != 0.0 else 1.0 for w in weights)
         _lib.call("rtts_tts_loss", r2.data_ptr(), p2.data_ptr(), nm, tgt.data_ptr(), msk.data_ptr(), s1.data_ptr(), 1, tst.data_ptr(),
-                  rows, nm, kind, float(pos_weight), float(weights[0]), float(weights[1]), float(weights[2]), d_raw.data_ptr(),
+                  rows, nm, kind, float(pos_weight), kw[0], kw[1], kw[2], d_raw.data_ptr(),
                   d_post.data_ptr(), nm, d_stop.data_ptr(), losses.data_ptr(), ws.data_ptr(), l, l, None, 0, 0, 0, 0, 0,
                   None, 0, 0, torch.cuda.current_stream().cuda_stream)
+        total = losses[0]
+        if kw != tuple(float(w) for w in weights):       # the kernel's total counted the zero-weight parts at weight 1
+            total = weights[0] * losses[1] + weights[1] * losses[2] + weights[2] * losses[3]
         ctx.save_for_backward(grads)
         ctx.meta = (raw.shape, stop.shape, weights, raw.dtype, post.dtype, stop.dtype)
-        return losses[0], losses[1], losses[2], losses[3]
+        return total, losses[1], losses[2], losses[3]
 
     @staticmethod
     def backward(ctx, g_total, g_raw, g_post, g_stop):
@@ -48,8 +54,11 @@ class _LossFn(torch.autograd.Function):
         n = shape[0] * shape[1] * shape[2]
 
         def scale(g_part, weight):
-            # the kernel stored d(total)/d(prediction) = weight * d(part)/d(prediction)
-            if g_part is None or weight == 0.0:
+            # the kernel stored d(total)/d(prediction) = weight * d(part)/d(prediction); for weight 0 it stored d(part)/d(prediction),
+            # which the total does not reach
+            if weight == 0.0:
+                return torch.zeros_like(g_total) if g_part is None else g_part
+            if g_part is None:
                 return g_total
             return g_total + g_part / weight
 

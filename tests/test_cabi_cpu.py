@@ -84,3 +84,14 @@ def test_model_refuses_to_run_off_the_gpu():
         model(batch["phonemes"], batch["spectrogram"][:, :-1])
     with pytest.raises(_lib.RttsError, match="GPU only"):
         model.infer(batch["phonemes"], max_len=90)
+
+
+def test_row_kernel_widths_are_all_tested():
+    """tests/test_rows_hip.py's WIDTHS is exactly the width list of FR_DISPATCH_D in csrc/fused_rows.hip: a width added to the
+    dispatch without its tests fails here."""
+    src = open(os.path.join(ROOT, "reformer-tts_amd", "csrc", "fused_rows.hip")).read()
+    body = re.search(r"#define FR_DISPATCH_D\(d, CALL\)(.*?)default:", src, flags=re.S).group(1)
+    widths = tuple(int(w) for w in re.findall(r"case (\d+):", body))
+    tests = open(os.path.join(ROOT, "tests", "test_rows_hip.py")).read()
+    listed = re.search(r"^WIDTHS = \(([^)]*)\)", tests, flags=re.M).group(1)
+    assert widths and tuple(int(w) for w in listed.split(",") if w.strip()) == widths
