@@ -506,6 +506,24 @@ int rtts_sw_depthwise_k3(const float* x, const float* w, const float* bias, int 
 int rtts_sw_gate(const void* pw, const void* cond, int64_t ld_cond, int cond_offset, int upsample, int B, int L, int Lm, int C,
                  void* acts, void* stream);
 int rtts_sw_coupling_inv(float* audio, int64_t ld_audio, const float* wn_out, int64_t rows, int half, void* stream);
+/* Ragged batches (SqueezeWave.infer_ragged / capture_ragged): the utterances of a batch laid end to end as rows, each vocoded
+ * as the reference vocodes one utterance trimmed at its stop index (cli.py:241 `spectrogram[:, :, :stop]`, then
+ * squeeze_wave/modules.py:334-376 per utterance).  moff is a DEVICE int32 table of nseg + 1 non-decreasing mel-frame
+ * offsets (1 <= nseg <= 1024), read when the kernel runs: utterance s owns mel rows [moff[s], moff[s+1]) and audio rows
+ * [upsample * moff[s], upsample * moff[s+1]).  Rows past upsample * moff[nseg], up to the capacity `rows`, are padding: they
+ * are computed, but no real row reads them.
+ *   rtts_sw_depthwise_k3_seg  rtts_sw_depthwise_k3 over `rows` packed rows: each segment has its own zero padding, and its
+ *                         first / last row gets edge_lo / edge_hi as row 0 / L-1 does in the uniform form (which is the
+ *                         same kernel with moff[s] = s * L / upsample, bit for bit)
+ *   rtts_sw_gate          needs no table: audio row r of segment s reads conditioning row moff[s] + (r - upsample * moff[s]) /
+ *                         upsample = r / upsample, which the uniform entry computes with B = 1, L = rows, Lm = rows / upsample
+ *   rtts_sw_pack_mel      dst (rows, ld_dst) fp32 = the packed mel rows the conditioning GEMM reads: row moff[s] + t = frame t
+ *                         of mel[s] (B, n_mel, L) read through its element strides, for t < moff[s+1] - moff[s] (and t < L);
+ *                         every other row up to `rows` is zero */
+int rtts_sw_depthwise_k3_seg(const float* x, const float* w, const float* bias, const int32_t* moff, int nseg, int upsample,
+                             int64_t rows, int C, void* y, const float* edge_lo, const float* edge_hi, void* stream);
+int rtts_sw_pack_mel(const float* mel, int64_t stride_b, int64_t stride_c, int64_t stride_t, int L, int n_mel, const int32_t* moff,
+                     int nseg, int64_t rows, float* dst, int64_t ld_dst, void* stream);
 int rtts_sw_coupling_inv1x1(const float* audio, int64_t ld_audio, const float* wn_out, int64_t ld_wn, const float* winv, int n,
                             int64_t rows, float* out, int64_t ld_out, void* stream);
 

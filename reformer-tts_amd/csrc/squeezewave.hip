@@ -14,30 +14,70 @@ static inline unsigned sw_grid(size_t items) {
     return (unsigned)b;
 }
 
+// Segments of packed rows (SqueezeWave.infer_ragged): utterances laid end to end, segment s = mel frames [moff[s], moff[s+1])
+// of a device int32 table of nseg + 1 non-decreasing offsets, audio rows [up * moff[s], up * moff[s+1]).  The table is read
+// when the kernel runs (a replayed hipGraph takes new lengths); at most SW_MAX_SEGMENTS segments (it is staged in LDS).
+#define SW_MAX_SEGMENTS 1024
+
+// [a, e) = the rows of the segment that holds `row`: between the largest row offset <= row and the next one.  Rows before
+// up * moff[0] and from up * moff[nseg] on (the capacity padding) form segments of their own.  The bracket is clamped to
+// [0, rows) and around `row`, so even a malformed table never sends a read outside the buffer.
+__device__ __forceinline__ void sw_segment_of(long long row, const int* s_off, int nseg, int up, long long rows, long long& a, long long& e) {
+    int lo = 0, hi = nseg + 1;                         // upper bound: the first offset above row
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)up * s_off[mid] <= row) lo = mid + 1;
+        else hi = mid;
+    }
+    a = lo > 0 ? (long long)up * s_off[lo - 1] : 0;
+    e = lo <= nseg ? (long long)up * s_off[lo] : rows;
+    a = a < 0 ? 0 : (a > row ? row : a);
+    e = e > rows ? rows : (e <= row ? row + 1 : e);
+}
+
 // y[b][l][c] = bias[c] + sum_k w[c][k] * x[b][l + k - 1][c]   (kernel 3, zero padding), x fp32 -> y bf16; 4 channels/thread.
 // edge_lo / edge_hi (may be null): per-channel constants subtracted at l = 0 / l = L-1 -- with an eval-mode BatchNorm folded
 // into w and bias, the reference's zero padding pads bn(x), so the folded constant must not be counted for the missing tap.
+// SEG = false: B sequences of L rows (moff unused); SEG = true: the segments of the offset table moff (L unused), each with
+// its own zero padding and edge corrections.  Both read and compute exactly the same taps for a row of the same sequence.
+template <bool SEG>
 __global__ __launch_bounds__(SW_THREADS) void sw_depthwise_k3_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                      const float* __restrict__ bias, int L, int C, size_t n4,
                                                                      bf16_t* __restrict__ y, const float* __restrict__ edge_lo,
-                                                                     const float* __restrict__ edge_hi) {
+                                                                     const float* __restrict__ edge_hi, const int* __restrict__ moff,
+                                                                     int nseg, int up) {
     const int c4 = C / 4;
+    __shared__ int s_off[SEG ? SW_MAX_SEGMENTS + 1 : 1];
+    if (SEG) {
+        for (int i = threadIdx.x; i <= nseg; i += blockDim.x) s_off[i] = moff[i];
+        __syncthreads();
+    }
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % c4) * 4;
         const size_t row = i / c4;
-        const int l = (int)(row % L);
+        bool first, last;
+        if (SEG) {
+            long long a, e;
+            sw_segment_of((long long)row, s_off, nseg, up, (long long)(n4 / c4), a, e);
+            first = (long long)row == a;
+            last = (long long)row + 1 == e;
+        } else {
+            const int l = (int)(row % L);
+            first = l == 0;
+            last = l + 1 == L;
+        }
         const float4 mid = *reinterpret_cast<const float4*>(x + row * C + c);
         float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-        if (l > 0) lo = *reinterpret_cast<const float4*>(x + (row - 1) * C + c);
-        if (l + 1 < L) hi = *reinterpret_cast<const float4*>(x + (row + 1) * C + c);
+        if (!first) lo = *reinterpret_cast<const float4*>(x + (row - 1) * C + c);
+        if (!last) hi = *reinterpret_cast<const float4*>(x + (row + 1) * C + c);
         const float a[4] = {lo.x, lo.y, lo.z, lo.w}, m[4] = {mid.x, mid.y, mid.z, mid.w}, h[4] = {hi.x, hi.y, hi.z, hi.w};
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float* wc = w + (size_t)(c + j) * 3;
             o[j] = __builtin_fmaf(wc[0], a[j], __builtin_fmaf(wc[1], m[j], __builtin_fmaf(wc[2], h[j], bias[c + j])));
-            if (edge_lo && l == 0) o[j] -= edge_lo[c + j];
-            if (edge_hi && l + 1 == L) o[j] -= edge_hi[c + j];
+            if (edge_lo && first) o[j] -= edge_lo[c + j];
+            if (edge_hi && last) o[j] -= edge_hi[c + j];
         }
         uint2 pk;
         pk.x = pack_bf16x2(o[0], o[1]);
@@ -47,7 +87,8 @@ __global__ __launch_bounds__(SW_THREADS) void sw_depthwise_k3_kernel(const float
 }
 
 // acts[m][c] = tanh(pw[m][c] + cond[r][off + c]) * sigmoid(pw[m][C + c] + cond[r][off + C + c]),  r = (b, l / up):
-// the per-layer slice of the mel conditioning, nearest-neighbour upsampled; 8 channels per thread
+// the per-layer slice of the mel conditioning, nearest-neighbour upsampled; 8 channels per thread.  Packed rows need no
+// table here: audio row m of segment s reads moff[s] + (m - up * moff[s]) / up = m / up, the B = 1 case over all rows.
 __global__ __launch_bounds__(SW_THREADS) void sw_gate_kernel(const bf16_t* __restrict__ pw, const bf16_t* __restrict__ cond, int64_t ld_cond,
                                                              int off, int up, int L, int Lm, int C, size_t n8, bf16_t* __restrict__ acts) {
     const int c8 = C / 8;
@@ -76,6 +117,35 @@ __global__ __launch_bounds__(SW_THREADS) void sw_gate_kernel(const bf16_t* __res
     }
 }
 
+// Packed mel rows for the ragged vocoder: dst[r][c] (fp32, row stride ld_dst) = mel[s][c][r - moff[s]] for the frames r of
+// segment s, zero in every other row up to `rows` (the capacity) and wherever the source frame would lie past L.  mel is read
+// through its three element strides (any layout of (B, n_mel, L)); one thread per output element, channels fastest.
+__global__ __launch_bounds__(SW_THREADS) void sw_pack_mel_kernel(const float* __restrict__ mel, int64_t sb, int64_t sc, int64_t st, int L,
+                                                                 int n_mel, const int* __restrict__ moff, int nseg, long long rows,
+                                                                 float* __restrict__ dst, int64_t ld_dst) {
+    __shared__ int s_off[SW_MAX_SEGMENTS + 1];
+    for (int i = threadIdx.x; i <= nseg; i += blockDim.x) s_off[i] = moff[i];
+    __syncthreads();
+    const size_t n = (size_t)rows * n_mel;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const long long r = (long long)(i / n_mel);
+        const int c = (int)(i % n_mel);
+        int lo = 0, hi = nseg + 1;                     // s = (first offset above r) - 1
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= r) lo = mid + 1;
+            else hi = mid;
+        }
+        const int s = lo - 1;
+        float v = 0.f;
+        if (s >= 0 && s < nseg && r < s_off[s + 1]) {
+            const long long t = r - s_off[s];
+            if (t < L) v = mel[(int64_t)s * sb + (int64_t)c * sc + t * st];
+        }
+        dst[r * ld_dst + c] = v;
+    }
+}
+
 // inverse affine coupling, in place on the second half of the channels: a1 = (a1 - b) / exp(s), wn = [s | b] (fp32)
 __global__ __launch_bounds__(SW_THREADS) void sw_coupling_inv_kernel(float* __restrict__ audio, int64_t ld_audio, const float* __restrict__ wn,
                                                                      int half, size_t n) {
@@ -93,8 +163,22 @@ extern "C" int rtts_sw_depthwise_k3(const float* x, const float* w, const float*
     RTTS_ENTER(stream);
     RTTS_REQUIRE(x && w && bias && y && B > 0 && L > 0 && C > 0 && C % 4 == 0, "rtts_sw_depthwise_k3: bad arguments (C %% 4 == 0)");
     const size_t n4 = (size_t)B * L * C / 4;
-    hipLaunchKernelGGL(sw_depthwise_k3_kernel, dim3(sw_grid(n4)), dim3(SW_THREADS), 0, (hipStream_t)stream, x, w, bias, L, C, n4, (bf16_t*)y, edge_lo, edge_hi);
+    hipLaunchKernelGGL(sw_depthwise_k3_kernel<false>, dim3(sw_grid(n4)), dim3(SW_THREADS), 0, (hipStream_t)stream, x, w, bias, L, C, n4, (bf16_t*)y,
+                       edge_lo, edge_hi, (const int*)nullptr, 0, 1);
     RTTS_LAUNCH_CHECK("rtts_sw_depthwise_k3");
+    return 0;
+}
+
+extern "C" int rtts_sw_depthwise_k3_seg(const float* x, const float* w, const float* bias, const int32_t* moff, int nseg, int upsample,
+                                        int64_t rows, int C, void* y, const float* edge_lo, const float* edge_hi, void* stream) {
+    RTTS_ENTER(stream);
+    RTTS_REQUIRE(x && w && bias && y && moff && rows > 0 && C > 0 && C % 4 == 0 && upsample >= 1 && rows % upsample == 0,
+                 "rtts_sw_depthwise_k3_seg: bad arguments (C %% 4 == 0, rows a multiple of upsample)");
+    RTTS_REQUIRE(nseg >= 1 && nseg <= SW_MAX_SEGMENTS, "rtts_sw_depthwise_k3_seg: 1..%d segments (got %d)", SW_MAX_SEGMENTS, nseg);
+    const size_t n4 = (size_t)rows * C / 4;
+    hipLaunchKernelGGL(sw_depthwise_k3_kernel<true>, dim3(sw_grid(n4)), dim3(SW_THREADS), 0, (hipStream_t)stream, x, w, bias, 0, C, n4, (bf16_t*)y,
+                       edge_lo, edge_hi, (const int*)moff, nseg, upsample);
+    RTTS_LAUNCH_CHECK("rtts_sw_depthwise_k3_seg");
     return 0;
 }
 
@@ -108,6 +192,18 @@ extern "C" int rtts_sw_gate(const void* pw, const void* cond, int64_t ld_cond, i
     hipLaunchKernelGGL(sw_gate_kernel, dim3(sw_grid(n8)), dim3(SW_THREADS), 0, (hipStream_t)stream, (const bf16_t*)pw, (const bf16_t*)cond,
                        ld_cond, cond_offset, upsample, L, Lm, C, n8, (bf16_t*)acts);
     RTTS_LAUNCH_CHECK("rtts_sw_gate");
+    return 0;
+}
+
+extern "C" int rtts_sw_pack_mel(const float* mel, int64_t stride_b, int64_t stride_c, int64_t stride_t, int L, int n_mel, const int32_t* moff,
+                                int nseg, int64_t rows, float* dst, int64_t ld_dst, void* stream) {
+    RTTS_ENTER(stream);
+    RTTS_REQUIRE(mel && moff && dst && L >= 0 && n_mel > 0 && rows > 0 && ld_dst >= n_mel, "rtts_sw_pack_mel: bad arguments");
+    RTTS_REQUIRE(nseg >= 1 && nseg <= SW_MAX_SEGMENTS, "rtts_sw_pack_mel: 1..%d segments (got %d)", SW_MAX_SEGMENTS, nseg);
+    const size_t n = (size_t)rows * n_mel;
+    hipLaunchKernelGGL(sw_pack_mel_kernel, dim3(sw_grid(n)), dim3(SW_THREADS), 0, (hipStream_t)stream, mel, stride_b, stride_c, stride_t, L, n_mel,
+                       (const int*)moff, nseg, (long long)rows, dst, ld_dst);
+    RTTS_LAUNCH_CHECK("rtts_sw_pack_mel");
     return 0;
 }
 

@@ -83,6 +83,78 @@ def _pad(n: int, q: int) -> int:
     return -(-n // q) * q
 
 
+class _Segments:
+    """Which activation rows of a WN block belong to which utterance.  ``b`` x ``length`` audio rows (``b`` x ``mel_len``
+    mel rows) are what the row-wise entry points see; ``moff`` is None for a uniform batch (``b`` utterances of ``length``
+    rows) or the device int32 table of ``nseg`` + 1 mel-frame offsets of a packed one (``b`` = 1: all rows, capacity
+    padding included, are one sequence to the row-wise kernels; the depthwise kernel reads the table)."""
+
+    __slots__ = ("b", "length", "mel_len", "up", "moff", "nseg")
+
+    def __init__(self, b: int, length: int, mel_len: int, up: int, moff: Optional[torch.Tensor] = None, nseg: int = 0):
+        self.b, self.length, self.mel_len, self.up, self.moff, self.nseg = b, length, mel_len, up, moff, nseg
+
+    @classmethod
+    def uniform(cls, b: int, mel_len: int, up: int) -> "_Segments":
+        return cls(b, up * mel_len, mel_len, up)
+
+    @classmethod
+    def packed(cls, moff: torch.Tensor, capacity_frames: int, up: int) -> "_Segments":
+        return cls(1, up * capacity_frames, capacity_frames, up, moff, moff.numel() - 1)
+
+    @property
+    def rows(self) -> int:
+        return self.b * self.length
+
+
+SW_MAX_SEGMENTS = 1024          # utterances of one ragged call: the offset table is staged in LDS (csrc/squeezewave.hip)
+
+
+def host_lengths(lengths) -> List[int]:
+    """Per-utterance mel frame counts as host ints (a list, tuple or CPU tensor; a device tensor would be a hidden sync)."""
+    if torch.is_tensor(lengths):
+        if lengths.is_cuda:
+            raise ValueError("lengths must be host values (a list or a CPU tensor)")
+        lengths = lengths.tolist()
+    out = [int(n) for n in lengths]
+    if any(n < 0 for n in out):
+        raise ValueError(f"negative utterance length in {out}")
+    return out
+
+
+def segment_offsets(lengths) -> List[int]:
+    """B + 1 non-decreasing mel-frame offsets of utterances laid end to end: [0, l0, l0 + l1, ...]."""
+    moff = [0]
+    for n in host_lengths(lengths):
+        moff.append(moff[-1] + n)
+    return moff
+
+
+def pack_noise(noise, lengths, up: int, capacity_frames: Optional[int] = None) -> List[torch.Tensor]:
+    """Per-utterance draws -> packed rows.  ``noise[i]`` is utterance i's list in the layout and order of
+    ``noise_shapes(1, lengths[i])``; draw k of all utterances becomes ONE fp32 (up * capacity_frames, C_k) row tensor,
+    utterance i in rows [up * moff[i], up * moff[i+1]) -- the rows ``infer`` itself makes of a (1, C_k, L) draw -- and zero
+    rows after the total."""
+    moff = segment_offsets(lengths)
+    cap = moff[-1] if capacity_frames is None else int(capacity_frames)
+    if cap < moff[-1] or len(noise) != len(moff) - 1:
+        raise ValueError(f"pack_noise: {len(noise)} noise lists for {len(moff) - 1} utterances, {moff[-1]} frames in a capacity of {cap}")
+    out = []
+    for k in range(len(noise[0]) if noise else 0):
+        pieces = [z[k][0].t() for z in noise]
+        pad = up * (cap - moff[-1])
+        if pad:
+            pieces.append(pieces[0].new_zeros(pad, pieces[0].shape[1]))
+        out.append(torch.cat(pieces).to(torch.float32))
+    return out
+
+
+def unpack_noise(draws, lengths, up: int) -> List[List[torch.Tensor]]:
+    """The inverse of ``pack_noise``: per-utterance views (1, C_k, up * lengths[i]) of packed draws (rows, C_k)."""
+    moff = segment_offsets(lengths)
+    return [[d[up * moff[i]:up * moff[i + 1]].t().unsqueeze(0) for d in draws] for i in range(len(moff) - 1)]
+
+
 class _FoldedWN:
     """Inference weights of one WN block: bf16 GEMM operands (row-major (Cout, Cin)), fp32 biases, depthwise taps with
     the eval-mode BatchNorm folded in:  dw(bn(x)) = sum_k (w_k * a) x_{l+k-1} + [b + (sum_k w_k) * c],
@@ -137,23 +209,24 @@ class _FoldedWN:
             self.w_rs.append(_normed(wn.res_skip_layers[i]).to(bf).contiguous())
             self.b_rs.append(wn.res_skip_layers[i].bias.detach().float().contiguous())
 
-    def condition(self, mel: torch.Tensor, b: int, mel_len: int) -> torch.Tensor:
+    def condition(self, mel: torch.Tensor, seg: _Segments) -> torch.Tensor:
         """mel fp32 (B*Lm, n_mel) rows -> (rows, 2c * n_layers) bf16: the conditioning of all layers in one GEMM."""
         if not self.in_tree:
             return torch.addmm(self.b_cond.to(torch.bfloat16), mel.to(torch.bfloat16), self.w_cond.t())
         from ..engine import gemm
-        mp, kp = _pad(b * mel_len, 128), self.w_cond.shape[1]
+        mp, kp = _pad(seg.b * seg.mel_len, 128), self.w_cond.shape[1]
         x = torch.empty(mp, kp, dtype=torch.bfloat16, device=mel.device)
-        _lib.call("rtts_to_halo", mel.data_ptr(), mel.stride(0), 0, self.n_mel, 1, b, mel_len, 0, kp, x.data_ptr(), 0, mp, _s())
+        _lib.call("rtts_to_halo", mel.data_ptr(), mel.stride(0), 0, self.n_mel, 1, seg.b, seg.mel_len, 0, kp, x.data_ptr(), 0, mp, _s())
         return gemm(x, self.w_cond, bias=self.b_cond)
 
-    def forward(self, audio: torch.Tensor, mel: torch.Tensor, b: int, length: int, mel_len: int) -> torch.Tensor:
-        """audio fp32 (B*L, n_rem) rows (the first n_half channels condition the block), mel fp32 (B*Lm, n_mel) rows
-        -> fp32 (rows >= B*L, n_end >= 2*n_half) = [s | b | zero columns]."""
+    def forward(self, audio: torch.Tensor, mel: torch.Tensor, seg: _Segments) -> torch.Tensor:
+        """audio fp32 (seg.rows, n_rem) rows (the first n_half channels condition the block), mel fp32 (B*Lm, n_mel) rows
+        -> fp32 (rows >= seg.rows, n_end >= 2*n_half) = [s | b | zero columns].  Only the depthwise convolution looks
+        across rows: it is the one launch that differs between a uniform and a packed batch."""
         dev, c = audio.device, self.c
-        m = b * length
-        up = length // mel_len
-        cond = self.condition(mel, b, mel_len)
+        b, length, mel_len, up = seg.b, seg.length, seg.mel_len, seg.up
+        m = seg.rows
+        cond = self.condition(mel, seg)
         if self.in_tree:
             from ..engine import gemm
             mp, kp = _pad(m, 128), self.w_start.shape[1]
@@ -175,8 +248,12 @@ class _FoldedWN:
         for i in range(self.nl):
             dw = torch.empty(mp, c, dtype=torch.bfloat16, device=dev)
             lo, hi = self.dw_edge[i]                                             # zero padding pads bn(x): no folded constant there
-            _lib.call("rtts_sw_depthwise_k3", h.data_ptr(), self.dw_w[i].data_ptr(), self.dw_b[i].data_ptr(), b, length, c, dw.data_ptr(),
-                      lo.data_ptr(), hi.data_ptr(), _s())
+            if seg.moff is None:
+                _lib.call("rtts_sw_depthwise_k3", h.data_ptr(), self.dw_w[i].data_ptr(), self.dw_b[i].data_ptr(), b, length, c, dw.data_ptr(),
+                          lo.data_ptr(), hi.data_ptr(), _s())
+            else:
+                _lib.call("rtts_sw_depthwise_k3_seg", h.data_ptr(), self.dw_w[i].data_ptr(), self.dw_b[i].data_ptr(), seg.moff.data_ptr(),
+                          seg.nseg, up, m, c, dw.data_ptr(), lo.data_ptr(), hi.data_ptr(), _s())
             pw = mm(dw, self.w_pw[i], self.b_pw[i])                                # (mp, 2c) bf16
             acts = torch.empty(mp, c, dtype=torch.bfloat16, device=dev)
             _lib.call("rtts_sw_gate", pw.data_ptr(), cond.data_ptr(), cond.stride(0), i * 2 * c, up, b, length, mel_len, c, acts.data_ptr(), _s())
@@ -231,13 +308,43 @@ class SqueezeWave(nn.Module):
         shapes += [(batch, self.early_return_size, length) for k in reversed(range(self.n_flows)) if self.return_early(k)]
         return shapes
 
+    def _device(self, what: str) -> torch.device:
+        dev = self.inv_conv_layers[0].conv.weight.device
+        if dev.type != "cuda":
+            raise _lib.RttsError(f"SqueezeWave.{what} runs on the GPU only (no CPU fallback for the HIP path)")
+        return dev
+
+    def _n_mel(self) -> int:
+        cond = self.wn_layers[0].cond_layer
+        return (cond.weight_v if hasattr(cond, "weight_v") else cond.weight).shape[1]
+
+    def _up(self) -> int:
+        up = self.wn_layers[0].upsample_scale
+        if up * self.n_audio_channels != 256:
+            raise ValueError("mel_upsample_scale must equal 256 // n_audio_channels")
+        return up
+
+    def _flows(self, folded: List[_FoldedWN], mel_rows: torch.Tensor, seg: _Segments, draws, sigma: float) -> torch.Tensor:
+        """The executor of ``infer`` (modules.py:340-376) over rows: ``draws`` yields the Gaussian draws as fp32
+        (seg.rows, C) rows in the order they are consumed -> clamped audio rows (seg.rows, n_audio_channels)."""
+        audio = next(draws)                                                        # (rows, n_remaining) fp32
+        for k in reversed(range(self.n_flows)):
+            n = audio.shape[1]
+            wn_out = folded[k].forward(audio, mel_rows, seg)                       # [s | b | padding], row stride n_end
+            nxt = torch.empty_like(audio)
+            # inverse coupling + inverse 1x1 convolution in one fp32 launch (modules.py:353-361)
+            _lib.call("rtts_sw_coupling_inv1x1", audio.data_ptr(), audio.stride(0), wn_out.data_ptr(), wn_out.stride(0),
+                      self._winv[k].data_ptr(), n, audio.shape[0], nxt.data_ptr(), nxt.stride(0), _s())
+            audio = nxt
+            if self.return_early(k):
+                audio = torch.cat((sigma * next(draws), audio), dim=1)
+        return torch.clamp(audio, -1, 1)
+
     @torch.no_grad()
     def infer(self, mel_spectrogram: torch.Tensor, sigma: float = 0.6, noise: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
         """``modules.py:334-376``: mel (B, n_mel, Lm) -> audio (B, 256 * Lm) in [-1, 1].  ``noise``: the Gaussian draws in
         the reference's (B, C, L) layout and order (see ``noise_shapes``); drawn on the device when omitted."""
-        dev = self.inv_conv_layers[0].conv.weight.device
-        if dev.type != "cuda":
-            raise _lib.RttsError("SqueezeWave.infer runs on the GPU only (no CPU fallback for the HIP path)")
+        dev = self._device("infer")
         folded = self._fold()
         mel = mel_spectrogram.to(dev)
         b, n_mel, mel_len = mel.shape
@@ -249,20 +356,75 @@ class SqueezeWave(nn.Module):
             noise = [torch.randn(s, device=dev) for s in shapes]
         assert [tuple(z.shape) for z in noise] == shapes, "noise tensors do not match noise_shapes()"
         rows = lambda z: z.to(dev, torch.float32).permute(0, 2, 1).reshape(b * length, -1).contiguous()    # noqa: E731
-        draws = iter(noise)
         mel_rows = mel.to(torch.float32).permute(0, 2, 1).reshape(b * mel_len, n_mel).contiguous()
-        audio = rows(next(draws))                                                  # (B*L, n_remaining) fp32
-        for k in reversed(range(self.n_flows)):
-            n = audio.shape[1]
-            wn_out = folded[k].forward(audio, mel_rows, b, length, mel_len)        # [s | b | padding], row stride n_end
-            nxt = torch.empty_like(audio)
-            # inverse coupling + inverse 1x1 convolution in one fp32 launch (modules.py:353-361)
-            _lib.call("rtts_sw_coupling_inv1x1", audio.data_ptr(), audio.stride(0), wn_out.data_ptr(), wn_out.stride(0),
-                      self._winv[k].data_ptr(), n, audio.shape[0], nxt.data_ptr(), nxt.stride(0), _s())
-            audio = nxt
-            if self.return_early(k):
-                audio = torch.cat((sigma * rows(next(draws)), audio), dim=1)
-        return torch.clamp(audio.view(b, length * audio.shape[1]), -1, 1)
+        audio = self._flows(folded, mel_rows, _Segments.uniform(b, mel_len, folded[0].up), (rows(z) for z in noise), sigma)
+        return audio.view(b, length * audio.shape[1])
+
+    def _pack_mel(self, mel: torch.Tensor, lens: List[int], moff: torch.Tensor, capacity_frames: int, out: Optional[torch.Tensor] = None):
+        """mel (B, n_mel, >= max(lens)) fp32, any strides -> packed fp32 rows (capacity_frames, n_mel), one launch."""
+        b, n_mel, lmax = mel.shape
+        if n_mel != self._n_mel() or len(lens) != b or (lens and max(lens) > lmax):
+            raise ValueError(f"mel {tuple(mel.shape)} does not hold {b} utterances of {lens} frames and {self._n_mel()} channels")
+        if not 1 <= b <= SW_MAX_SEGMENTS:
+            raise ValueError(f"a ragged vocoder call takes 1..{SW_MAX_SEGMENTS} utterances (got {b})")
+        if mel.dtype != torch.float32:
+            mel = mel.float()
+        if out is None:
+            out = torch.empty(capacity_frames, n_mel, dtype=torch.float32, device=mel.device)
+        _lib.call("rtts_sw_pack_mel", mel.data_ptr(), mel.stride(0), mel.stride(1), mel.stride(2), lmax, n_mel, moff.data_ptr(), b,
+                  capacity_frames, out.data_ptr(), out.stride(0), _s())
+        return out
+
+    def _offsets_to(self, moff_host: List[int], dev, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The offset table on the device: a pinned host copy, enqueued without waiting for the device."""
+        host = torch.tensor(moff_host, dtype=torch.int32).pin_memory()
+        if out is None:
+            return host.to(dev, non_blocking=True)
+        return out.copy_(host, non_blocking=True)
+
+    @staticmethod
+    def split_packed(audio: torch.Tensor, moff_host: List[int]) -> List[torch.Tensor]:
+        """Packed audio -> the per-utterance views (256 samples per mel frame) of the offsets ``moff_host``."""
+        flat = audio.view(-1)
+        return [flat[256 * moff_host[i]:256 * moff_host[i + 1]] for i in range(len(moff_host) - 1)]
+
+    def pack_noise(self, noise, lengths, capacity_frames: Optional[int] = None) -> List[torch.Tensor]:
+        """Per-utterance draws (``noise_shapes(1, lengths[i])`` each) -> the packed rows ``infer_ragged`` consumes."""
+        lens = host_lengths(lengths)
+        for i, (z, n) in enumerate(zip(noise, lens)):
+            if [tuple(t.shape) for t in z] != self.noise_shapes(1, n):
+                raise ValueError(f"noise of utterance {i} does not match noise_shapes(1, {n})")
+        return pack_noise(noise, lens, self._up(), capacity_frames)
+
+    def unpack_noise(self, draws, lengths) -> List[List[torch.Tensor]]:
+        """Packed draws (e.g. what a ``capture_ragged`` replay drew: ``run.noise``) -> per-utterance ``noise_shapes(1, n)`` views."""
+        return unpack_noise(draws, lengths, self._up())
+
+    @torch.no_grad()
+    def infer_ragged(self, mel: torch.Tensor, lengths, sigma: float = 0.6, noise=None):
+        """A batch of utterances of different lengths, each vocoded as ``infer(mel[i:i+1, :, :lengths[i]])`` would vocode it:
+        mel (B, n_mel, Lmax) (any strides), ``lengths`` (B,) host ints -> (packed audio (256 * sum(lengths),), list of B
+        views of 256 * lengths[i] samples).  The utterances are laid end to end as rows; only the depthwise convolution
+        looks across rows, and it stops at each utterance's edges (``rtts_sw_depthwise_k3_seg``).  ``noise``: one list per
+        utterance in the shapes and order of ``noise_shapes(1, lengths[i])``; drawn on the device when omitted."""
+        dev = self._device("infer_ragged")
+        folded = self._fold()
+        up = self._up()
+        lens = host_lengths(lengths)
+        moff_h = segment_offsets(lens)
+        total = moff_h[-1]
+        if total == 0:
+            empty = torch.empty(0, device=dev)
+            return empty, [empty] * len(lens)
+        mel = mel.to(dev)
+        moff = self._offsets_to(moff_h, dev)
+        mel_rows = self._pack_mel(mel, lens, moff, total)
+        if noise is None:
+            draws = (torch.randn(up * total, s[1], device=dev) for s in self.noise_shapes(1, 1))
+        else:
+            draws = iter([z.to(dev) for z in self.pack_noise(noise, lens)])
+        audio = self._flows(folded, mel_rows, _Segments.packed(moff, total, up), draws, sigma).view(-1)
+        return audio, self.split_packed(audio, moff_h)
 
     def capture(self, batch: int, mel_len: int, sigma: float = 0.6):
         """-> ``run(mel) -> audio``: the whole ``infer`` for one (batch, mel_len) shape as ONE hipGraph (~1000 launches
@@ -287,5 +449,53 @@ class SqueezeWave(nn.Module):
             mel_buf.copy_(mel, non_blocking=True)
             graph.replay()
             return out
+        return run
+
+    def capture_ragged(self, batch: int, capacity_frames: int, sigma: float = 0.6):
+        """-> ``run(mel, lengths) -> (packed audio, per-utterance views)``: ``infer_ragged`` for up to ``batch`` utterances
+        of at most ``capacity_frames`` mel frames in total, as ONE hipGraph that any set of lengths replays.  Per call the
+        offset table is copied in and the mel packed into the graph's input rows (one kernel, outside the graph); the
+        Gaussian draws are made inside the graph over all capacity rows, into ``run.noise`` (packed rows, readable after
+        the replay: ``unpack_noise(run.noise, lengths)`` gives each utterance's draws).  A total above the capacity raises
+        before anything is launched.  Graphs are kept per (batch, capacity, sigma).  The returned audio is the graph's
+        output buffer: copy it before the next call."""
+        dev = self._device("capture_ragged")
+        batch, cap = int(batch), int(capacity_frames)
+        if not 1 <= batch <= SW_MAX_SEGMENTS or cap < 1:
+            raise ValueError(f"capture_ragged: 1..{SW_MAX_SEGMENTS} utterances and a positive capacity (got {batch}, {cap})")
+        cache = self.__dict__.setdefault("_ragged_graphs", {})
+        key = (batch, cap, float(sigma))
+        if key in cache and cache[key].folded is self._fold():
+            return cache[key]
+        folded = self._fold()
+        up = self._up()
+        widths = [s[1] for s in self.noise_shapes(1, 1)]
+        mel_rows = torch.zeros(cap, self._n_mel(), device=dev)
+        moff = torch.zeros(batch + 1, dtype=torch.int32, device=dev)        # every row padding until a call sets the table
+        seg = _Segments.packed(moff, cap, up)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                          # warm-up: allocator, lazy attributes
+            self._flows(folded, mel_rows, seg, iter([torch.randn(up * cap, w, device=dev) for w in widths]), sigma)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with capturing(graph):
+            draws = [torch.randn(up * cap, w, device=dev) for w in widths]
+            out = self._flows(folded, mel_rows, seg, iter(draws), sigma).view(-1)
+
+        def run(mel: torch.Tensor, lengths):
+            lens = host_lengths(lengths)
+            moff_h = segment_offsets(lens)
+            if len(lens) != batch or moff_h[-1] > cap:
+                raise ValueError(f"capture_ragged graph for {batch} utterances of {cap} frames in total: got {len(lens)} utterances, "
+                                 f"{moff_h[-1]} frames")
+            mel = mel.to(dev)
+            self._offsets_to(moff_h, dev, out=moff)
+            self._pack_mel(mel, lens, moff, cap, out=mel_rows)
+            graph.replay()
+            return out, self.split_packed(out, moff_h)
+        run.noise, run.batch, run.capacity, run.folded, run.graph = draws, batch, cap, folded, graph
+        cache[key] = run
         return run
 
