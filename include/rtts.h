@@ -527,6 +527,34 @@ int rtts_sw_pack_mel(const float* mel, int64_t stride_b, int64_t stride_c, int64
 int rtts_sw_coupling_inv1x1(const float* audio, int64_t ld_audio, const float* wn_out, int64_t ld_wn, const float* winv, int n,
                             int64_t rows, float* out, int64_t ld_out, void* stream);
 
+/* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
+ * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84
+ * MelSpectrogramCreator is the same call with power 2 and another mel matrix) and spectrogram_to_log_scale, for a RAGGED batch of
+ * utterances in one launch: per utterance torch.stft(center=True, pad_mode="reflect") magnitudes ^ power, the mel matrix,
+ * log(max(., clip)).  All arithmetic is f32 (v_mfma_f32_32x32x2_f32, bit for bit a k-ordered fmaf chain): an utterance's output is
+ * bitwise the same alone and anywhere in a batch.
+ *   audio           f32, the utterances end to end: utterance s is samples [sample_offsets[s], sample_offsets[s+1])
+ *   sample_offsets  i64 (nseg + 1), frame_offsets i64 (nseg + 1): DEVICE tables the kernel reads, and the same values in
+ *                   sample_offsets_host / frame_offsets_host, which the entry point validates and sizes the grid by (1 <= nseg <= 65535)
+ *                   The two copies MUST hold the same values: the kernel takes lengths and output columns from the device tables,
+ *                   the bounds check and the grid come from the host tables, and nothing can compare them without a host
+ *                   synchronisation -- a mismatch is undefined behaviour (reads and stores out of bounds)
+ *   utterance s     N_s samples > n_fft / 2 (reflect padding), T_s = rtts_mel_frames(N_s, hop) = N_s / hop + 1 frames, written to
+ *                   columns [frame_offsets[s], + T_s); frame_offsets[s+1] - frame_offsets[s] >= T_s, columns past T_s are not touched
+ *   dft_basis       f32 (n_fft, n_fft) row-major, row n = sample of the frame, window folded in: column k < n_fft/2 =
+ *                   w[n] cos(2 pi n k / n_fft); column n_fft/2 + k = w[n] sin(2 pi n k / n_fft) for 1 <= k < n_fft/2; column n_fft/2 =
+ *                   w[n] cos(pi n), the Nyquist bin (the sine of bin 0 is zero).  w = periodic Hann of win_length, centred in n_fft
+ *   mel_basis       f32 (n_mels, n_fft/2 + 1) row-major, applied to |X|^power
+ *   out             f32 (n_mels, ld_out) rows, ld_out >= frame_offsets[nseg]: columns [frame_offsets[s], + T_s) are the reference's
+ *                   (n_mels, T) of utterance s
+ * Supported: n_fft in {512, 1024, 2048}, hop = n_fft / 4, 1 <= n_mels <= 128, power 1 (magnitude) or 2, clip > 0.  Anything else, a
+ * null pointer, nseg < 1 or an utterance of <= n_fft / 2 samples is rejected before any launch. */
+int64_t rtts_mel_frames(int64_t n_samples, int hop);
+int rtts_mel_spectrogram(const float* audio, const int64_t* sample_offsets_host, const int64_t* frame_offsets_host,
+                         const int64_t* sample_offsets, const int64_t* frame_offsets, int nseg, const float* dft_basis,
+                         const float* mel_basis, int n_fft, int hop, int n_mels, int power, float clip, float* out, int64_t ld_out,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

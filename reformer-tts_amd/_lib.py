@@ -134,6 +134,8 @@ SIGNATURES = {
     "rtts_sw_pack_mel": [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _i64, _vp],
     "rtts_sw_coupling_inv1x1": [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _vp, _i64, _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
+    "rtts_mel_frames": [_i64, _i32],
+    "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
 }
 
 _lib = None
@@ -188,6 +190,7 @@ def load() -> C.CDLL:
             fn.argtypes = args
             fn.restype = C.c_int
         lib.rtts_gemm_nt_gate_words.restype = C.c_int64
+        lib.rtts_mel_frames.restype = C.c_int64
         _lib = lib
         # A/B scripts may name a run length in the environment: read ONCE, here -- the library's launch path reads none
         fw, bw = os.environ.get("RTTS_LSH_FWD_WALK"), os.environ.get("RTTS_LSH_BWD_WALK")

@@ -186,3 +186,32 @@ def lsh_attn_bwd(qk, v, st, out, dout, lse_tot, heads: int, bucket_size: int, ca
     _lib.call("rtts_lsh_bwd_reduce", dqk_part.data_ptr(), dv_part.data_ptr(), b, heads, t, dh, n_hashes, dqk.data_ptr(),
               dv.data_ptr(), ld_d, _ptr(flags), _stream())
     return dqk, dv
+
+
+def mel_spectrogram(audio: torch.Tensor, sample_offsets_host, frame_offsets_host, offsets: torch.Tensor, nseg: int,
+                    dft_basis: torch.Tensor, mel_basis: torch.Tensor, n_fft: int, hop: int, power: int, clip: float,
+                    out: torch.Tensor) -> torch.Tensor:
+    """audio: the utterances end to end (flat f32); offsets: (2, nseg + 1) i64 device table [sample offsets; frame offsets] and the
+    same values as two host ``ctypes.c_int64`` arrays; dft_basis (n_fft, n_fft) f32, mel_basis (n_mels, n_fft/2 + 1) f32 ->
+    out (n_mels, >= total frames) f32 = the log-mel rows, one ``rtts_mel_spectrogram`` launch on the current stream."""
+    for name, t in (("audio", audio), ("dft_basis", dft_basis), ("mel_basis", mel_basis), ("out", out)):
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise _lib.RttsError(f"mel_spectrogram runs on the GPU only: {name} must be a CUDA float32 tensor "
+                                 f"(got {t.dtype} on {t.device})")
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.shape == (2, nseg + 1) and offsets.is_contiguous()):
+        raise ValueError(f"offsets: expected a contiguous CUDA int64 (2, {nseg + 1}) table")
+    n_mels = mel_basis.shape[0]
+    if not (audio.dim() == 1 and audio.is_contiguous() and dft_basis.is_contiguous() and mel_basis.is_contiguous()
+            and tuple(dft_basis.shape) == (n_fft, n_fft) and tuple(mel_basis.shape) == (n_mels, n_fft // 2 + 1)
+            and out.dim() == 2 and out.shape[0] == n_mels and out.stride(1) == 1):
+        raise ValueError("mel_spectrogram: audio flat, dft_basis (n_fft, n_fft), mel_basis (n_mels, n_fft/2 + 1), out (n_mels, frames) rows")
+    if audio.numel() < sample_offsets_host[nseg] or out.shape[1] < frame_offsets_host[nseg]:
+        raise ValueError(f"mel_spectrogram: {audio.numel()} samples / {out.shape[1]} output frames for offsets ending at "
+                         f"{sample_offsets_host[nseg]} / {frame_offsets_host[nseg]}")
+    frames = frame_offsets_host[nseg]
+    ev = TIMING.start(f"rtts_mel_spectrogram/n{n_fft}")
+    _lib.call("rtts_mel_spectrogram", audio.data_ptr(), sample_offsets_host, frame_offsets_host, offsets[0].data_ptr(),
+              offsets[1].data_ptr(), nseg, dft_basis.data_ptr(), mel_basis.data_ptr(), n_fft, hop, n_mels, power, clip,
+              out.data_ptr(), out.stride(0), _stream())
+    TIMING.stop(ev, 2.0 * frames * (n_fft * n_fft + n_mels * (n_fft // 2 + 1)))
+    return out

@@ -86,3 +86,28 @@ def synthesize(tts, vocoder, phonemes: Sequence[torch.Tensor], *, sigma: float =
     spectrogram, stop = tts.infer(batch, use_graph=use_graph, **infer_kwargs)
     waves = vocode_trimmed(vocoder, spectrogram, stop, sigma=sigma, use_graph=use_graph, max_len=infer_kwargs.get("max_len"))
     return waves, spectrogram, stop
+
+
+@torch.no_grad()
+def mel_round_trip_error(vocoder_waves: Sequence[torch.Tensor], spectrogram: torch.Tensor, frames, creator) -> torch.Tensor:
+    """How far a vocoded batch is from the spectrograms it was vocoded from: per utterance, the mean of
+    |log-mel(audio_i)[:, :frames_i] - spectrogram[i, :, :frames_i]| -> (B,) f32 on the device.
+
+    ``vocoder_waves``: the waveforms ``synthesize`` / ``vocode_trimmed`` returned (256 * frames_i samples each, on the
+    device); ``spectrogram`` (B, n_mel, L) and ``frames`` (host ints: ``frame_counts(stop, L)``) what they were vocoded
+    from; ``creator``: a ``dataset.audio`` spectrogram module of the format the vocoder was trained on
+    (``Tacotron2Spectrogram`` for the reference's configs).  One ragged mel launch over all the waveforms; an utterance needs
+    more than n_fft / 2 samples (three frames at the config values)."""
+    lens = host_lengths(frames)
+    waves = [w.reshape(-1) for w in vocoder_waves]
+    if len(waves) != len(lens) or spectrogram.dim() != 3 or spectrogram.shape[0] != len(lens) or spectrogram.shape[1] != creator.n_mels:
+        raise ValueError(f"mel_round_trip_error: {len(waves)} waveforms, {len(lens)} frame counts, spectrogram {tuple(spectrogram.shape)}")
+    flat = torch.cat([w.to(torch.float32) for w in waves])
+    packed, foff = creator.forward_packed(flat, [int(w.numel()) for w in waves])
+    errs = []
+    for i, n in enumerate(lens):
+        if n > foff[i + 1] - foff[i] or n > spectrogram.shape[2]:
+            raise ValueError(f"mel_round_trip_error: utterance {i} has {n} frames, its waveform {foff[i + 1] - foff[i]}, the spectrogram "
+                             f"{spectrogram.shape[2]}")
+        errs.append((packed[:, foff[i]:foff[i] + n] - spectrogram[i, :, :n].to(packed.device, torch.float32)).abs().mean())
+    return torch.stack(errs)

@@ -7,6 +7,7 @@ frame), next to the CPU oracle of the vocoder on a bounded mel length.
     python scripts/vocoder_bench.py --ragged-only            # only the ragged legs (16 utterances of 100-870 frames)
     python scripts/vocoder_bench.py --ragged-kernels-only    # the ragged vocoder stage alone: run it under
         rocprofv3 --kernel-trace --stats for the segment kernels' bytes/s (ragged_kernel_bytes in the JSON)
+    python scripts/vocoder_bench.py --round-trip             # only mel(vocoder(mel)) against mel, per utterance
 """
 import argparse
 import json
@@ -108,6 +109,25 @@ def ragged_legs(sw, dev, args):
     return res
 
 
+def round_trip_leg(sw, dev):
+    """mel -> vocoder -> audio -> log-mel against the mel that went in, for 8 of the ragged utterances: per-utterance mean
+    |difference| in log units (synthesis.mel_round_trip_error, one ragged mel launch) and its wall time.  With random-init
+    weights the size of the error says nothing; a trained vocoder is judged by it."""
+    from reformer_tts_amd import synthesis
+    from reformer_tts_amd.dataset.audio import Tacotron2Spectrogram
+    lens = ragged_lengths()[:8]
+    g = torch.Generator().manual_seed(1)
+    mel = torch.full((len(lens), 80, max(lens)), -11.5)
+    for i, n in enumerate(lens):
+        mel[i, :, :n] = (torch.randn(80, n, generator=g) * 2 - 5).clamp(-11.5, 2.0)
+    mel = mel.to(dev)
+    creator = Tacotron2Spectrogram(SR, 1024, 1024, 256, 80).to(dev)
+    _, waves = sw.infer_ragged(mel, lens)
+    dt, err = timed(lambda: synthesis.mel_round_trip_error(waves, mel, lens, creator), 5)
+    return {"lengths": lens, "mean_abs_log_mel_error": [round(float(e), 4) for e in err.cpu()], "ms": round(1e3 * dt, 3),
+            "note": "random-init vocoder: the wiring is measured, not the quality"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mel-len", type=int, default=1024)
@@ -115,6 +135,7 @@ def main():
     ap.add_argument("--cpu-mel-len", type=int, default=64)
     ap.add_argument("--ragged-only", action="store_true", help="only the ragged legs")
     ap.add_argument("--ragged-kernels-only", action="store_true", help="ragged legs (a)-(c) only, for a rocprofv3 kernel trace")
+    ap.add_argument("--round-trip", action="store_true", help="only the mel(vocoder(mel)) round-trip leg")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -122,6 +143,10 @@ def main():
     for wn in sw.wn_layers:                                   # end_conv is zero-initialised: give the flow something to do
         wn.end_conv.weight.data.normal_(0, 0.01)
     out = {"unit": "audio samples/s", "sample_rate": SR}
+    if args.round_trip:
+        out["round_trip"] = round_trip_leg(sw, dev)
+        print(json.dumps(out))
+        return
     if args.ragged_only or args.ragged_kernels_only:
         out["ragged"] = ragged_legs(sw, dev, args)
         lens = out["ragged"]["lengths"]
