@@ -555,6 +555,43 @@ int rtts_mel_spectrogram(const float* audio, const int64_t* sample_offsets_host,
                          const float* mel_basis, int n_fft, int hop, int n_mels, int power, float clip, float* out, int64_t ld_out,
                          void* stream);
 
+/* ---- Sample-rate conversion (dataset preprocessing, in front of the log-mel call) -------------
+ * Replaces resample_wav of reference reformer_tts/dataset/convert.py:131-146 (torchaudio.transforms.Resample, keep channel 0),
+ * for a RAGGED batch of utterances that share (orig, new, channels), in one launch.  With c = 0.99 * min(orig, new) / 2, L = 6,
+ * W = L / (2 c), an utterance x[0..N), zero outside, gives M = rtts_resample_len(N, orig, new) = ceil(N * new / orig) samples
+ *     out[k] = sum_i x[i] h(i / orig - k / new),   h(d) = (1 + cos(2 pi c d / L)) / 2 * sin(2 pi c d) / (pi d) / orig for |d| < W, else 0
+ * (the Hann-windowed sinc of Kaldi's LinearResample = torchaudio's sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99).
+ * The filter arrives as tables over the reduced ratio orig_red : new_red = orig / g : new / g, g = gcd(orig, new): output
+ * k = j * new_red + p is the f32 fmaf chain over t = 0 .. taps-1, in this order, of x[j * orig_red + first[p] + t] * taps_table[t][p].
+ * Padded taps and samples outside the utterance take part as zeros, so an utterance's output is bitwise the same alone and anywhere
+ * in a batch.
+ *   audio           in_format 0: f32 mono, the utterances end to end (channels must be 1).  in_format 1: int16 PCM, `channels`
+ *                   interleaved (a WAV payload as it is): channel 0 is read and scaled by 1 / 32768, the other channels are skipped
+ *   in_offsets / out_offsets (nseg + 1 non-decreasing int64, in FRAMES = one sample per channel), each given twice: *_host in host
+ *                   memory, read by this call; the others in DEVICE memory, read by the kernel when it runs.  The two copies MUST hold
+ *                   the same values, as for rtts_mel_spectrogram: the bounds check and the grid come from the host tables
+ *   utterance s     owns input frames [in_offsets[s], in_offsets[s+1]), N_s >= 1 of them (shorter than taps is fine), and writes
+ *                   out[out_offsets[s] .. + M_s); out_offsets[s+1] - out_offsets[s] >= M_s, samples past M_s are not touched.  `out`
+ *                   with out_offsets is exactly the (audio, sample_offsets) input of rtts_mel_spectrogram
+ *   first           int32 (new_red), device: ceil(p * orig_red / new_red - W * orig), negative for small p, non-decreasing in p with
+ *                   first[p + new_red] = first[p] + orig_red
+ *   taps_table      f32 (taps, new_red) row-major, device: row t, column p = h((first[p] + t) / orig - p / new), zero where a
+ *                   phase has fewer than `taps` coefficients.  Built in float64 on the host and rounded once
+ *                   (dataset/audio.py resample_tables)
+ * A workgroup computes RTTS_RESAMPLE_TILE consecutive outputs of one utterance from one LDS image of the inputs they share.
+ * Supported: orig_red != new_red, both >= 1; taps in 1..RTTS_RESAMPLE_MAX_TAPS; new_red * taps <= RTTS_RESAMPLE_MAX_TABLE; a tile's
+ * inputs, ceil((RTTS_RESAMPLE_TILE - 1) * orig_red / new_red) + 1 + taps words, plus min(new_red, RTTS_RESAMPLE_TILE) words must fit
+ * 64 KB of LDS (downsampling by up to about 15 : 1; upsampling is not limited by it); 1 <= channels <= 8 (int16), channels = 1
+ * (f32); nseg in 1..65535.  Anything else, a null pointer, offsets that decrease, an empty utterance or an output slot smaller
+ * than M_s is rejected before any launch. */
+#define RTTS_RESAMPLE_TILE 1024
+#define RTTS_RESAMPLE_MAX_TAPS 256
+#define RTTS_RESAMPLE_MAX_TABLE (1 << 22)
+int64_t rtts_resample_len(int64_t n_samples, int orig, int new_);
+int rtts_resample(const void* audio, int in_format, int channels, const int64_t* in_offsets_host, const int64_t* out_offsets_host,
+                  const int64_t* in_offsets, const int64_t* out_offsets, int nseg, const int32_t* first, const float* taps_table,
+                  int orig_red, int new_red, int taps, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

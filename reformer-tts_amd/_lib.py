@@ -136,6 +136,8 @@ SIGNATURES = {
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
+    "rtts_resample_len": [_i64, _i32, _i32],
+    "rtts_resample": [_vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
 }
 
 _lib = None
@@ -191,6 +193,7 @@ def load() -> C.CDLL:
             fn.restype = C.c_int
         lib.rtts_gemm_nt_gate_words.restype = C.c_int64
         lib.rtts_mel_frames.restype = C.c_int64
+        lib.rtts_resample_len.restype = C.c_int64
         _lib = lib
         # A/B scripts may name a run length in the environment: read ONCE, here -- the library's launch path reads none
         fw, bw = os.environ.get("RTTS_LSH_FWD_WALK"), os.environ.get("RTTS_LSH_BWD_WALK")

@@ -6,7 +6,11 @@ The reference goes through torchaudio (``Spectrogram(pad=0)`` = ``torch.stft(cen
 Hann window) and librosa (``filters.mel``: Slaney scale, Slaney norm), one file at a time on the CPU.  Here a ragged batch of
 utterances is one launch of ``rtts_mel_spectrogram`` (csrc/mel.hip): framing, the windowed DFT, the mel matrix and the log are
 fused, in f32 throughout.  The window and the DFT live in one basis matrix built here in float64 and rounded once; the mel
-matrix is ``mel_filterbank``, the triangular-ramp construction librosa and torchaudio share."""
+matrix is ``mel_filterbank``, the triangular-ramp construction librosa and torchaudio share.
+
+In front of it, ``Resample`` / ``resample_wav`` are the reference's ``resample_wav`` (``convert.py:131-146``:
+``torchaudio.transforms.Resample``, keep channel 0) as one ragged launch of ``rtts_resample`` (csrc/resample.hip), whose packed
+output is the packed input of the mel launch: ``preprocess_directory(resample=True)`` uploads raw PCM and runs the two."""
 from __future__ import annotations
 
 import ctypes
@@ -23,6 +27,9 @@ from .. import _lib, ops
 
 MEL_MAX_SEGMENTS = 65535        # utterances of one launch (the grid's second dimension)
 SUPPORTED_N_FFT = (512, 1024, 2048)
+RESAMPLE_TILE = 1024            # outputs of one workgroup of rtts_resample (RTTS_RESAMPLE_TILE of include/rtts.h)
+RESAMPLE_MAX_TAPS = 256         # RTTS_RESAMPLE_MAX_TAPS
+RESAMPLE_MAX_TABLE = 1 << 22    # RTTS_RESAMPLE_MAX_TABLE: coefficients of one table (new_red * taps)
 
 
 def _hz_to_mel(f: np.ndarray, mel_scale: str) -> np.ndarray:
@@ -134,6 +141,32 @@ def _offsets(counts: Sequence[int]) -> List[int]:
     return off
 
 
+def _utterances(audio, lengths, who: str) -> Tuple[List[torch.Tensor], List[int]]:
+    """The two input forms of the modules' ``forward`` -- a list of 1-D device tensors, or a padded (B, N) device tensor with
+    ``lengths`` -- as (the utterances, their lengths)."""
+    if torch.is_tensor(audio):
+        if audio.dim() != 2 or lengths is None:
+            raise ValueError("forward takes a list of 1-D tensors, or a padded (B, N) tensor with lengths")
+        if not audio.is_cuda:
+            raise _lib.RttsError(f"{who}.forward runs on the GPU only (no CPU fallback for the HIP path)")
+        if torch.is_tensor(lengths):
+            lengths = lengths.tolist()
+        lens = [int(n) for n in lengths]
+        if len(lens) != audio.shape[0] or max(lens) > audio.shape[1]:
+            raise ValueError(f"lengths {lens} do not fit audio of shape {tuple(audio.shape)}")
+        parts = [audio[i, :n] for i, n in enumerate(lens)]
+    else:
+        parts = list(audio)
+        if any(not torch.is_tensor(p) or p.dim() != 1 for p in parts):
+            raise ValueError("forward takes a list of 1-D tensors, or a padded (B, N) tensor with lengths")
+        if any(not p.is_cuda for p in parts):
+            raise _lib.RttsError(f"{who}.forward runs on the GPU only (no CPU fallback for the HIP path)")
+        lens = [int(p.numel()) for p in parts]
+    if not parts:
+        raise ValueError("forward: no utterances")
+    return parts, lens
+
+
 class MelTables:
     """Offset tables of one ragged call: utterance lengths -> sample / frame offsets, as host arrays (validated by the entry
     point) and as one device tensor (read by the kernel).  Build it once to replay a captured call on new audio of the same
@@ -204,26 +237,7 @@ class _LogMel(nn.Module):
 
     def _gather(self, audio, lengths) -> Tuple[torch.Tensor, List[int]]:
         dev = self._device("forward")
-        if torch.is_tensor(audio):
-            if audio.dim() != 2 or lengths is None:
-                raise ValueError("forward takes a list of 1-D tensors, or a padded (B, N) tensor with lengths")
-            if not audio.is_cuda:
-                raise _lib.RttsError(f"{type(self).__name__}.forward runs on the GPU only (no CPU fallback for the HIP path)")
-            if torch.is_tensor(lengths):
-                lengths = lengths.tolist()
-            lens = [int(n) for n in lengths]
-            if len(lens) != audio.shape[0] or max(lens) > audio.shape[1]:
-                raise ValueError(f"lengths {lens} do not fit audio of shape {tuple(audio.shape)}")
-            parts = [audio[i, :n] for i, n in enumerate(lens)]
-        else:
-            parts = list(audio)
-            if any(not torch.is_tensor(p) or p.dim() != 1 for p in parts):
-                raise ValueError("forward takes a list of 1-D tensors, or a padded (B, N) tensor with lengths")
-            if any(not p.is_cuda for p in parts):
-                raise _lib.RttsError(f"{type(self).__name__}.forward runs on the GPU only (no CPU fallback for the HIP path)")
-            lens = [int(p.numel()) for p in parts]
-        if not parts:
-            raise ValueError("forward: no utterances")
+        parts, lens = _utterances(audio, lengths, type(self).__name__)
         short = [n for n in lens if n <= self.n_fft // 2]
         if short:
             raise ValueError(f"utterances of {short} samples: reflect padding needs more than n_fft / 2 = {self.n_fft // 2}")
@@ -272,32 +286,256 @@ class MelSpectrogram(_LogMel):
         super().__init__(sample_rate, n_fft, win_length, hop_length, n_mels, power=2, mel_scale="htk", norm=None)
 
 
-def preprocess_directory(audio_dir, mel_dir, creator: _LogMel, max_batch_samples: int = 1 << 24, suffix: str = ".wav") -> List[str]:
-    """The loop of ``preprocess.py:100-108``, batched: every ``*.wav`` of ``audio_dir`` -> ``mel_dir/<stem>.pt`` (the
-    reference's file format).  Files are sorted by length and packed into ragged launches of at most ``max_batch_samples``
-    samples (one file alone may exceed it); only one batch of audio is in host memory at a time.  A file whose sample rate is
-    not the creator's raises.  -> the written paths, in the order of the sorted input names."""
-    dev = creator._device("preprocess_directory")
-    names = sorted(f for f in os.listdir(audio_dir) if f.endswith(suffix))
-    os.makedirs(mel_dir, exist_ok=True)
-    samples = {}
-    for name in names:                                             # headers only: the audio is decoded batch by batch
-        samples[name], rate = wav_info(os.path.join(audio_dir, name))
-        creator._check_rate(rate, os.path.join(audio_dir, name))
-    order = sorted(names, key=lambda name: (samples[name], name))
-    written = {}
+def resample_tables(orig: int, new: int) -> Tuple[torch.Tensor, torch.Tensor, int, int, int]:
+    """The tables of ``rtts_resample`` for ``orig`` -> ``new`` Hz -> (first int32 (new',), coefficients f32 (taps, new'), orig',
+    new', taps), the rates reduced by their gcd.  Output k = j new' + p is sum_t x[j orig' + first[p] + t] * coefficients[t, p],
+    with coefficients[t, p] = h((first[p] + t) / orig - p / new) for the filter
+        h(d) = (1 + cos(2 pi c d / L)) / 2 * sin(2 pi c d) / (pi d) / orig  for |d| < W, else 0    (2 c / orig at d = 0),
+        c = 0.99 * min(orig, new) / 2,  L = 6,  W = L / (2 c)
+    (torchaudio's Resample: Kaldi's LinearResample, lowpass_filter_width 6).  first[p] = ceil(p orig' / new' - W orig); taps is the
+    largest number of inputs within W of any phase, and shorter phases end in zeros.  The coefficient matrix is stored
+    [tap][phase]: the lanes of a wave, consecutive outputs, read consecutive words.  Phase centres, the support and first[] are
+    exact integer arithmetic (d = (i new' - p orig') / (orig' new' g), W = 200 / (33 min(orig, new))); h is evaluated in float64
+    and rounded once to f32."""
+    orig, new = int(orig), int(new)
+    if orig < 1 or new < 1 or orig == new:
+        raise ValueError(f"resample_tables: the rates must be positive and different (got {orig}, {new})")
+    g = math.gcd(orig, new)
+    o, w, lo = orig // g, new // g, min(orig, new)
+    den, reach = 33 * lo * w, 200 * orig * w                      # p o / w -+ W orig = (33 lo p o -+ 200 orig w) / (33 lo w)
+    first = [-((reach - 33 * lo * p * o) // den) for p in range(w)]
+    last = [(33 * lo * p * o + reach) // den for p in range(w)]
+    taps = max(b - a + 1 for a, b in zip(first, last))
+    if taps > RESAMPLE_MAX_TAPS or w * taps > RESAMPLE_MAX_TABLE:
+        raise ValueError(f"resample_tables: {orig} -> {new} Hz needs {taps} taps for {w} phases; supported are up to "
+                         f"{RESAMPLE_MAX_TAPS} taps and {RESAMPLE_MAX_TABLE} coefficients")
+    first_a = np.array(first, dtype=np.int64)
+    num = (first_a[None, :] + np.arange(taps, dtype=np.int64)[:, None]) * w - np.arange(w, dtype=np.int64)[None, :] * o
+    inside = np.abs(num) * (33 * lo) < 200 * (o * w * g)          # |d| < W
+    d = num.astype(np.float64) / float(o * w * g)
+    c = 0.495 * lo
+    safe = np.where(num == 0, 1.0, d)
+    sinc = np.where(num == 0, 2.0 * c, np.sin(2.0 * np.pi * c * safe) / (np.pi * safe))
+    h = np.where(inside, 0.5 * (1.0 + np.cos(2.0 * np.pi * c * d / 6.0)) * sinc / orig, 0.0)
+    return torch.tensor(first, dtype=torch.int32), torch.from_numpy(h.astype(np.float32)), o, w, taps
+
+
+def resample_len(n_samples: int, orig: int, new: int) -> int:
+    """Samples of an utterance of ``n_samples`` after ``orig`` -> ``new`` Hz: ceil(n_samples * new / orig) (``rtts_resample_len``)."""
+    lib = _lib.load()
+    m = lib.rtts_resample_len(int(n_samples), int(orig), int(new))
+    if m < 0:
+        raise _lib.RttsError(lib.rtts_last_error().decode())
+    return int(m)
+
+
+class ResampleTables:
+    """Offset tables of one ragged ``rtts_resample`` call: utterance lengths in frames -> input / output offsets, as host arrays
+    and as one device tensor, like ``MelTables``.  ``out_lengths`` / ``out_offsets`` are the lengths / sample offsets of the mel
+    call that takes the output."""
+
+    def __init__(self, lengths: Sequence[int], orig: int, new: int, device):
+        self.lengths = [int(n) for n in lengths]
+        if not 1 <= len(self.lengths) <= MEL_MAX_SEGMENTS:
+            raise ValueError(f"a resample call takes 1..{MEL_MAX_SEGMENTS} utterances (got {len(self.lengths)})")
+        if min(self.lengths) < 1:
+            raise ValueError(f"utterances need at least one sample (got lengths {self.lengths})")
+        self.out_lengths = [-((-n * new) // orig) for n in self.lengths]
+        self.in_offsets, self.out_offsets = _offsets(self.lengths), _offsets(self.out_lengths)
+        n1 = len(self.lengths) + 1
+        self.ioff_host = (ctypes.c_int64 * n1)(*self.in_offsets)
+        self.ooff_host = (ctypes.c_int64 * n1)(*self.out_offsets)
+        host = torch.tensor([self.in_offsets, self.out_offsets], dtype=torch.int64).pin_memory()
+        self.device_table = host.to(device, non_blocking=True)    # enqueued, not waited for
+        self._pinned = host                                       # alive until the copy has run
+
+
+class Resample(nn.Module):
+    """``torchaudio.transforms.Resample(orig_freq, new_freq)`` as the reference uses it (``convert.py:137``), for ragged batches on
+    the GPU: one ``rtts_resample`` launch per call.  ``orig_freq == new_freq`` returns its input unchanged, as torchaudio's does."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000):
+        super().__init__()
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        if self.orig_freq < 1 or self.new_freq < 1:
+            raise ValueError(f"the rates must be positive (got {orig_freq}, {new_freq})")
+        if self.orig_freq == self.new_freq:
+            first, coef, self.orig_red, self.new_red, self.taps = torch.zeros(1, dtype=torch.int32), torch.ones(1, 1), 1, 1, 1
+        else:
+            first, coef, self.orig_red, self.new_red, self.taps = resample_tables(self.orig_freq, self.new_freq)
+        self.register_buffer("first", first, persistent=False)
+        self.register_buffer("coefficients", coef.contiguous(), persistent=False)
+
+    def _device(self, what: str) -> torch.device:
+        dev = self.first.device
+        if dev.type != "cuda":
+            raise _lib.RttsError(f"{type(self).__name__}.{what} runs on the GPU only (no CPU fallback for the HIP path)")
+        return dev
+
+    def tables(self, lengths: Sequence[int]) -> ResampleTables:
+        return ResampleTables(lengths, self.orig_red, self.new_red, self._device("tables"))
+
+    @torch.no_grad()
+    def forward_packed(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None, *, tables: Optional[ResampleTables] = None,
+                       channels: int = 1, out: Optional[torch.Tensor] = None):
+        """``audio``: the utterances end to end, a flat device tensor, f32 (mono) or int16 (``channels`` interleaved: a WAV payload
+        as it is; channel 0 / 32768 is resampled); ``lengths``: their frame counts (host ints), or ``tables`` from an earlier
+        ``self.tables(lengths)`` -> (flat f32 of the resampled utterances, output offsets: utterance i owns
+        [offsets[i], offsets[i+1])).  One launch, stream-ordered; the result is the packed input of a creator's
+        ``forward_packed`` with lengths ``offsets[i+1] - offsets[i]``."""
+        dev = self._device("forward_packed")
+        if not (audio.is_cuda and audio.device == dev):
+            raise _lib.RttsError(f"{type(self).__name__}.forward_packed runs on the GPU only: audio is on {audio.device}, the tables on {dev}")
+        if self.orig_freq == self.new_freq:
+            if audio.dtype != torch.float32 or lengths is None:
+                raise ValueError("orig_freq == new_freq passes f32 audio with lengths through; there is nothing to launch")
+            return audio, _offsets(lengths)
+        if tables is None:
+            if lengths is None:
+                raise ValueError("forward_packed needs lengths or tables")
+            tables = self.tables(lengths)
+        if out is None:
+            out = torch.empty(tables.out_offsets[-1], dtype=torch.float32, device=dev)
+        ops.resample(audio, tables.ioff_host, tables.ooff_host, tables.device_table, len(tables.lengths), self.first, self.coefficients,
+                     self.orig_red, self.new_red, out, channels=channels)
+        return out, list(tables.out_offsets)
+
+    @torch.no_grad()
+    def forward(self, audio, lengths=None):
+        """``audio``: a list of 1-D device tensors, or a padded (B, N) device tensor with ``lengths`` (host ints or a tensor)
+        -> (resampled (B, M_max) f32, zero behind each utterance's M_i = ceil(N_i new / orig) samples; M (B,) int64 on the
+        device)."""
+        if self.orig_freq == self.new_freq:
+            return audio, lengths
+        dev = self._device("forward")
+        parts, lens = _utterances(audio, lengths, type(self).__name__)
+        packed, ooff = self.forward_packed(torch.cat([p.to(dev, torch.float32) for p in parts]), lens)
+        m = [ooff[i + 1] - ooff[i] for i in range(len(lens))]
+        res = torch.zeros(len(lens), max(m), dtype=torch.float32, device=dev)
+        for i, n in enumerate(m):
+            res[i, :n] = packed[ooff[i]:ooff[i + 1]]
+        return res, torch.tensor(m, dtype=torch.int64).to(dev, non_blocking=True)
+
+
+def pcm_info(path) -> Tuple[int, int, int]:
+    """(frames, sample rate, channels) of a 16-bit PCM WAV from its header alone; any other sample format raises."""
+    with wave.open(os.fspath(path), "rb") as f:
+        if f.getsampwidth() != 2 or f.getcomptype() != "NONE":
+            raise ValueError(f"{path}: expected 16-bit PCM, got {8 * f.getsampwidth()} bits ({f.getcomptype()})")
+        return f.getnframes(), f.getframerate(), f.getnchannels()
+
+
+def read_pcm(path) -> Tuple[torch.Tensor, int]:
+    """16-bit PCM WAV of any channel count -> (int16 (frames, channels), sample rate): the payload as it is."""
+    with wave.open(os.fspath(path), "rb") as f:
+        if f.getsampwidth() != 2 or f.getcomptype() != "NONE":
+            raise ValueError(f"{path}: expected 16-bit PCM, got {8 * f.getsampwidth()} bits ({f.getcomptype()})")
+        rate, channels = f.getframerate(), f.getnchannels()
+        raw = f.readframes(f.getnframes())
+    pcm = np.frombuffer(raw, dtype="<i2").astype(np.int16).reshape(-1, channels)
+    return torch.from_numpy(pcm), rate
+
+
+def write_wav(path, samples: torch.Tensor, rate: int) -> None:
+    """f32 samples (any shape, flattened) -> 16-bit PCM mono WAV: round(x * 32768), ties to even, clipped to [-32768, 32767]
+    (the inverse of ``read_wav`` on every value a 16-bit file can hold)."""
+    x = samples.detach().reshape(-1).to("cpu", torch.float64).numpy()
+    pcm = np.clip(np.rint(x * 32768.0), -32768, 32767).astype("<i2")
+    with wave.open(os.fspath(path), "wb") as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(rate))
+        f.writeframes(pcm.tobytes())
+
+
+def resample_wav(input_path, output_path, sampling_rate: int = 22050, device="cuda") -> None:
+    """The reference's ``resample_wav`` (``convert.py:131-146``): channel 0 of a 16-bit PCM WAV, resampled to ``sampling_rate``
+    on ``device``, saved as 16-bit mono.  A file already at the rate keeps its channel 0 bit for bit."""
+    pcm, rate = read_pcm(input_path)
+    if rate == sampling_rate:
+        write_wav(output_path, pcm[:, 0].to(torch.float32) / 32768.0, rate)
+        return
+    resampler = Resample(rate, sampling_rate).to(device)
+    out, _ = resampler.forward_packed(pcm.reshape(-1).to(resampler._device("resample_wav")), [pcm.shape[0]], channels=pcm.shape[1])
+    write_wav(output_path, out, sampling_rate)
+
+
+def group_by_format(info: dict) -> dict:
+    """{name: (frames, rate, channels)} -> {(rate, channels): names sorted by (frames, name)}, keys in ascending order: the launches
+    of ``preprocess_directory(resample=True)`` share a rate and a channel count."""
+    groups = {}
+    for name, (_, rate, channels) in info.items():
+        groups.setdefault((rate, channels), []).append(name)
+    return {key: sorted(groups[key], key=lambda name: (info[name][0], name)) for key in sorted(groups)}
+
+
+def _batches(order: Sequence[str], size: dict, max_batch_samples: int):
+    """Consecutive runs of ``order`` of at most ``max_batch_samples`` samples and MEL_MAX_SEGMENTS files (one file alone may
+    exceed the former)."""
     i = 0
     while i < len(order):
         batch, count = [], 0
-        while i < len(order) and len(batch) < MEL_MAX_SEGMENTS and (not batch or count + samples[order[i]] <= max_batch_samples):
+        while i < len(order) and len(batch) < MEL_MAX_SEGMENTS and (not batch or count + size[order[i]] <= max_batch_samples):
             batch.append(order[i])
-            count += samples[order[i]]
+            count += size[order[i]]
             i += 1
-        waves = [read_wav(os.path.join(audio_dir, name))[0] for name in batch]
-        packed, foff = creator.forward_packed(torch.cat(waves).to(dev), [w.numel() for w in waves])
-        host = packed.cpu()
-        for j, name in enumerate(batch):
-            path = os.path.join(mel_dir, name[:-len(suffix)] + ".pt")
-            torch.save(host[:, foff[j]:foff[j + 1]].unsqueeze(0).clone(), path)
-            written[name] = path
+        yield batch
+
+
+def _save_batch(packed: torch.Tensor, foff: Sequence[int], batch: Sequence[str], mel_dir, suffix: str, written: dict) -> None:
+    host = packed.cpu()
+    for j, name in enumerate(batch):
+        path = os.path.join(mel_dir, name[:-len(suffix)] + ".pt")
+        torch.save(host[:, foff[j]:foff[j + 1]].unsqueeze(0).clone(), path)
+        written[name] = path
+
+
+def _read_channel0(path) -> torch.Tensor:
+    pcm, _ = read_pcm(path)
+    return torch.from_numpy(pcm[:, 0].numpy().astype(np.float32) / 32768.0)
+
+
+def preprocess_directory(audio_dir, mel_dir, creator: _LogMel, max_batch_samples: int = 1 << 24, suffix: str = ".wav",
+                         resample: bool = False) -> List[str]:
+    """The loop of ``preprocess.py:100-108``, batched: every ``*.wav`` of ``audio_dir`` -> ``mel_dir/<stem>.pt`` (the
+    reference's file format).  Files are sorted by length and packed into ragged launches of at most ``max_batch_samples``
+    samples (one file alone may exceed it); only one batch of audio is in host memory at a time.  A file whose sample rate is
+    not the creator's raises -- unless ``resample`` is set: then the reference's ``resample_wav`` step (``preprocess.py:81-87``)
+    runs in front, on the GPU.  16-bit PCM files of any rate and channel count are grouped by (rate, channels); a batch of a
+    group is uploaded as raw PCM, channel 0 is resampled to ``creator.sample_rate`` by one ``rtts_resample`` launch, and its
+    packed output feeds the mel launch without leaving the device (``max_batch_samples`` counts input frames).  Mono files
+    already at the rate take the path above.  -> the written paths, in the order of the sorted input names."""
+    dev = creator._device("preprocess_directory")
+    names = sorted(f for f in os.listdir(audio_dir) if f.endswith(suffix))
+    os.makedirs(mel_dir, exist_ok=True)
+    written = {}
+    if not resample:
+        samples = {}
+        for name in names:                                         # headers only: the audio is decoded batch by batch
+            samples[name], rate = wav_info(os.path.join(audio_dir, name))
+            creator._check_rate(rate, os.path.join(audio_dir, name))
+        for batch in _batches(sorted(names, key=lambda name: (samples[name], name)), samples, max_batch_samples):
+            waves = [read_wav(os.path.join(audio_dir, name))[0] for name in batch]
+            packed, foff = creator.forward_packed(torch.cat(waves).to(dev), [w.numel() for w in waves])
+            _save_batch(packed, foff, batch, mel_dir, suffix, written)
+        return [written[name] for name in names]
+    info = {name: pcm_info(os.path.join(audio_dir, name)) for name in names}
+    frames = {name: info[name][0] for name in names}
+    for (rate, channels), order in group_by_format(info).items():
+        resampler = None if rate == creator.sample_rate else Resample(rate, creator.sample_rate).to(dev)
+        for name in order:
+            m = frames[name] if resampler is None else resample_len(frames[name], rate, creator.sample_rate)
+            if m <= creator.n_fft // 2:
+                raise ValueError(f"{os.path.join(audio_dir, name)}: {m} samples at {creator.sample_rate} Hz; reflect padding needs "
+                                 f"more than n_fft / 2 = {creator.n_fft // 2}")
+        for batch in _batches(order, frames, max_batch_samples):
+            paths = [os.path.join(audio_dir, name) for name in batch]
+            if resampler is None:                                  # at the rate already: channel 0, decoded on the host as read_wav does
+                waves = [read_wav(p)[0] if channels == 1 else _read_channel0(p) for p in paths]
+                packed, foff = creator.forward_packed(torch.cat(waves).to(dev), [w.numel() for w in waves])
+            else:
+                raw = torch.cat([read_pcm(p)[0].reshape(-1) for p in paths]).to(dev)
+                audio, ooff = resampler.forward_packed(raw, [frames[name] for name in batch], channels=channels)
+                packed, foff = creator.forward_packed(audio, [ooff[j + 1] - ooff[j] for j in range(len(batch))])
+            _save_batch(packed, foff, batch, mel_dir, suffix, written)
     return [written[name] for name in names]

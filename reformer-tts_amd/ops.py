@@ -215,3 +215,32 @@ def mel_spectrogram(audio: torch.Tensor, sample_offsets_host, frame_offsets_host
               out.data_ptr(), out.stride(0), _stream())
     TIMING.stop(ev, 2.0 * frames * (n_fft * n_fft + n_mels * (n_fft // 2 + 1)))
     return out
+
+
+def resample(audio: torch.Tensor, in_offsets_host, out_offsets_host, offsets: torch.Tensor, nseg: int, first: torch.Tensor,
+             taps_table: torch.Tensor, orig_red: int, new_red: int, out: torch.Tensor, channels: int = 1) -> torch.Tensor:
+    """audio: the utterances end to end, flat f32 (mono) or flat int16 (``channels`` interleaved, channel 0 is taken); offsets:
+    (2, nseg + 1) i64 device table [input frame offsets; output offsets] and the same values as two host ``ctypes.c_int64``
+    arrays; first (new_red,) i32 and taps_table (taps, new_red) f32 from ``dataset.audio.resample_tables`` -> out, flat f32 of
+    >= out_offsets[nseg] samples: one ``rtts_resample`` launch on the current stream."""
+    if not (audio.is_cuda and audio.dtype in (torch.float32, torch.int16)):
+        raise _lib.RttsError(f"resample runs on the GPU only: audio must be a CUDA float32 or int16 tensor (got {audio.dtype} on {audio.device})")
+    for name, t, dt in (("first", first, torch.int32), ("taps_table", taps_table, torch.float32), ("out", out, torch.float32)):
+        if not (t.is_cuda and t.dtype == dt):
+            raise _lib.RttsError(f"resample runs on the GPU only: {name} must be a CUDA {dt} tensor (got {t.dtype} on {t.device})")
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.shape == (2, nseg + 1) and offsets.is_contiguous()):
+        raise ValueError(f"offsets: expected a contiguous CUDA int64 (2, {nseg + 1}) table")
+    if not (audio.dim() == 1 and audio.is_contiguous() and out.dim() == 1 and out.is_contiguous() and first.is_contiguous()
+            and taps_table.dim() == 2 and taps_table.is_contiguous() and tuple(first.shape) == (new_red,)
+            and taps_table.shape[1] == new_red):
+        raise ValueError("resample: audio and out flat, first (new_red,), taps_table (taps, new_red)")
+    if audio.numel() < in_offsets_host[nseg] * channels or out.numel() < out_offsets_host[nseg]:
+        raise ValueError(f"resample: {audio.numel()} input values / {out.numel()} output samples for offsets ending at "
+                         f"{in_offsets_host[nseg]} frames of {channels} channel(s) / {out_offsets_host[nseg]}")
+    taps = taps_table.shape[0]
+    ev = TIMING.start(f"rtts_resample/{orig_red}to{new_red}")
+    _lib.call("rtts_resample", audio.data_ptr(), 0 if audio.dtype == torch.float32 else 1, channels, in_offsets_host, out_offsets_host,
+              offsets[0].data_ptr(), offsets[1].data_ptr(), nseg, first.data_ptr(), taps_table.data_ptr(), orig_red, new_red, taps,
+              out.data_ptr(), _stream())
+    TIMING.stop(ev, 2.0 * taps * out_offsets_host[nseg])
+    return out
