@@ -526,6 +526,32 @@ int rtts_sw_pack_mel(const float* mel, int64_t stride_b, int64_t stride_c, int64
                      int nseg, int64_t rows, float* dst, int64_t ld_dst, void* stream);
 int rtts_sw_coupling_inv1x1(const float* audio, int64_t ld_audio, const float* wn_out, int64_t ld_wn, const float* winv, int n,
                             int64_t rows, float* out, int64_t ld_out, void* stream);
+/* The analysis direction, audio -> latent z with its likelihood terms (SqueezeWave.forward, squeeze_wave/modules.py:294-332, in
+ * eval mode, and SqueezeWaveLoss, squeeze_wave/loss.py:14-31), over the same channels-last fp32 rows:
+ *   rtts_sw_coupling_fwd1x1  one flow boundary, the mirror of rtts_sw_coupling_inv1x1: the previous flow's affine coupling
+ *                         c = [x0 | exp(log_s) * x1 + b] (:326-327) with [log_s | b] = wn_out (row stride ld_wn, half = n_in / 2),
+ *                         this flow's early output (:312-314: columns [0, n_early) of c -> z[:, z_col : z_col + n_early]) and
+ *                         this flow's invertible 1x1 convolution (:53-65, :316) of the remaining n = n_in - n_early columns:
+ *                         out (rows, n) = c[:, n_early:] @ w^T, w (n, n) fp32 row-major.  ls_row[row] += sum_c log_s[row][c]
+ *                         (fp32, a fixed order per row, no atomics: the caller zeroes it once; :328 and loss.py:23-24).
+ *                         wn_out NULL: the first flow, no coupling and ls_row untouched.  w NULL: the tail after the last
+ *                         flow, n_early == n_in and everything goes to z (:329-331).  n_in even, <= 128; n_early and n even;
+ *                         NOT in place (out != x); fp32 FMA arithmetic
+ *   rtts_sw_nll_reduce    out (nseg, 2) FLOAT64 = {sum z^2, sum ls_row} per segment (loss.py:21-28, per utterance): z (rows, C)
+ *                         with row stride ld_z; segment s = audio rows [upsample * moff[s], upsample * moff[s+1]) of the device
+ *                         offset table, clamped to [0, rows), or rows [s * L, (s + 1) * L) with moff NULL (nseg * L == rows).
+ *                         One workgroup per segment, float64 accumulation in a fixed order; rows of no segment are not read;
+ *                         an empty segment gives zeros
+ *   rtts_sw_pack_audio    dst (rows, C) fp32 contiguous = the packed audio rows (:304-306 `unfold` per utterance, laid end to
+ *                         end): utterance s contributes exactly upsample * C * (moff[s+1] - moff[s]) samples, read from
+ *                         src[start[s] ...] (start: DEVICE int64 table of nseg first-sample indices into the flat fp32 buffer
+ *                         src of n_src samples); elements past the total, or whose source index falls outside src, are zero */
+int rtts_sw_coupling_fwd1x1(const float* x, int64_t ld_x, const float* wn_out, int64_t ld_wn, const float* w, int n_in, int n_early,
+                            int64_t rows, float* out, int64_t ld_out, float* z, int64_t ld_z, int z_col, float* ls_row, void* stream);
+int rtts_sw_nll_reduce(const float* z, int64_t ld_z, int C, const float* ls_row, const int32_t* moff, int nseg, int upsample, int64_t L,
+                       int64_t rows, double* out, void* stream);
+int rtts_sw_pack_audio(const float* src, int64_t n_src, const int64_t* start, const int32_t* moff, int nseg, int upsample, int C,
+                       int64_t rows, float* dst, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

@@ -133,6 +133,9 @@ SIGNATURES = {
     "rtts_sw_depthwise_k3_seg": [_vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp],
     "rtts_sw_pack_mel": [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _i64, _vp],
     "rtts_sw_coupling_inv1x1": [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _vp, _i64, _vp],
+    "rtts_sw_coupling_fwd1x1": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp],
+    "rtts_sw_nll_reduce": [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp],
+    "rtts_sw_pack_audio": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],

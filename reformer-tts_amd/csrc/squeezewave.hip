@@ -289,3 +289,209 @@ extern "C" int rtts_sw_coupling_inv1x1(const float* audio, int64_t ld_audio, con
     RTTS_LAUNCH_CHECK("rtts_sw_coupling_inv1x1");
     return 0;
 }
+
+// ------------------------------------------------------------------ forward (analysis) direction: audio -> latent z
+// One flow boundary of SqueezeWave.forward (reference reformer_tts/squeeze_wave/modules.py:311-328), the mirror of the
+// kernel above: the PREVIOUS flow's affine coupling c = [x0 | exp(log_s) * x1 + b] (:326-327), this flow's early output
+// (:312-314: the first n_early columns of c go to z at column z_col) and this flow's invertible 1x1 convolution (:53-65,
+// y[c] = sum_k W[c][k] x[k]) over the remaining n = n_in - n_early columns, in one fp32 launch.  wn == null: the first flow
+// (no coupling in front of it); w == null: the tail after the last flow (n_early == n_in, everything goes to z).
+// Same shape as the inverse kernel: 32 rows per workgroup, W^T and the coupled rows in LDS, thread (row, g) owns the output
+// columns g, g + 8, ...  The eight lanes of a row also sum its log_s (columns g, g + 8, ... in order, then the fixed DPP
+// tree of rtts_sum8): one workgroup owns a row's sum, no atomics, and the order does not depend on where the row falls in a
+// workgroup.  ls_row[row] += that sum.
+__global__ __launch_bounds__(SW_THREADS) void sw_coupling_fwd1x1_kernel(const float* __restrict__ x, int64_t ld_x,
+                                                                        const float* __restrict__ wn, int64_t ld_wn,
+                                                                        const float* __restrict__ w, int n_in, int n_early, long long rows,
+                                                                        float* __restrict__ out, int64_t ld_out, float* __restrict__ z,
+                                                                        int64_t ld_z, int z_col, float* __restrict__ ls_row) {
+    extern __shared__ __attribute__((aligned(16))) float swf_smem[];
+    const int n = n_in - n_early, half = n_in / 2;
+    float* Wt = swf_smem;                     // [n][n]: Wt[k][c] = W[c][k]
+    float* X = Wt + n * n;                    // [SWI_ROWS][n_in + 1]: the coupled rows
+    const int tid = threadIdx.x;
+    if (w) {
+        for (int i = tid; i < n * n; i += SW_THREADS) {
+            const int c = i / n, k = i % n;
+            Wt[k * n + c] = w[i];
+        }
+    }
+    const long long r0 = (long long)blockIdx.x * SWI_ROWS;
+    for (int i = tid; i < SWI_ROWS * n_in; i += SW_THREADS) {
+        const int rr = i / n_in, k = i % n_in;
+        const long long row = r0 + rr;
+        float v = 0.f;
+        if (row < rows) {
+            v = x[row * ld_x + k];
+            if (wn && k >= half) {
+                const float s = wn[row * ld_wn + (k - half)], b = wn[row * ld_wn + k];
+                v = __builtin_fmaf(__expf(s), v, b);
+            }
+        }
+        X[rr * (n_in + 1) + k] = v;
+    }
+    __syncthreads();
+    const int rr = tid >> 3, g = tid & 7;
+    const long long row = r0 + rr;
+    const float* xr = X + rr * (n_in + 1);
+    if (row < rows) {
+        for (int k = g; k < n_early; k += 8) z[row * ld_z + z_col + k] = xr[k];
+    }
+    if (wn) {                                 // all 64 lanes of a wave take part in the DPP sum: rows past the end add zeros
+        float ls = 0.f;
+        if (row < rows) {
+            for (int k = g; k < half; k += 8) ls += wn[row * ld_wn + k];
+        }
+        ls = rtts_sum8(ls);
+        if (row < rows && g == 0) ls_row[row] += ls;
+    }
+    if (!w) return;
+    float acc[SWI_MAXN / 8];
+#pragma unroll
+    for (int j = 0; j < SWI_MAXN / 8; ++j) acc[j] = 0.f;
+    xr += n_early;
+    for (int k = 0; k < n; ++k) {
+        const float xv = xr[k];
+        const float* wk = Wt + k * n + g;
+#pragma unroll
+        for (int j = 0; j < SWI_MAXN / 8; ++j)
+            if (g + 8 * j < n) acc[j] = __builtin_fmaf(xv, wk[8 * j], acc[j]);
+    }
+    if (row < rows) {
+#pragma unroll
+        for (int j = 0; j < SWI_MAXN / 8; ++j)
+            if (g + 8 * j < n) out[row * ld_out + g + 8 * j] = acc[j];
+    }
+}
+
+static RttsLdsState g_swf_lds;
+
+extern "C" int rtts_sw_coupling_fwd1x1(const float* x, int64_t ld_x, const float* wn_out, int64_t ld_wn, const float* w, int n_in, int n_early,
+                                       int64_t rows, float* out, int64_t ld_out, float* z, int64_t ld_z, int z_col, float* ls_row,
+                                       void* stream) {
+    RTTS_ENTER(stream);
+    RTTS_REQUIRE(n_in >= 2 && n_in % 2 == 0 && n_in <= SWI_MAXN, "rtts_sw_coupling_fwd1x1: n_in must be even and <= %d (got n_in=%d)", SWI_MAXN,
+                 n_in);
+    RTTS_REQUIRE(n_early >= 0 && n_early <= n_in && n_early % 2 == 0,
+                 "rtts_sw_coupling_fwd1x1: n_early must be even and within [0, n_in] (got n_early=%d, n_in=%d)", n_early, n_in);
+    const int n = n_in - n_early;
+    RTTS_REQUIRE(x && rows > 0 && ld_x >= n_in && (!wn_out || (ld_wn >= n_in && ls_row)),
+                 "rtts_sw_coupling_fwd1x1: bad arguments (x, rows > 0, leading dimensions >= n_in, ls_row with wn_out)");
+    RTTS_REQUIRE(n_early == 0 || (z && z_col >= 0 && ld_z >= (int64_t)z_col + n_early),
+                 "rtts_sw_coupling_fwd1x1: the early output needs z with ld_z >= z_col + n_early (got z_col=%d, n_early=%d)", z_col, n_early);
+    if (w) {
+        RTTS_REQUIRE(n >= 2 && out && ld_out >= n, "rtts_sw_coupling_fwd1x1: the convolution needs n = n_in - n_early >= 2 and out with ld_out >= n");
+        RTTS_REQUIRE(out != x, "rtts_sw_coupling_fwd1x1: not in place (a block reads rows of x that another may have rewritten)");
+    } else {
+        RTTS_REQUIRE(n == 0, "rtts_sw_coupling_fwd1x1: without W every column is early output: n_early must equal n_in (got %d, %d)", n_early, n_in);
+    }
+    RTTS_REQUIRE(!z || (z != x && z != out), "rtts_sw_coupling_fwd1x1: z must not alias x or out");
+    const size_t lds = ((size_t)n * n + (size_t)SWI_ROWS * (n_in + 1)) * sizeof(float);
+    RTTS_ENSURE_LDS("rtts_sw_coupling_fwd1x1", sw_coupling_fwd1x1_kernel, lds, g_swf_lds);
+    const unsigned blocks = (unsigned)((rows + SWI_ROWS - 1) / SWI_ROWS);
+    hipLaunchKernelGGL(sw_coupling_fwd1x1_kernel, dim3(blocks), dim3(SW_THREADS), lds, (hipStream_t)stream, x, ld_x, wn_out, ld_wn, w, n_in,
+                       n_early, (long long)rows, out, ld_out, z, ld_z, z_col, ls_row);
+    RTTS_LAUNCH_CHECK("rtts_sw_coupling_fwd1x1");
+    return 0;
+}
+
+// Per-utterance sums of the negative log-likelihood (reference reformer_tts/squeeze_wave/loss.py:21-28): out[s] =
+// {sum z^2, sum log_s} over the rows of segment s, in float64.  Segment s = audio rows [up * moff[s], up * moff[s+1]) of the
+// offset table (clamped to [0, rows), like sw_segment_of: a malformed table cannot send a read outside the buffers), or rows
+// [s * L, (s + 1) * L) when moff is null.  One workgroup per segment: thread t adds elements t, t + 256, ... of the segment
+// (counted from ITS first row) in order, then a fixed LDS tree -- a segment's sums depend on its rows only, not on where
+// they lie.  Rows outside every segment (capacity padding, rows before moff[0]) are never read; an empty segment gives zeros.
+__global__ __launch_bounds__(SW_THREADS) void sw_nll_reduce_kernel(const float* __restrict__ z, int64_t ld_z, int C,
+                                                                   const float* __restrict__ ls_row, const int* __restrict__ moff, int up,
+                                                                   long long L, long long rows, double* __restrict__ out) {
+    __shared__ double s_sq[SW_THREADS], s_ls[SW_THREADS];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    long long a, e;
+    if (moff) {
+        a = (long long)up * moff[s];
+        e = (long long)up * moff[s + 1];
+    } else {
+        a = (long long)s * L;
+        e = a + L;
+    }
+    a = a < 0 ? 0 : (a > rows ? rows : a);
+    e = e < a ? a : (e > rows ? rows : e);
+    const long long nel = (e - a) * C;
+    double sq = 0.0, ls = 0.0;
+    const float* zs = z + a * ld_z;
+    const bool dense = ld_z == C;             // no row stride: the segment is one contiguous run (no division per element)
+    for (long long i = tid; i < nel; i += SW_THREADS) {
+        const float v = dense ? zs[i] : zs[(i / C) * ld_z + i % C];
+        sq += (double)v * (double)v;
+    }
+    for (long long r = a + tid; r < e; r += SW_THREADS) ls += (double)ls_row[r];
+    s_sq[tid] = sq;
+    s_ls[tid] = ls;
+    __syncthreads();
+    for (int w = SW_THREADS / 2; w > 0; w >>= 1) {
+        if (tid < w) {
+            s_sq[tid] += s_sq[tid + w];
+            s_ls[tid] += s_ls[tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[2 * s] = s_sq[0];
+        out[2 * s + 1] = s_ls[0];
+    }
+}
+
+extern "C" int rtts_sw_nll_reduce(const float* z, int64_t ld_z, int C, const float* ls_row, const int32_t* moff, int nseg, int upsample,
+                                  int64_t L, int64_t rows, double* out, void* stream) {
+    RTTS_ENTER(stream);
+    RTTS_REQUIRE(z && ls_row && out && C > 0 && ld_z >= C && rows > 0 && upsample >= 1, "rtts_sw_nll_reduce: bad arguments");
+    RTTS_REQUIRE(nseg >= 1 && nseg <= SW_MAX_SEGMENTS, "rtts_sw_nll_reduce: 1..%d segments (got %d)", SW_MAX_SEGMENTS, nseg);
+    RTTS_REQUIRE(moff || (L > 0 && (int64_t)nseg * L == rows),
+                 "rtts_sw_nll_reduce: without an offset table the rows are nseg segments of L rows (got nseg=%d, L=%lld, rows=%lld)", nseg,
+                 (long long)L, (long long)rows);
+    hipLaunchKernelGGL(sw_nll_reduce_kernel, dim3((unsigned)nseg), dim3(SW_THREADS), 0, (hipStream_t)stream, z, ld_z, C, ls_row, (const int*)moff,
+                       upsample, (long long)L, (long long)rows, out);
+    RTTS_LAUNCH_CHECK("rtts_sw_nll_reduce");
+    return 0;
+}
+
+// Packed audio rows for the ragged likelihood, the audio twin of sw_pack_mel_kernel: dst (rows, C) fp32 contiguous, i.e.
+// the reference's audio.unfold(1, C, C) (modules.py:304-306) of every utterance laid end to end.  Utterance s contributes
+// exactly up * C * (moff[s+1] - moff[s]) samples (256 per mel frame for the reference's configurations), read from
+// src[start[s] + j]; every element past the total, and any whose source index would fall outside [0, n_src), is zero.
+__global__ __launch_bounds__(SW_THREADS) void sw_pack_audio_kernel(const float* __restrict__ src, long long n_src,
+                                                                   const long long* __restrict__ start, const int* __restrict__ moff, int nseg,
+                                                                   long long spf, size_t n, float* __restrict__ dst) {
+    __shared__ int s_off[SW_MAX_SEGMENTS + 1];
+    for (int i = threadIdx.x; i <= nseg; i += blockDim.x) s_off[i] = moff[i];
+    __syncthreads();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const long long f = (long long)(i / (size_t)spf);          // mel frame of this sample
+        int lo = 0, hi = nseg + 1;                                 // s = (first offset above f) - 1
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= f) lo = mid + 1;
+            else hi = mid;
+        }
+        const int s = lo - 1;
+        float v = 0.f;
+        if (s >= 0 && s < nseg && f < s_off[s + 1]) {
+            const long long j = start[s] + ((long long)i - spf * s_off[s]);
+            if (j >= 0 && j < n_src) v = src[j];
+        }
+        dst[i] = v;
+    }
+}
+
+extern "C" int rtts_sw_pack_audio(const float* src, int64_t n_src, const int64_t* start, const int32_t* moff, int nseg, int upsample, int C,
+                                  int64_t rows, float* dst, void* stream) {
+    RTTS_ENTER(stream);
+    RTTS_REQUIRE(src && start && moff && dst && n_src > 0 && upsample >= 1 && C > 0 && rows > 0 && rows % upsample == 0,
+                 "rtts_sw_pack_audio: bad arguments (rows a multiple of upsample)");
+    RTTS_REQUIRE(nseg >= 1 && nseg <= SW_MAX_SEGMENTS, "rtts_sw_pack_audio: 1..%d segments (got %d)", SW_MAX_SEGMENTS, nseg);
+    const size_t n = (size_t)rows * C;
+    hipLaunchKernelGGL(sw_pack_audio_kernel, dim3(sw_grid(n)), dim3(SW_THREADS), 0, (hipStream_t)stream, src, (long long)n_src,
+                       (const long long*)start, (const int*)moff, nseg, (long long)upsample * C, n, dst);
+    RTTS_LAUNCH_CHECK("rtts_sw_pack_audio");
+    return 0;
+}

@@ -1,2 +1,3 @@
 from .config import SqueezeWaveConfig, WNConfig  # noqa: F401
 from .modules import SqueezeWave  # noqa: F401
+from .loss import SqueezeWaveLoss, validation_loss  # noqa: F401

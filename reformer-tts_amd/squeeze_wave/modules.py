@@ -17,7 +17,13 @@ modules here only HOLD parameters.  ``infer`` (:334-376) runs through an explici
 * the inverse of each invertible 1x1 convolution is cached (fp32) like the reference's ``W_inverse`` and applied, with the
   inverse coupling in front of it, by the fp32 kernel ``rtts_sw_coupling_inv1x1``.
 
-There is no CPU fallback: ``infer`` raises off the GPU."""
+The analysis direction, ``forward`` (:294-332) and the likelihood ``nll`` / ``nll_ragged`` / ``capture_nll_ragged``
+(``squeeze_wave/loss.py:14-31``), runs the same folded WN blocks in eval mode (running-statistics BatchNorm): per flow one
+``rtts_sw_coupling_fwd1x1`` launch (the previous flow's coupling, this flow's early output and 1x1 convolution) in front of
+``_FoldedWN.forward``, and one ``rtts_sw_nll_reduce`` launch for the per-utterance sums.  Training-mode BatchNorm and the
+backward are not on the HIP path.
+
+There is no CPU fallback: ``infer`` and ``forward`` raise off the GPU."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -296,8 +302,12 @@ class SqueezeWave(nn.Module):
                 # twelve matrices of at most 128 x 128, once per parameter version: inverted on the host in float64 (LAPACK) -- no
                 # device library (rocSOLVER / hipBLAS) call anywhere in the vocoder
                 dev = self.inv_conv_layers[0].conv.weight.device
-                self._winv = [conv.conv.weight.detach().squeeze(-1).double().cpu().inverse().float().contiguous().to(dev)
-                              for conv in self.inv_conv_layers]
+                w64 = [conv.conv.weight.detach().squeeze(-1).double().cpu() for conv in self.inv_conv_layers]
+                self._winv = [w.inverse().float().contiguous().to(dev) for w in w64]
+                # the forward direction: W itself (fp32, as the reference's conv applies it) and log det W in float64 on the
+                # host (modules.py:63 computes it per call in fp32); (sign, log|det|) per flow, judged where it is used
+                self._wfwd = [conv.conv.weight.detach().squeeze(-1).float().contiguous() for conv in self.inv_conv_layers]
+                self._slogdet = [tuple(float(v) for v in torch.linalg.slogdet(w)) for w in w64]
             self._folded_key = key
         return self._folded
 
@@ -499,3 +509,244 @@ class SqueezeWave(nn.Module):
         cache[key] = run
         return run
 
+
+    # ------------------------------------------------------------------ the analysis direction: audio -> z, likelihood
+    def _logdets(self) -> List[float]:
+        """log det W of every flow (float64, cached by ``_fold``).  The reference's ``torch.logdet`` (modules.py:63) returns
+        NaN for a negative determinant and -inf for a singular W; here that is an error that names the flow."""
+        self._fold()
+        for k, (sign, _) in enumerate(self._slogdet):
+            if sign <= 0:
+                raise ValueError(f"inv_conv_layers.{k}: det W is {'zero' if sign == 0 else 'negative'}: log det W is undefined, the flow "
+                                 "has no likelihood (the reference's torch.logdet would return NaN or -inf)")
+        return [v for _, v in self._slogdet]
+
+    def _likelihood_device(self, what: str) -> torch.device:
+        dev = self._device(what)
+        if self.training:
+            raise _lib.RttsError(f"SqueezeWave.{what} needs eval mode: batch-statistics (training-mode) BatchNorm is not on the HIP path, "
+                                 "the likelihood is computed with the running statistics (call .eval())")
+        return dev
+
+    @staticmethod
+    def _on_device(t: torch.Tensor, dev, what: str, name: str) -> torch.Tensor:
+        if not torch.is_tensor(t) or t.device != dev:
+            raise _lib.RttsError(f"SqueezeWave.{what} runs on the GPU only: {name} is on {getattr(t, 'device', type(t).__name__)}, the model on {dev}")
+        return t
+
+    def _flows_fwd(self, folded: List[_FoldedWN], mel_rows: torch.Tensor, seg: _Segments, audio_rows: torch.Tensor, keep: bool):
+        """The executor of ``forward`` (modules.py:308-331) over rows: audio rows fp32 (seg.rows, n_audio_channels) ->
+        (z rows (seg.rows, n_audio_channels): the early blocks in flow order, then the remainder; ls_row (seg.rows,): every
+        row's sum of log_s over all flows; the WN outputs [log_s | b | padding] per flow if ``keep``).  Per flow: one
+        boundary launch (the previous flow's coupling, this flow's early split and 1x1 convolution), then the WN block;
+        a last launch applies the final coupling."""
+        rows, dev = seg.rows, audio_rows.device
+        z = torch.empty(rows, self.n_audio_channels, dtype=torch.float32, device=dev)
+        ls_row = torch.zeros(rows, dtype=torch.float32, device=dev)
+        x, wn_prev, zcol, kept = audio_rows, None, 0, []
+
+        def boundary(w, n_early, out):
+            _lib.call("rtts_sw_coupling_fwd1x1", x.data_ptr(), x.stride(0), None if wn_prev is None else wn_prev.data_ptr(),
+                      0 if wn_prev is None else wn_prev.stride(0), None if w is None else w.data_ptr(), x.shape[1], n_early, rows,
+                      None if out is None else out.data_ptr(), 0 if out is None else out.stride(0), z.data_ptr(), z.stride(0), zcol,
+                      ls_row.data_ptr(), _s())
+
+        for k in range(self.n_flows):
+            n_early = self.early_return_size if self.return_early(k) else 0
+            out = torch.empty(rows, x.shape[1] - n_early, dtype=torch.float32, device=dev)
+            boundary(self._wfwd[k], n_early, out)
+            zcol += n_early
+            x = out
+            wn_prev = folded[k].forward(x, mel_rows, seg)                          # [log_s | b | padding], row stride n_end
+            if keep:
+                kept.append(wn_prev)
+        boundary(None, x.shape[1], None)
+        return z, ls_row, kept
+
+    def _uniform_rows(self, mel: torch.Tensor, audio: torch.Tensor, dev, what: str):
+        """(mel (B, n_mel, Lm), audio (B, 256 * Lm)) on the device -> (mel rows, audio rows, segments, B, L)."""
+        self._on_device(mel, dev, what, "mel")
+        self._on_device(audio, dev, what, "audio")
+        up, c = self._up(), self.n_audio_channels
+        if mel.dim() != 3 or mel.shape[1] != self._n_mel() or mel.shape[0] < 1 or mel.shape[2] < 1:
+            raise ValueError(f"SqueezeWave.{what}: mel {tuple(mel.shape)} is not (B, {self._n_mel()}, Lm)")
+        b, n_mel, mel_len = mel.shape
+        if tuple(audio.shape) != (b, up * c * mel_len):
+            raise ValueError(f"SqueezeWave.{what}: audio {tuple(audio.shape)} is not (B, {up * c} * Lm) = ({b}, {up * c * mel_len}) for mel "
+                             f"{tuple(mel.shape)}")
+        mel_rows = mel.to(torch.float32).permute(0, 2, 1).reshape(b * mel_len, n_mel).contiguous()
+        audio_rows = audio.to(torch.float32).reshape(b * up * mel_len, c).contiguous()      # unfold(1, C, C): row l = samples [l*C, (l+1)*C)
+        return mel_rows, audio_rows, _Segments.uniform(b, mel_len, up), b, up * mel_len
+
+    @torch.no_grad()
+    def forward(self, forward_input):
+        """``modules.py:294-332`` in eval mode: (mel (B, n_mel, Lm), audio (B, 256 * Lm)) -> (z (B, n_audio_channels, L),
+        log_s_list, log_det_W_list) with L = 256 * Lm / n_audio_channels; z = the early outputs in flow order, then the
+        remainder.  ``log_s_list[k]`` (B, n_half_k, L) is a view of flow k's WN output; ``log_det_W_list[k]`` = B * L * log det
+        W_k (fp32, 0-dim), log det taken in float64 at fold time.  ``SqueezeWaveLoss(sigma)`` of this tuple is ``nll``."""
+        mel, audio = forward_input
+        dev = self._likelihood_device("forward")
+        folded, logdet = self._fold(), self._logdets()
+        mel_rows, audio_rows, seg, b, length = self._uniform_rows(mel, audio, dev, "forward")
+        z, _, kept = self._flows_fwd(folded, mel_rows, seg, audio_rows, True)
+        log_s = [w[:seg.rows, :f.n_half].unflatten(0, (b, length)).permute(0, 2, 1) for w, f in zip(kept, folded)]
+        ld = torch.tensor([b * length * v for v in logdet], dtype=torch.float64).to(torch.float32).to(dev)
+        return z.view(b, length, -1).permute(0, 2, 1), log_s, list(ld.unbind(0))
+
+    def _nll_from_sums(self, sums: torch.Tensor, nrows: torch.Tensor, sigma: float, logdet: List[float]):
+        """``loss.py:21-31`` from the per-utterance sums: sums (n, 2) float64 = {sum z^2, sum log_s}, nrows (n,) float64 = audio
+        rows per utterance -> (per-utterance loss (n,) fp32: 0 / 0 = NaN for an empty one, loss of the whole batch 0-dim fp32)."""
+        c = self.n_audio_channels
+        num = sums[:, 0] / (2.0 * float(sigma) ** 2) - sums[:, 1] - nrows * sum(logdet)
+        return (num / (nrows * c)).float(), (num.sum() / (nrows.sum() * c)).float()
+
+    def _reduce(self, z: torch.Tensor, ls_row: torch.Tensor, seg: _Segments) -> torch.Tensor:
+        n = seg.b if seg.moff is None else seg.nseg
+        sums = torch.empty(n, 2, dtype=torch.float64, device=z.device)
+        _lib.call("rtts_sw_nll_reduce", z.data_ptr(), z.stride(0), z.shape[1], ls_row.data_ptr(), None if seg.moff is None else seg.moff.data_ptr(),
+                  n, seg.up, seg.length, seg.rows, sums.data_ptr(), _s())
+        return sums
+
+    @torch.no_grad()
+    def nll(self, mel: torch.Tensor, audio: torch.Tensor, sigma: float = 1.0) -> torch.Tensor:
+        """The negative log-likelihood per element of ``audio`` under the flow, ``SqueezeWaveLoss(sigma)(self((mel, audio)))``
+        (``loss.py:14-31``; what ``LitSqueezeWave.validation_step`` logs, ``training/wrappers.py:361-368``), without the
+        ``log_s`` list: every flow boundary adds its rows' sums of log_s into one fp32 vector, and one launch reduces z^2 and
+        that vector per utterance in float64 -> 0-dim fp32 on the device."""
+        dev = self._likelihood_device("nll")
+        folded, logdet = self._fold(), self._logdets()
+        mel_rows, audio_rows, seg, b, length = self._uniform_rows(mel, audio, dev, "nll")
+        z, ls_row, _ = self._flows_fwd(folded, mel_rows, seg, audio_rows, False)
+        nrows = torch.full((b,), float(length), dtype=torch.float64, device=dev)
+        return self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)[1]
+
+    def samples_per_frame(self) -> int:
+        """Audio samples per mel frame: mel_upsample_scale * n_audio_channels (256, ``modules.py:341``)."""
+        return self._up() * self.n_audio_channels
+
+    def _audio_starts(self, audio: torch.Tensor, lens: List[int], sample_offsets, dev, what: str):
+        """-> (flat fp32 device buffer, host list of every utterance's first sample in it).  ``audio``: (B, N) padded rows
+        (utterance i = the first 256 * lens[i] samples of row i) or a flat buffer with ``sample_offsets`` (B or B + 1 host
+        ints; default: the utterances end to end, 256 * lens[i] samples each)."""
+        self._on_device(audio, dev, what, "audio")
+        spf = self.samples_per_frame()
+        if audio.dim() == 2:
+            if sample_offsets is not None or audio.shape[0] != len(lens):
+                raise ValueError(f"SqueezeWave.{what}: audio {tuple(audio.shape)} for {len(lens)} utterances (sample_offsets go with a flat buffer)")
+            starts = [i * audio.shape[1] for i in range(len(lens))]
+            ends = [(i + 1) * audio.shape[1] for i in range(len(lens))]
+        elif audio.dim() == 1:
+            if sample_offsets is None:
+                starts = [spf * m for m in segment_offsets(lens)[:-1]]
+            else:
+                starts = host_lengths(sample_offsets)[:len(lens)]
+                if len(starts) != len(lens):
+                    raise ValueError(f"SqueezeWave.{what}: {len(starts)} sample offsets for {len(lens)} utterances")
+            ends = [audio.numel()] * len(lens)
+        else:
+            raise ValueError(f"SqueezeWave.{what}: audio is (B, N) or a flat buffer (got {tuple(audio.shape)})")
+        for i, (a, e, n) in enumerate(zip(starts, ends, lens)):
+            if a + spf * n > e:
+                raise ValueError(f"SqueezeWave.{what}: utterance {i} has {n} frames = {spf * n} samples, its audio holds {max(e - a, 0)} "
+                                 f"(the audio length must be {spf} * frames)")
+        flat = audio.to(torch.float32).contiguous().view(-1)
+        return flat, starts
+
+    def _pack_audio(self, flat: torch.Tensor, starts: List[int], moff: torch.Tensor, nseg: int, capacity_frames: int,
+                    start_table: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """flat fp32 audio + per-utterance first samples -> packed rows (up * capacity_frames, n_audio_channels), one launch."""
+        up, c = self._up(), self.n_audio_channels
+        host = torch.tensor(starts, dtype=torch.int64).pin_memory()
+        start_table = host.to(flat.device, non_blocking=True) if start_table is None else start_table.copy_(host, non_blocking=True)
+        if out is None:
+            out = torch.empty(up * capacity_frames, c, dtype=torch.float32, device=flat.device)
+        _lib.call("rtts_sw_pack_audio", flat.data_ptr(), max(flat.numel(), 1), start_table.data_ptr(), moff.data_ptr(), nseg, up, c,
+                  up * capacity_frames, out.data_ptr(), _s())
+        return out
+
+    def _ragged_lengths(self, frames, what: str):
+        lens = host_lengths(frames)
+        if not 1 <= len(lens) <= SW_MAX_SEGMENTS:
+            raise ValueError(f"SqueezeWave.{what}: a ragged vocoder call takes 1..{SW_MAX_SEGMENTS} utterances (got {len(lens)})")
+        return lens, segment_offsets(lens)
+
+    @torch.no_grad()
+    def nll_ragged(self, mel: torch.Tensor, frames, audio: torch.Tensor, sample_offsets=None, sigma: float = 1.0):
+        """B utterances of different lengths, each scored as ``nll(mel[i:i+1, :, :frames[i]], its 256 * frames[i] samples)``
+        would score it: mel (B, n_mel, Lmax) (any strides), ``frames`` (B,) host ints, ``audio`` (B, N) padded rows or a flat
+        buffer (``sample_offsets``: every utterance's first sample, host ints; default end to end) -> (per-utterance NLL
+        (B,) fp32, the loss of the whole batch 0-dim fp32: all sums over all utterances divided by the total element count,
+        ``SqueezeWaveLoss`` of the concatenation).  The utterances are laid end to end as rows, as in ``infer_ragged``.  An
+        utterance of zero frames scores NaN and adds nothing to the batch loss."""
+        dev = self._likelihood_device("nll_ragged")
+        folded, logdet = self._fold(), self._logdets()
+        lens, moff_h = self._ragged_lengths(frames, "nll_ragged")
+        self._on_device(mel, dev, "nll_ragged", "mel")
+        flat, starts = self._audio_starts(audio, lens, sample_offsets, dev, "nll_ragged")
+        total = moff_h[-1]
+        if total == 0:
+            nan = torch.full((len(lens),), float("nan"), device=dev)
+            return nan, nan[0].clone()
+        up = self._up()
+        moff = self._offsets_to(moff_h, dev)
+        mel_rows = self._pack_mel(mel, lens, moff, total)
+        audio_rows = self._pack_audio(flat, starts, moff, len(lens), total)
+        seg = _Segments.packed(moff, total, up)
+        z, ls_row, _ = self._flows_fwd(folded, mel_rows, seg, audio_rows, False)
+        nrows = (moff[1:] - moff[:-1]).to(torch.float64) * up
+        return self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)
+
+    def capture_nll_ragged(self, batch: int, capacity_frames: int, sigma: float = 1.0):
+        """-> ``run(mel, frames, audio, sample_offsets=None) -> (per-utterance NLL (B,), batch NLL)``: ``nll_ragged`` for
+        ``batch`` utterances of at most ``capacity_frames`` mel frames in total, as ONE hipGraph that any set of lengths
+        replays (the contract and cache of ``capture_ragged``).  Per call the offset tables are copied in and the mel and the
+        audio packed into the graph's input rows (two kernels, outside the graph).  A total above the capacity raises before
+        anything is launched.  The returned tensors are the graph's output buffers: copy them before the next call."""
+        dev = self._likelihood_device("capture_nll_ragged")
+        batch, cap = int(batch), int(capacity_frames)
+        if not 1 <= batch <= SW_MAX_SEGMENTS or cap < 1:
+            raise ValueError(f"capture_nll_ragged: 1..{SW_MAX_SEGMENTS} utterances and a positive capacity (got {batch}, {cap})")
+        cache = self.__dict__.setdefault("_nll_graphs", {})
+        key = (batch, cap, float(sigma))
+        if key in cache and cache[key].folded is self._fold():
+            return cache[key]
+        folded, logdet = self._fold(), self._logdets()
+        up, c = self._up(), self.n_audio_channels
+        mel_rows = torch.zeros(cap, self._n_mel(), device=dev)
+        audio_rows = torch.zeros(up * cap, c, device=dev)
+        moff = torch.zeros(batch + 1, dtype=torch.int32, device=dev)        # every row padding until a call sets the table
+        start_table = torch.zeros(batch, dtype=torch.int64, device=dev)
+        seg = _Segments.packed(moff, cap, up)
+
+        def score():
+            z, ls_row, _ = self._flows_fwd(folded, mel_rows, seg, audio_rows, False)
+            nrows = (moff[1:] - moff[:-1]).to(torch.float64) * up
+            return self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                          # warm-up: allocator, lazy attributes
+            score()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with capturing(graph):
+            per, total_loss = score()
+
+        def run(mel: torch.Tensor, frames, audio: torch.Tensor, sample_offsets=None):
+            if self.training:
+                raise _lib.RttsError("capture_nll_ragged: the graph was captured in eval mode (running-statistics BatchNorm); call .eval()")
+            lens, moff_h = self._ragged_lengths(frames, "capture_nll_ragged")
+            if len(lens) != batch or moff_h[-1] > cap:
+                raise ValueError(f"capture_nll_ragged graph for {batch} utterances of {cap} frames in total: got {len(lens)} utterances, "
+                                 f"{moff_h[-1]} frames")
+            self._on_device(mel, dev, "capture_nll_ragged", "mel")
+            flat, starts = self._audio_starts(audio, lens, sample_offsets, dev, "capture_nll_ragged")
+            self._offsets_to(moff_h, dev, out=moff)
+            self._pack_mel(mel, lens, moff, cap, out=mel_rows)
+            self._pack_audio(flat, starts, moff, batch, cap, start_table=start_table, out=audio_rows)
+            graph.replay()
+            return per, total_loss
+        run.batch, run.capacity, run.folded, run.graph = batch, cap, folded, graph
+        cache[key] = run
+        return run

@@ -111,3 +111,27 @@ def mel_round_trip_error(vocoder_waves: Sequence[torch.Tensor], spectrogram: tor
                              f"{spectrogram.shape[2]}")
         errs.append((packed[:, foff[i]:foff[i] + n] - spectrogram[i, :, :n].to(packed.device, torch.float32)).abs().mean())
     return torch.stack(errs)
+
+
+@torch.no_grad()
+def score_audio(vocoder, creator, audio, lengths=None, sigma: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Waveforms -> how likely each is under the vocoder: per utterance, the negative log-likelihood per sample of its first
+    256 * frames_i samples given its own log-mel, frames_i = n_samples_i // 256 -> (per-utterance NLL (B,) f32, the loss of
+    the whole batch, 0-dim f32), both on the device (``SqueezeWave.nll_ragged``; the number of the reference's
+    ``validation_step``, ``training/wrappers.py:361-368``, per recording).
+
+    ``audio``: a list of 1-D device tensors, or a padded (B, N) device tensor with ``lengths`` (host ints), as
+    ``creator.forward`` takes them; ``creator``: a ``dataset.audio`` spectrogram module of the format the vocoder was trained
+    on.  One ragged mel launch over all the waveforms (``creator.forward_packed``: n // 256 + 1 frames per utterance, cut to
+    n // 256) and one ragged vocoder call; the host reads only the lengths.  An utterance needs more than n_fft / 2 samples."""
+    flat, lens = creator._gather(audio, lengths)
+    spf = vocoder.samples_per_frame()
+    if creator.hop_length != spf or creator.n_mels != vocoder._n_mel():
+        raise ValueError(f"score_audio: the spectrogram format (hop {creator.hop_length}, {creator.n_mels} mels) is not the vocoder's "
+                         f"({spf} samples per frame, {vocoder._n_mel()} mels)")
+    packed, foff = creator.forward_packed(flat, lens)
+    frames = [n // spf for n in lens]
+    mel = torch.zeros(len(lens), creator.n_mels, max(max(frames), 1), dtype=torch.float32, device=packed.device)
+    for i, t in enumerate(frames):
+        mel[i, :, :t] = packed[:, foff[i]:foff[i] + t]
+    return vocoder.nll_ragged(mel, frames, flat, sample_offsets=segment_offsets(lens)[:-1], sigma=sigma)
