@@ -221,7 +221,13 @@ int rtts_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
  *   T_k > 256 (or 384, 640, ...): the forward walks the keys in rtts_xattn_key_chunks(T_k) chunks with a running maximum and
  *   normaliser; the backward gives every chunk its own workgroups (P = exp(s - lse) needs only the forward's lse), which
  *   write their shares of dQ to dq_chunks (chunks, B*Tq, H*dh) bf16 -- summed into dq (ld_dq == H*dh) by the same call;
- *   one chunk: dq_chunks may be NULL */
+ *   one chunk: dq_chunks may be NULL
+ *   A sample WITHOUT ANY valid key (kvalid all 0): its normaliser is 0, so rtts_xattn_fwd writes o = NaN (0 * inf) and
+ *   lse = -inf for its rows, as nn.MultiheadAttention does; rtts_lsh_bwd_delta then gives delta = NaN and rtts_xattn_bwd
+ *   dq = NaN and dk = NaN (dS = P * (dP - delta) with P = 0, delta = NaN), while dv is exactly 0 (P is taken as 0 where
+ *   kvalid is 0; nn.MultiheadAttention's dv is NaN there).  This is NaN in data, never a fault, and the other samples of the
+ *   batch are bit-identical to a call in which that sample has valid keys (tests/test_xattn_hip.py).  A padded key of a
+ *   sample that has valid keys gets dk = dv = 0 exactly. */
 int rtts_xattn_key_chunks(int Tk);
 int rtts_xattn_fwd(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
                    int B, int H, int Tq, int Tk, int dh, void* o, int64_t ld_o, float* lse,
