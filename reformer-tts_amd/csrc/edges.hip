@@ -929,9 +929,12 @@ extern "C" int rtts_bn_act_bwd(const float* y, const void* dz, int dz_halo, cons
     RTTS_ENTER(stream);
     RTTS_REQUIRE(y && dz && mean && rstd && gamma && beta && dy && dgamma && dbeta && partial_ws && B > 0 && L > 0 && halo >= 0 && C % 4 == 0 &&
                      (act == 1 || act == 2), "rtts_bn_act_bwd: bad arguments");
+    RTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "rtts_bn_act_bwd: drop_p must be in [0, 1)");
     const EdHalo g = ed_halo(B, L, halo);
-    RTTS_REQUIRE(dy_lead >= 0 && dy_rows >= dy_lead + (int64_t)B * g.P && (halo > 0 || dz_halo == 0 || true),
+    RTTS_REQUIRE(dy_lead >= 0 && dy_rows >= dy_lead + (int64_t)B * g.P,
                  "rtts_bn_act_bwd: dy needs room for B*(L+2*halo) rows behind its lead-in");
+    const size_t n4 = (size_t)dy_rows * C / 4;
+    RTTS_REQUIRE(n4 < (1ull << 30), "rtts_bn_act_bwd: more than 2^32 elements");
     const dim3 grid = ed_col_grid(B * g.P, C);
     const uint32_t th = ed_thresh(drop_p);
     const float ds = 1.f / (1.f - drop_p);
@@ -941,8 +944,6 @@ extern "C" int rtts_bn_act_bwd(const float* y, const void* dz, int dz_halo, cons
                        seed, seed_dev, th, ds, g, dzh, C, partial_ws);
     hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3((C + 63) / 64), dim3(64 * ED_FIN_WAVES), 0, (hipStream_t)stream, partial_ws,
                        (int)grid.x, C, sums, dgamma, dbeta);
-    const size_t n4 = (size_t)dy_rows * C / 4;
-    RTTS_REQUIRE(n4 < (1ull << 30), "rtts_bn_act_bwd: more than 2^32 elements");
     hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(ed_grid(n4)), dim3(ED_THREADS), 0, (hipStream_t)stream, y, (const bf16_t*)dz, mean, rstd,
                        gamma, beta, act, seed, seed_dev, th, ds, sums, 1.f / (float)((size_t)B * L), g, dzh, dy_lead, n4, C, ed_cshift(C), (bf16_t*)dy);
     RTTS_LAUNCH_CHECK("rtts_bn_act_bwd");
@@ -978,6 +979,7 @@ extern "C" int rtts_bn_act_bwd_sums(const float* y, const void* dz, int dz_halo,
     RTTS_ENTER(stream);
     RTTS_REQUIRE(y && dz && mean && rstd && gamma && beta && sums && dgamma && dbeta && partial_ws && B > 0 && L > 0 && halo >= 0 && C % 4 == 0 &&
                      (act == 1 || act == 2), "rtts_bn_act_bwd_sums: bad arguments");
+    RTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "rtts_bn_act_bwd_sums: drop_p must be in [0, 1)");
     const EdHalo g = ed_halo(B, L, halo);
     const dim3 grid = ed_col_grid(B * g.P, C);
     const int dzh = (halo > 0 && dz_halo) ? 1 : 0;
@@ -995,6 +997,7 @@ extern "C" int rtts_bn_act_bwd_apply(const float* y, const void* dz, int dz_halo
     RTTS_ENTER(stream);
     RTTS_REQUIRE(y && dz && mean && rstd && gamma && beta && sums && dy && count >= 0 && B > 0 && L > 0 && halo >= 0 && C % 4 == 0 &&
                      (act == 1 || act == 2), "rtts_bn_act_bwd_apply: bad arguments");
+    RTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "rtts_bn_act_bwd_apply: drop_p must be in [0, 1)");
     const EdHalo g = ed_halo(B, L, halo);
     RTTS_REQUIRE(dy_lead >= 0 && dy_rows >= dy_lead + (int64_t)B * g.P, "rtts_bn_act_bwd_apply: dy needs room for B*(L+2*halo) rows behind its lead-in");
     const int dzh = (halo > 0 && dz_halo) ? 1 : 0;
@@ -1117,6 +1120,8 @@ extern "C" int rtts_pe_dalpha(const float* dy, const float* table, float drop_p,
                               int d, float* dalpha, float* partial_ws, void* stream) {
     RTTS_ENTER(stream);
     RTTS_REQUIRE(dy && table && dalpha && partial_ws && T > 0 && M > 0 && d % 4 == 0 && M % T == 0, "rtts_pe_dalpha: bad arguments");
+    RTTS_REQUIRE(d > 0, "rtts_pe_dalpha: d must be positive");
+    RTTS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "rtts_pe_dalpha: drop_p must be in [0, 1)");
     const size_t n4 = (size_t)M * d / 4;
     const int blocks = 512;
     hipLaunchKernelGGL(pe_dalpha_partial_kernel, dim3(blocks), dim3(ED_THREADS), 0, (hipStream_t)stream, dy, table, seed, seed_dev, ed_thresh(drop_p),
