@@ -558,6 +558,38 @@ int rtts_sw_nll_reduce(const float* z, int64_t ld_z, int C, const float* ls_row,
                        int64_t rows, double* out, void* stream);
 int rtts_sw_pack_audio(const float* src, int64_t n_src, const int64_t* start, const int32_t* moff, int nseg, int upsample, int C,
                        int64_t rows, float* dst, void* stream);
+/* Training (SqueezeWave.nll_backward): the backward of the analysis direction with the BatchNorms on batch statistics
+ * (squeeze_wave/modules.py:100-117 DepthwiseSeparableConv1d in .train(), :203-235 WN.forward, :294-332 SqueezeWave.forward,
+ * loss.py:14-31; the optimiser step of training/wrappers.py:327-418 differentiates exactly this).  The 1x1 convolutions'
+ * gradients are rtts_gemm_nt (w_is_kn = 1) and rtts_gemm_tn; these are the pieces between them.  All are deterministic (no
+ * atomics, partial sums added in a fixed order, fp32 accumulation) and validate their arguments before any launch.
+ *   rtts_sw_gate_bwd      backward of rtts_sw_gate (:10-24, :216-225): dacts bf16 (B*L, C) -> dpw bf16 (B*L, 2C) = [d_t | d_s],
+ *                         d_t = da g (1 - t^2), d_s = da t g (1 - g) with t, g recomputed from pw and cond as the forward did;
+ *                         dcond[r][cond_offset : +2C] (bf16, B*Lm rows of stride ld_dcond) = the fp32 sum of [d_t | d_s] over the
+ *                         `upsample` audio rows of conditioning row r, rounded once (the backward of nn.Upsample(nearest))
+ *   rtts_sw_dwbn_bwd_sums / _apply   backward of BatchNorm1d (batch statistics over the B*L rows) followed by the depthwise k3
+ *                         convolution (:100-117, zero padding of bn(h) per utterance): h fp32 (B*L, C) the block's input, dy bf16
+ *                         (B*L, C) the gradient of the convolution's output, mean / rstd the batch statistics, gamma / beta the
+ *                         BatchNorm's affine, w (C, 3) the depthwise taps; C % 8 == 0, h / dy / dh 16-byte aligned (8 channels per access).  _sums: sums (6, C) fp32 = {d w_0, d w_1, d w_2, d bias,
+ *                         d gamma, d beta} (stored, not accumulated) through partial_ws of rtts_sw_dwbn_bwd_partial_floats(B*L, C)
+ *                         floats.  _apply: dh (B*L, C) fp32 += gamma rstd (du - sums[5] / m - xhat sums[4] / m), m = B*L
+ *   rtts_sw_boundary_bwd  backward of rtts_sw_coupling_fwd1x1 (same x, wn_out, w, n_in, n_early, z, z_col): dout (rows, n) the
+ *                         gradient of its `out`; the early columns' gradient is z * z_scale (the loss's sum z^2 / (2 sigma^2 N)).
+ *                         dw (n, n) fp32 = dout^T c[:, n_early:] (stored; through partial_ws of rtts_sw_boundary_bwd_blocks(rows)
+ *                         * n * n floats); with wn_out: dx (rows, n_in) = [dc_0 | dc_1 exp(log_s)] and dwn (rows, >= n_in) =
+ *                         [dc_1 x_1 exp(log_s) - inv_n | dc_1], dc = [z-seed | dout w] (inv_n = 1 / N: the loss's -sum log_s / N).
+ *                         wn_out NULL: the first flow (only dw).  w NULL: the tail (n_early == n_in, dc is the z-seed). */
+int rtts_sw_gate_bwd(const void* pw, const void* cond, int64_t ld_cond, int cond_offset, int upsample, int B, int L, int Lm, int C,
+                     const void* dacts, void* dpw, void* dcond, int64_t ld_dcond, void* stream);
+int rtts_sw_dwbn_bwd_partial_floats(int64_t rows, int C);
+int rtts_sw_dwbn_bwd_sums(const float* h, const void* dy, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                          const float* w, int B, int L, int C, float* sums, float* partial_ws, void* stream);
+int rtts_sw_dwbn_bwd_apply(const float* h, const void* dy, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                           const float* w, const float* sums, int B, int L, int C, float* dh, void* stream);
+int rtts_sw_boundary_bwd_blocks(int64_t rows);
+int rtts_sw_boundary_bwd(const float* x, int64_t ld_x, const float* wn_out, int64_t ld_wn, const float* w, int n_in, int n_early,
+                         int64_t rows, const float* dout, int64_t ld_dout, const float* z, int64_t ld_z, int z_col, float z_scale,
+                         float inv_n, float* dx, int64_t ld_dx, float* dwn, int64_t ld_dwn, float* dw, float* partial_ws, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

@@ -136,6 +136,13 @@ SIGNATURES = {
     "rtts_sw_coupling_fwd1x1": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp],
     "rtts_sw_nll_reduce": [_vp, _i64, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp],
     "rtts_sw_pack_audio": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp],
+    "rtts_sw_gate_bwd": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
+    "rtts_sw_dwbn_bwd_partial_floats": [_i64, _i32],
+    "rtts_sw_dwbn_bwd_sums": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "rtts_sw_dwbn_bwd_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "rtts_sw_boundary_bwd_blocks": [_i64],
+    "rtts_sw_boundary_bwd": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _f32, _vp, _i64, _vp, _i64, _vp, _vp,
+                             _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],

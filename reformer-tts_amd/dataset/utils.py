@@ -81,3 +81,25 @@ class BatchPrefetcher:
             batch = self.into
         self._stage()
         return batch
+
+
+def vocoder_segment(audio: torch.Tensor, spectrogram: torch.Tensor, audio_segment_length: int, mel_hop_length: int,
+                    random_hop: Optional[int] = None):
+    """The fixed-length training segment of ``SpectrogramToSpeechDataset.__getitem__`` (reference
+    ``dataset/interface.py:64-97``) on host tensors: audio (N,), spectrogram (n_mels, T) -> (audio (audio_segment_length,),
+    spectrogram (n_mels, audio_segment_length // mel_hop_length)).  An utterance of at least ``audio_segment_length`` samples is
+    cropped at hop ``random_hop`` (drawn with ``random.randint(0, (N - audio_segment_length) // mel_hop_length)``, as the
+    reference draws it, when not given); a shorter one is zero-padded at its end, and so is its spectrogram."""
+    audio_size = audio.size(0)
+    n_hops = audio_segment_length // mel_hop_length
+    if audio_size >= audio_segment_length:
+        max_hop = (audio_size - audio_segment_length) // mel_hop_length
+        if random_hop is None:
+            import random
+            random_hop = random.randint(0, max_hop)
+        if not 0 <= random_hop <= max_hop:
+            raise ValueError(f"vocoder_segment: random_hop {random_hop} outside [0, {max_hop}]")
+        start = random_hop * mel_hop_length
+        return audio[start:start + n_hops * mel_hop_length], spectrogram[:, random_hop:random_hop + n_hops]
+    audio = torch.nn.functional.pad(audio, [0, audio_segment_length - audio_size], "constant")
+    return audio, torch.nn.functional.pad(spectrogram, [0, n_hops - spectrogram.shape[-1]], "constant")

@@ -20,8 +20,12 @@ modules here only HOLD parameters.  ``infer`` (:334-376) runs through an explici
 The analysis direction, ``forward`` (:294-332) and the likelihood ``nll`` / ``nll_ragged`` / ``capture_nll_ragged``
 (``squeeze_wave/loss.py:14-31``), runs the same folded WN blocks in eval mode (running-statistics BatchNorm): per flow one
 ``rtts_sw_coupling_fwd1x1`` launch (the previous flow's coupling, this flow's early output and 1x1 convolution) in front of
-``_FoldedWN.forward``, and one ``rtts_sw_nll_reduce`` launch for the per-utterance sums.  Training-mode BatchNorm and the
-backward are not on the HIP path.
+``_FoldedWN.forward``, and one ``rtts_sw_nll_reduce`` launch for the per-utterance sums.
+
+Training (``LitSqueezeWave``, ``training/wrappers.py:327-418``): ``nll_backward`` runs the same flow with batch-statistics
+BatchNorm (``_TrainWN``), keeps every layer's activations, and walks it backwards -- ``rtts_sw_boundary_bwd`` per flow boundary,
+``rtts_sw_gate_bwd`` and ``rtts_sw_dwbn_bwd_sums`` / ``_apply`` per layer, ``rtts_gemm_nt`` (input gradients) and
+``rtts_gemm_tn`` (weight gradients) for every 1x1 convolution -- adding the loss's gradient into every parameter's ``.grad``.
 
 There is no CPU fallback: ``infer`` and ``forward`` raise off the GPU."""
 from __future__ import annotations
@@ -175,7 +179,7 @@ class _FoldedWN:
     are never read back).  ``in_tree`` is False for toy widths the MFMA kernel does not tile (n_channels % 64, n_half % 8 or
     n_mel % 8 != 0): those run the same arithmetic through the library GEMM and say so once."""
 
-    def __init__(self, wn: WN):
+    def __init__(self, wn: WN, fold_bn: bool = True):
         bf = torch.bfloat16
         self.c, self.nl, self.up = wn.n_channels, wn.n_layers, wn.upsample_scale
         if wn.kernel_size != 3:
@@ -203,6 +207,12 @@ class _FoldedWN:
         self.dw_w, self.dw_b, self.dw_edge, self.w_pw, self.b_pw, self.w_rs, self.b_rs = [], [], [], [], [], [], []
         for i in range(wn.n_layers):
             bn, dw, pw = wn.in_layers[i].layer
+            self.w_pw.append(pw.weight.detach().float().squeeze(-1).to(bf).contiguous())
+            self.b_pw.append(pw.bias.detach().float().contiguous())
+            self.w_rs.append(_normed(wn.res_skip_layers[i]).to(bf).contiguous())
+            self.b_rs.append(wn.res_skip_layers[i].bias.detach().float().contiguous())
+            if not fold_bn:          # a training step folds its own batch statistics (_TrainWN): no depthwise taps here
+                continue
             a = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
             cst = bn.bias.detach().float() - bn.running_mean.float() * a
             w = dw.weight.detach().float().squeeze(1)                          # (C, 3)
@@ -210,10 +220,6 @@ class _FoldedWN:
             self.dw_b.append((dw.bias.detach().float() + w.sum(1) * cst).contiguous())
             # at l = 0 the tap k = 0 sees the zero padding of bn(x), not c; at l = L-1 the tap k = 2 likewise
             self.dw_edge.append(((w[:, 0] * cst).contiguous(), (w[:, 2] * cst).contiguous()))
-            self.w_pw.append(pw.weight.detach().float().squeeze(-1).to(bf).contiguous())
-            self.b_pw.append(pw.bias.detach().float().contiguous())
-            self.w_rs.append(_normed(wn.res_skip_layers[i]).to(bf).contiguous())
-            self.b_rs.append(wn.res_skip_layers[i].bias.detach().float().contiguous())
 
     def condition(self, mel: torch.Tensor, seg: _Segments) -> torch.Tensor:
         """mel fp32 (B*Lm, n_mel) rows -> (rows, 2c * n_layers) bf16: the conditioning of all layers in one GEMM."""
@@ -270,6 +276,217 @@ class _FoldedWN:
         return mm(hb, self.w_end, self.b_end, True)
 
 
+def _zero_tail(t: torch.Tensor, m: int) -> torch.Tensor:
+    """Rows from ``m`` on are padding to the GEMMs' 128-row granule: zeroed, so that a reduction over all rows (a weight
+    gradient, a bias sum) sees nothing there, whatever the allocator handed out."""
+    if t.shape[0] > m:
+        t[m:].zero_()
+    return t
+
+
+def _k128(x: torch.Tensor) -> torch.Tensor:
+    """bf16 rows with the width rounded up to 128 (zero columns): the K granule of ``rtts_gemm_tn``."""
+    if x.shape[1] % 128 == 0:
+        return x
+    out = torch.zeros(x.shape[0], _pad(x.shape[1], 128), dtype=x.dtype, device=x.device)
+    out[:, :x.shape[1]] = x
+    return out
+
+
+TRAIN_WIDTHS = (128, 256, 512, 1024)     # n_channels the in-tree backward tiles: rtts_gemm_tn's 128 granule, the column-sum kernels' widths
+
+
+class _TrainWN:
+    """One WN block of a training step (``WN.forward``, reference ``modules.py:203-235``, in ``.train()``): the sequence of
+    ``_FoldedWN.forward`` with two differences.  In front of each depthwise convolution the statistics of the fp32 residual
+    stream over the B * L real rows are taken (``rtts_bn_moments`` / ``rtts_bn_from_moments``, which also maintain the running
+    statistics) and folded into the depthwise taps and edge corrections on the device (C-sized torch ops, no host read); and
+    every layer's input, depthwise output, pointwise output, gate output and statistics are kept for ``backward``.
+
+    Padding rows (the activation buffers are rounded up to 128 rows) are zeroed wherever a buffer is written by a kernel that
+    stops at the real rows: the weight-gradient GEMMs and column sums run over all rows.  Toy widths (``in_tree`` False) run
+    the same arithmetic through ``torch.mm``, as the forward does."""
+
+    def __init__(self, wn: WN, f: _FoldedWN):
+        self.wn, self.f = wn, f                 # widths: SqueezeWave._train_widths has refused what the backward does not tile
+
+    # ---- the GEMM forms of the backward: bf16 operands, fp32 accumulation
+    def _mm(self, x, w, bias=None, f32=False):
+        if self.f.in_tree:
+            from ..engine import gemm
+            return gemm(x, w, bias=bias, out_f32=f32)
+        y = torch.mm(x, w.t(), out_dtype=torch.float32)
+        y = y if bias is None else y + bias
+        return y if f32 else y.to(torch.bfloat16)
+
+    def _dgrad(self, dy, w, f32=False):
+        """dx = dy @ w, w (N, K) as the forward holds it."""
+        if self.f.in_tree:
+            from ..engine import gemm
+            return gemm(dy, w, kn=True, out_f32=f32)
+        dx = torch.mm(dy, w, out_dtype=torch.float32)
+        return dx if f32 else dx.to(torch.bfloat16)
+
+    def _wgrad(self, dy, x):
+        """dW (N, K) fp32 = dy^T @ x over ALL rows (padding rows of dy are zero, of x finite)."""
+        if not self.f.in_tree:
+            return torch.mm(dy.t(), x, out_dtype=torch.float32)
+        from ..engine import _slab_ws
+        n, k = dy.shape[1], x.shape[1]
+        out = torch.empty(n, k, dtype=torch.float32, device=dy.device)
+        ws = _slab_ws(dy.device)
+        _lib.call("rtts_gemm_tn", dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dy.shape[0], n, k, out.data_ptr(), k, 0, ws.data_ptr(),
+                  ws.numel(), _s())
+        return out
+
+    def _cast_colsum(self, d):
+        """fp32 (M, d) -> (its bf16 copy, its column sums fp32 (d,))."""
+        if not self.f.in_tree:
+            return d.to(torch.bfloat16), d.sum(0)
+        from ..engine import _WS
+        m, w = d.shape
+        db = torch.empty(m, w, dtype=torch.bfloat16, device=d.device)
+        out = torch.zeros(w, dtype=torch.float32, device=d.device)
+        _lib.call("rtts_cast_colsum", d.data_ptr(), db.data_ptr(), out.data_ptr(), _WS.partial(d.device, w).data_ptr(), m, w, 0.0, 0, None, None, _s())
+        return db, out
+
+    def _colsum(self, d, col0: int, width: int, out: torch.Tensor):
+        """out (width,) fp32 += column sums of columns [col0, col0 + width) of the bf16 rows ``d``."""
+        if not self.f.in_tree:
+            out += d[:, col0:col0 + width].float().sum(0)
+            return
+        from ..engine import _WS
+        view = d[:, col0:col0 + width]
+        _lib.call("rtts_colsum_bf16", view.data_ptr(), None, d.stride(0), out.data_ptr(), _WS.partial(d.device, width).data_ptr(), d.shape[0], width,
+                  0, 1.0, None, _s())
+
+    def forward(self, audio: torch.Tensor, xmel: torch.Tensor, seg: _Segments) -> torch.Tensor:
+        """audio fp32 (seg.rows, n_rem) rows, xmel the bf16 mel rows (``SqueezeWave._train_mel``) -> fp32 (rows >= seg.rows,
+        n_end) = [log_s | b | zero columns]; everything ``backward`` needs stays on ``self``."""
+        from ..edges import _ws
+        f, wn = self.f, self.wn
+        dev, c, bf = audio.device, f.c, torch.bfloat16
+        b, length, mel_len, m = seg.b, seg.length, seg.mel_len, seg.rows
+        self.xmel = xmel
+        if f.in_tree:
+            self.cond = self._mm(xmel[:, :f.w_cond.shape[1]], f.w_cond, f.b_cond)
+            mp, kp = _pad(m, 128), f.w_start.shape[1]
+            a0 = torch.empty(mp, kp, dtype=bf, device=dev)
+            _lib.call("rtts_to_halo", audio.data_ptr(), audio.stride(0), 0, f.n_half, 1, b, length, 0, kp, a0.data_ptr(), 0, mp, _s())
+            h = self._mm(a0, f.w_start, f.b_start, True)
+            self.a0 = _k128(a0)
+        else:
+            _lib.note_general_path("SqueezeWave WN block", f"widths (n_channels {c}, n_half {f.n_half}, n_mel {f.n_mel}) the MFMA GEMM "
+                                   "does not tile (n_channels % 64, n_half % 8, n_mel % 8): library GEMM")
+            self.cond = torch.addmm(f.b_cond.to(bf), xmel, f.w_cond.t())
+            mp = m
+            self.a0 = audio[:, :f.n_half].contiguous()
+            h = torch.addmm(f.b_start, self.a0, f.w_start.float().t())
+        self.mp, self.layers = mp, []
+        rows = lambda width, dtype: _zero_tail(torch.empty(mp, width, dtype=dtype, device=dev), m)     # noqa: E731
+        for i in range(f.nl):
+            bn, dwc, _ = wn.in_layers[i].layer
+            mom = torch.empty(2 * c + 1, dtype=torch.float32, device=dev)
+            mean, rstd = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
+            _lib.call("rtts_bn_moments", h.data_ptr(), b, length, 0, c, mom.data_ptr(), _ws(dev, c).data_ptr(), _s())
+            _lib.call("rtts_bn_from_moments", mom.data_ptr(), m, c, mean.data_ptr(), rstd.data_ptr(), bn.running_mean.data_ptr(),
+                      bn.running_var.data_ptr(), None, bn.num_batches_tracked.data_ptr(), _s())
+            # dw(bn(h)) with a = gamma * rstd, c0 = beta - mean * a folded into the taps, as _FoldedWN folds the running statistics
+            a = bn.weight.detach() * rstd
+            c0 = bn.bias.detach() - mean * a
+            w = dwc.weight.detach().squeeze(1)                                     # (C, 3)
+            taps, bias = (w * a[:, None]).contiguous(), dwc.bias.detach() + w.sum(1) * c0
+            lo, hi = (w[:, 0] * c0).contiguous(), (w[:, 2] * c0).contiguous()
+            dwo = rows(c, bf)
+            _lib.call("rtts_sw_depthwise_k3", h.data_ptr(), taps.data_ptr(), bias.data_ptr(), b, length, c, dwo.data_ptr(), lo.data_ptr(),
+                      hi.data_ptr(), _s())
+            pw = self._mm(dwo, f.w_pw[i], f.b_pw[i])                               # (mp, 2c) bf16
+            acts = rows(c, bf)
+            _lib.call("rtts_sw_gate", pw.data_ptr(), self.cond.data_ptr(), self.cond.stride(0), i * 2 * c, seg.up, b, length, mel_len, c,
+                      acts.data_ptr(), _s())
+            rs = self._mm(acts, f.w_rs[i])
+            nxt = rows(c, torch.float32)
+            _lib.call("rtts_residual_epilogue", h.data_ptr(), rs.data_ptr(), f.b_rs[i].data_ptr(), 1.0, nxt.data_ptr(), m, c, 0.0, 0, None, _s())
+            self.layers.append((h, dwo, pw, acts, mean, rstd, w.contiguous()))
+            h = nxt
+        self.hb = rows(c, bf)
+        _lib.call("rtts_cast_f32_bf16", h.data_ptr(), self.hb.data_ptr(), m * c, _s())
+        return self._mm(self.hb, f.w_end, f.b_end, True)
+
+    def new_dwn(self, seg: _Segments) -> torch.Tensor:
+        """The buffer ``rtts_sw_boundary_bwd`` writes d [log_s | b] into: 128 columns wide and zero outside the real rows and
+        columns on the in-tree path (N of the end_conv weight-gradient GEMM)."""
+        dev = self.hb.device
+        if self.f.in_tree:
+            return torch.zeros(self.mp, 128, dtype=torch.float32, device=dev)
+        return torch.empty(seg.rows, 2 * self.f.n_half, dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _weight_norm_grads(conv, dw: torch.Tensor, grads: list):
+        """dw (Cout, Cin) fp32 = the gradient of the effective weight w = g * v / ||v|| -> the gradients of g and v."""
+        dw = dw.unsqueeze(-1)
+        if not hasattr(conv, "weight_g"):
+            grads.append((conv.weight, dw))
+            return
+        v, g = conv.weight_v.detach(), conv.weight_g.detach()
+        nrm = v.flatten(1).norm(dim=1).view(-1, 1, 1)
+        vh = v / nrm
+        dg = (dw * vh).flatten(1).sum(1).view(-1, 1, 1)
+        grads.append((conv.weight_g, dg))
+        grads.append((conv.weight_v, (g / nrm) * (dw - dg * vh)))
+
+    def backward(self, dwn: torch.Tensor, seg: _Segments, grads: list) -> torch.Tensor:
+        """dwn = d loss / d [log_s | b] (``new_dwn``) -> d loss / d (the conditioning half of the block's input) fp32 (seg.rows,
+        n_half); appends (parameter, gradient) for every parameter of the block to ``grads``."""
+        f, wn = self.f, self.wn
+        dev, c, nh, bf = dwn.device, f.c, f.n_half, torch.bfloat16
+        b, length, mel_len, m, mp = seg.b, seg.length, seg.mel_len, seg.rows, self.mp
+        dwn_b, db_end = self._cast_colsum(dwn)
+        dw_end = self._wgrad(dwn_b, self.hb)
+        grads.append((wn.end_conv.weight, dw_end[:2 * nh].unsqueeze(-1)))
+        grads.append((wn.end_conv.bias, db_end[:2 * nh]))
+        dh = self._dgrad(dwn_b[:, :f.w_end.shape[0]], f.w_end, True)              # (mp, c) fp32, zero in the padding rows
+        dcond = _zero_tail(torch.empty(self.cond.shape, dtype=bf, device=dev), b * mel_len)
+        db_cond = torch.zeros(self.cond.shape[1], dtype=torch.float32, device=dev)
+        n_part = _lib.load().rtts_sw_dwbn_bwd_partial_floats(m, c)
+        part = torch.empty(n_part, dtype=torch.float32, device=dev)
+        for i in reversed(range(f.nl)):
+            h_in, dwo, pw, acts, mean, rstd, w = self.layers[i]
+            bn, dwc, pwc = wn.in_layers[i].layer
+            drs, db_rs = self._cast_colsum(dh)
+            self._weight_norm_grads(wn.res_skip_layers[i], self._wgrad(drs, acts), grads)
+            grads.append((wn.res_skip_layers[i].bias, db_rs))
+            dacts = self._dgrad(drs, f.w_rs[i])
+            dpw = _zero_tail(torch.empty(mp, 2 * c, dtype=bf, device=dev), m)
+            _lib.call("rtts_sw_gate_bwd", pw.data_ptr(), self.cond.data_ptr(), self.cond.stride(0), i * 2 * c, seg.up, b, length, mel_len, c,
+                      dacts.data_ptr(), dpw.data_ptr(), dcond.data_ptr(), dcond.stride(0), _s())
+            self._colsum(dcond, i * 2 * c, 2 * c, db_cond[i * 2 * c:(i + 1) * 2 * c])
+            db_pw = torch.zeros(2 * c, dtype=torch.float32, device=dev)
+            self._colsum(dpw, 0, 2 * c, db_pw)
+            grads.append((pwc.weight, self._wgrad(dpw, dwo).unsqueeze(-1)))
+            grads.append((pwc.bias, db_pw))
+            ddw = self._dgrad(dpw, f.w_pw[i])                                      # (mp, c) bf16
+            sums = torch.empty(6, c, dtype=torch.float32, device=dev)
+            stats = (mean.data_ptr(), rstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), w.data_ptr())
+            _lib.call("rtts_sw_dwbn_bwd_sums", h_in.data_ptr(), ddw.data_ptr(), *stats, b, length, c, sums.data_ptr(), part.data_ptr(), _s())
+            _lib.call("rtts_sw_dwbn_bwd_apply", h_in.data_ptr(), ddw.data_ptr(), *stats, sums.data_ptr(), b, length, c, dh.data_ptr(), _s())
+            grads.append((dwc.weight, sums[0:3].t().unsqueeze(1)))
+            grads.append((dwc.bias, sums[3]))
+            grads.append((bn.weight, sums[4]))
+            grads.append((bn.bias, sums[5]))
+        self._weight_norm_grads(wn.cond_layer, self._wgrad(dcond, self.xmel)[:, :f.n_mel], grads)
+        grads.append((wn.cond_layer.bias, db_cond))
+        if f.in_tree:
+            dhs, db_start = self._cast_colsum(dh)
+            dw_start = self._wgrad(dhs, self.a0)[:, :nh]
+            da0 = self._dgrad(dhs, f.w_start, True)[:m, :nh]
+        else:                                                                      # the toy path keeps start_conv's input in fp32
+            db_start, dw_start, da0 = dh.sum(0), torch.mm(dh.t(), self.a0), torch.mm(dh, f.w_start.float())
+        self._weight_norm_grads(wn.start_conv, dw_start, grads)
+        grads.append((wn.start_conv.bias, db_start))
+        return da0
+
+
 class SqueezeWave(nn.Module):
     def __init__(self, n_flows: int, n_audio_channels: int, n_mel_channels: int, early_return_interval: int, early_return_size: int,
                  wn_config: WNConfig):
@@ -294,11 +511,13 @@ class SqueezeWave(nn.Module):
     def return_early(self, flow: int) -> bool:
         return flow % self.early_return_interval == 0 and flow > 0
 
-    def _fold(self):
+    def _fold(self, fold_bn: bool = True):
+        """``fold_bn=False`` (a training step): the GEMM operands only, built anew and not kept as the inference fold -- the step
+        changes the parameters and the running statistics anyway."""
         key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
-        if self._folded is None or self._folded_key != key:
+        if self._folded is None or self._folded_key != key or not fold_bn:
             with torch.no_grad():
-                self._folded = [_FoldedWN(wn) for wn in self.wn_layers]
+                self._folded = [_FoldedWN(wn, fold_bn) for wn in self.wn_layers]
                 # twelve matrices of at most 128 x 128, once per parameter version: inverted on the host in float64 (LAPACK) -- no
                 # device library (rocSOLVER / hipBLAS) call anywhere in the vocoder
                 dev = self.inv_conv_layers[0].conv.weight.device
@@ -308,7 +527,7 @@ class SqueezeWave(nn.Module):
                 # host (modules.py:63 computes it per call in fp32); (sign, log|det|) per flow, judged where it is used
                 self._wfwd = [conv.conv.weight.detach().squeeze(-1).float().contiguous() for conv in self.inv_conv_layers]
                 self._slogdet = [tuple(float(v) for v in torch.linalg.slogdet(w)) for w in w64]
-            self._folded_key = key
+            self._folded_key = key if fold_bn else None
         return self._folded
 
     def noise_shapes(self, batch: int, mel_len: int):
@@ -515,6 +734,9 @@ class SqueezeWave(nn.Module):
         """log det W of every flow (float64, cached by ``_fold``).  The reference's ``torch.logdet`` (modules.py:63) returns
         NaN for a negative determinant and -inf for a singular W; here that is an error that names the flow."""
         self._fold()
+        return self._checked_logdets()
+
+    def _checked_logdets(self) -> List[float]:
         for k, (sign, _) in enumerate(self._slogdet):
             if sign <= 0:
                 raise ValueError(f"inv_conv_layers.{k}: det W is {'zero' if sign == 0 else 'negative'}: log det W is undefined, the flow "
@@ -619,6 +841,122 @@ class SqueezeWave(nn.Module):
         z, ls_row, _ = self._flows_fwd(folded, mel_rows, seg, audio_rows, False)
         nrows = torch.full((b,), float(length), dtype=torch.float64, device=dev)
         return self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)[1]
+
+    # ------------------------------------------------------------------ training: the likelihood's gradient
+    def _train_mel(self, folded: List[_FoldedWN], mel_rows: torch.Tensor, seg: _Segments) -> torch.Tensor:
+        """The bf16 mel rows every flow's cond_layer reads (and its weight gradient reads again): zero-padded to 128 rows and
+        a width of 128 on the in-tree path."""
+        f = folded[0]
+        if not f.in_tree:
+            return mel_rows.to(torch.bfloat16)
+        mp, kp = _pad(seg.b * seg.mel_len, 128), f.w_cond.shape[1]
+        x = torch.empty(mp, kp, dtype=torch.bfloat16, device=mel_rows.device)
+        _lib.call("rtts_to_halo", mel_rows.data_ptr(), mel_rows.stride(0), 0, f.n_mel, 1, seg.b, seg.mel_len, 0, kp, x.data_ptr(), 0, mp, _s())
+        return _k128(x)
+
+    def _train_widths(self):
+        """Widths the forward runs on the MFMA GEMMs (``_FoldedWN.in_tree``) but the backward does not tile are refused by name:
+        ``rtts_gemm_tn`` needs N, K % 128 and the column-sum kernels take 128, 256, 512, 1024 or 2048 columns."""
+        n_mel = self._n_mel()
+        for wn in self.wn_layers:
+            c = wn.n_channels
+            n_half = (wn.start_conv.weight_v if hasattr(wn.start_conv, "weight_v") else wn.start_conv.weight).shape[1]
+            if c % 64 == 0 and n_half % 8 == 0 and n_mel % 8 == 0 and c not in TRAIN_WIDTHS:
+                raise _lib.RttsError(f"SqueezeWave.nll_backward: n_channels {c} is not one of {TRAIN_WIDTHS}, the widths the HIP backward "
+                                     "tiles (weight-gradient GEMM and column sums); inference and the likelihood take it")
+
+    @torch.no_grad()
+    def nll_backward(self, mel: torch.Tensor, audio: torch.Tensor, sigma: float = 1.0, _after_forward=None) -> torch.Tensor:
+        """One forward + backward of the reference's training step (``training/wrappers.py:350-359``): the loss
+        ``SqueezeWaveLoss(sigma)(self((mel, audio)))`` with the BatchNorms in training mode (``modules.py:100-117``: batch
+        statistics over the B * L rows), mel (B, n_mel, Lm) and audio (B, 256 * Lm) on the device -> the loss (0-dim fp32 on the
+        device).  d loss / d p is ADDED into ``p.grad`` of every parameter (created where it is None) and every BatchNorm's
+        ``running_mean`` / ``running_var`` / ``num_batches_tracked`` is updated as ``nn.BatchNorm1d`` updates them (momentum 0.1,
+        unbiased variance).  Uniform batches only; the model must be in ``.train()``.
+
+        Every layer's activations are kept for the backward (no recomputation through the inverse flow).  ``log det W_k`` and
+        ``W_k^-T`` come from ``_fold`` (host float64, one small device -> host copy per parameter version, i.e. per step).
+        ``n_channels`` that the MFMA forward takes but the backward does not tile (64, 192, 320, ...: anything outside
+        ``TRAIN_WIDTHS``) are refused.  ``_after_forward`` (measurement only): called once between the forward and the backward."""
+        self._train_widths()
+        dev = self._device("nll_backward")
+        if not self.training:
+            raise _lib.RttsError("SqueezeWave.nll_backward needs training mode (call .train()): it differentiates the loss with "
+                                 "batch-statistics BatchNorm; nll scores in eval mode")
+        if any(p.dtype != torch.float32 for p in self.parameters()):
+            raise _lib.RttsError("SqueezeWave.nll_backward: the parameters must be fp32 (they are the optimiser's master weights)")
+        folded = self._fold(fold_bn=False)
+        logdet = self._checked_logdets()
+        mel_rows, audio_rows, seg, _, _ = self._uniform_rows(mel, audio, dev, "nll_backward")
+        try:
+            return self._train_step(folded, logdet, mel_rows, audio_rows, seg, float(sigma), _after_forward)
+        finally:
+            self._folded, self._folded_key = None, None      # not an inference fold, and the running statistics changed in place
+
+    def _train_step(self, folded, logdet, mel_rows, audio_rows, seg: _Segments, sigma: float, after_forward=None) -> torch.Tensor:
+        rows, dev, c = seg.rows, audio_rows.device, self.n_audio_channels
+        f32 = torch.float32
+        blocks = [_TrainWN(wn, f) for wn, f in zip(self.wn_layers, folded)]
+        xmel = self._train_mel(folded, mel_rows, seg)
+        z = torch.empty(rows, c, dtype=f32, device=dev)
+        ls_row = torch.zeros(rows, dtype=f32, device=dev)
+        x, wn_prev, zcol, bnd = audio_rows, None, 0, []
+
+        def boundary(w, n_early, out):
+            _lib.call("rtts_sw_coupling_fwd1x1", x.data_ptr(), x.stride(0), None if wn_prev is None else wn_prev.data_ptr(),
+                      0 if wn_prev is None else wn_prev.stride(0), None if w is None else w.data_ptr(), x.shape[1], n_early, rows,
+                      None if out is None else out.data_ptr(), 0 if out is None else out.stride(0), z.data_ptr(), z.stride(0), zcol,
+                      ls_row.data_ptr(), _s())
+            bnd.append((x, wn_prev, zcol, n_early, w))
+
+        for k in range(self.n_flows):
+            n_early = self.early_return_size if self.return_early(k) else 0
+            out = torch.empty(rows, x.shape[1] - n_early, dtype=f32, device=dev)
+            boundary(self._wfwd[k], n_early, out)
+            zcol += n_early
+            x = out
+            wn_prev = blocks[k].forward(x, xmel, seg)
+        boundary(None, x.shape[1], None)
+        nrows = torch.full((seg.b,), float(seg.length), dtype=torch.float64, device=dev)
+        loss = self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)[1]
+        if after_forward is not None:
+            after_forward()
+
+        # backward: the boundaries from the tail to the first flow, each WN block between two of them
+        n_all = float(rows) * c
+        z_scale, inv_n = 1.0 / (sigma * sigma * n_all), 1.0 / n_all
+        nblk = _lib.load().rtts_sw_boundary_bwd_blocks(rows)
+        grads, dout = [], None
+        for j in reversed(range(self.n_flows + 1)):
+            x_in, wn_in, zc, n_early, w = bnd[j]
+            n_in = x_in.shape[1]
+            n = n_in - n_early
+            dx = dwn = dw = part = None
+            if wn_in is not None:
+                dx = torch.empty(rows, n_in, dtype=f32, device=dev)
+                dwn = blocks[j - 1].new_dwn(seg)
+            if w is not None:
+                dw = torch.empty(n, n, dtype=f32, device=dev)
+                part = torch.empty(nblk * n * n, dtype=f32, device=dev)
+            ptr = lambda t: None if t is None else t.data_ptr()     # noqa: E731
+            ld = lambda t: 0 if t is None else t.stride(0)          # noqa: E731
+            _lib.call("rtts_sw_boundary_bwd", x_in.data_ptr(), x_in.stride(0), ptr(wn_in), ld(wn_in), ptr(w), n_in, n_early, rows, ptr(dout),
+                      ld(dout), z.data_ptr(), z.stride(0), zc, z_scale, inv_n, ptr(dx), ld(dx), ptr(dwn), ld(dwn), ptr(dw), ptr(part), _s())
+            if w is not None:                                                      # - (B L / N) W^-T from the log-determinant
+                grads.append((self.inv_conv_layers[j].conv.weight, (dw - self._winv[j].t() / c).unsqueeze(-1)))
+            if wn_in is not None:
+                da0 = blocks[j - 1].backward(dwn, seg, grads)
+                dx[:, :da0.shape[1]] += da0
+                dout = dx
+        params = {id(p) for p in self.parameters()}
+        assert len(grads) == len(params) and {id(p) for p, _ in grads} == params, "nll_backward: a parameter was left without a gradient"
+        for p, g in grads:                     # one addition per parameter: two calls give exactly twice the gradient
+            g = g.reshape(p.shape)
+            if p.grad is None:
+                p.grad = g.contiguous().clone()
+            else:
+                p.grad.add_(g)
+        return loss
 
     def samples_per_frame(self) -> int:
         """Audio samples per mel frame: mel_upsample_scale * n_audio_channels (256, ``modules.py:341``)."""
