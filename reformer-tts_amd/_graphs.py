@@ -25,3 +25,18 @@ def capturing(graph, **kw):
     finally:
         if was_enabled:
             gc.enable()
+
+
+def warm_capture(fn):
+    """``fn`` once on a side stream (the warm-up: folding, allocator, lazy attributes), joined and synchronised, then ``fn``
+    captured into a new graph -> (graph, what the captured ``fn`` returned: the graph's output buffers)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with capturing(graph):
+        out = fn()
+    return graph, out

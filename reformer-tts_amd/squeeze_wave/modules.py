@@ -20,12 +20,15 @@ modules here only HOLD parameters.  ``infer`` (:334-376) runs through an explici
 The analysis direction, ``forward`` (:294-332) and the likelihood ``nll`` / ``nll_ragged`` / ``capture_nll_ragged``
 (``squeeze_wave/loss.py:14-31``), runs the same folded WN blocks in eval mode (running-statistics BatchNorm): per flow one
 ``rtts_sw_coupling_fwd1x1`` launch (the previous flow's coupling, this flow's early output and 1x1 convolution) in front of
-``_FoldedWN.forward``, and one ``rtts_sw_nll_reduce`` launch for the per-utterance sums.
+``_FoldedWN.forward``, and one ``rtts_sw_nll_reduce`` launch for the per-utterance sums.  The launch list of a WN block is
+written once, ``_FoldedWN.walk``, and so is the walk over the flows of each direction (``_flows``, ``_flows_fwd``); the mel is
+cast to bf16 rows once per call (``_MelRows``) and every flow's conditioning GEMM reads those rows.
 
-Training (``LitSqueezeWave``, ``training/wrappers.py:327-418``): ``nll_backward`` runs the same flow with batch-statistics
-BatchNorm (``_TrainWN``), keeps every layer's activations, and walks it backwards -- ``rtts_sw_boundary_bwd`` per flow boundary,
-``rtts_sw_gate_bwd`` and ``rtts_sw_dwbn_bwd_sums`` / ``_apply`` per layer, ``rtts_gemm_nt`` (input gradients) and
-``rtts_gemm_tn`` (weight gradients) for every 1x1 convolution -- adding the loss's gradient into every parameter's ``.grad``.
+Training (``LitSqueezeWave``, ``training/wrappers.py:327-418``): ``nll_backward`` runs the same ``_flows_fwd`` over ``_TrainWN``
+blocks -- the same ``walk``, given batch-statistics depthwise taps and a stash that keeps every layer's activations -- and walks
+it backwards -- ``rtts_sw_boundary_bwd`` per flow boundary, ``rtts_sw_gate_bwd`` and ``rtts_sw_dwbn_bwd_sums`` / ``_apply`` per
+layer, ``rtts_gemm_nt`` (input gradients) and ``rtts_gemm_tn`` (weight gradients) for every 1x1 convolution -- adding the loss's
+gradient into every parameter's ``.grad``.
 
 There is no CPU fallback: ``infer`` and ``forward`` raise off the GPU."""
 from __future__ import annotations
@@ -36,7 +39,9 @@ import torch
 from torch import nn
 
 from .. import _lib
-from .._graphs import capturing
+from .._graphs import warm_capture
+from ..edges import _ws
+from ..engine import _WS, _slab_ws, gemm
 from .config import WNConfig
 
 
@@ -165,11 +170,48 @@ def unpack_noise(draws, lengths, up: int) -> List[List[torch.Tensor]]:
     return [[d[up * moff[i]:up * moff[i + 1]].t().unsqueeze(0) for d in draws] for i in range(len(moff) - 1)]
 
 
+class _MelRows:
+    """The mel of one call: fp32 (B*Lm, n_mel) rows, and the bf16 rows the cond_layer of every flow reads, made ONCE per call
+    and layout.  ``in_tree`` is per flow (n_half shrinks at every early return), so a model may mix the two layouts: zero-padded
+    to 128 rows and the width of ``w_cond`` for the MFMA GEMM, a plain cast for the library GEMM.  ``wide`` (a training block:
+    cond_layer's weight gradient reads the rows again) widens the in-tree rows to ``rtts_gemm_tn``'s 128-column K granule."""
+
+    def __init__(self, rows: torch.Tensor, seg: _Segments):
+        self.rows, self.seg, self.cast = rows, seg, {}
+
+    def bf16(self, f: "_FoldedWN", wide: bool) -> torch.Tensor:
+        key = (f.in_tree, wide)
+        if key not in self.cast:
+            self.cast[key] = self._cast(f, wide)
+        return self.cast[key]
+
+    def _cast(self, f: "_FoldedWN", wide: bool) -> torch.Tensor:
+        rows, seg = self.rows, self.seg
+        if not f.in_tree:
+            return rows.to(torch.bfloat16)
+        mp, kp = _pad(seg.b * seg.mel_len, 128), f.w_cond.shape[1]
+        x = torch.empty(mp, kp, dtype=torch.bfloat16, device=rows.device)
+        _lib.call("rtts_to_halo", rows.data_ptr(), rows.stride(0), 0, f.n_mel, 1, seg.b, seg.mel_len, 0, kp, x.data_ptr(), 0, mp, _s())
+        return _k128(x) if wide else x
+
+
+def _fold_taps(bn, dw, a: torch.Tensor, mean: torch.Tensor):
+    """BatchNorm as x * a + c0, c0 = beta - mean * a, folded into the depthwise convolution behind it:
+    dw(bn(x)) = sum_k (w_k * a) x_{l+k-1} + [b + (sum_k w_k) * c0] -> (taps (C, 3), bias, lo, hi), all fp32.  Zero padding pads
+    bn(x), i.e. the reference does NOT add the constant c0 at the borders: at l = 0 the tap k = 0 sees the zero padding, not c0,
+    and at l = L-1 the tap k = 2 likewise, so the border rows get the exact corrections lo = w_0 * c0 and hi = w_2 * c0 taken
+    off by the depthwise kernel.  ``a`` and ``mean`` come from the running statistics (inference, the likelihood) or from the
+    batch's (training)."""
+    c0 = bn.bias.detach().float() - mean * a
+    w = dw.weight.detach().float().squeeze(1)                                  # (C, 3)
+    taps, bias = (w * a[:, None]).contiguous(), (dw.bias.detach().float() + w.sum(1) * c0).contiguous()
+    return taps, bias, (w[:, 0] * c0).contiguous(), (w[:, 2] * c0).contiguous()
+
+
 class _FoldedWN:
-    """Inference weights of one WN block: bf16 GEMM operands (row-major (Cout, Cin)), fp32 biases, depthwise taps with
-    the eval-mode BatchNorm folded in:  dw(bn(x)) = sum_k (w_k * a) x_{l+k-1} + [b + (sum_k w_k) * c],
-    a = gamma / sqrt(var + eps), c = beta - mean * a.  (Zero padding pads bn(x), i.e. the constant c is NOT added at the
-    borders by the reference; the border rows get the exact correction below.)
+    """Weights of one WN block and the walk over its launches: bf16 GEMM operands (row-major (Cout, Cin)), fp32 biases, and for
+    inference and the likelihood the depthwise taps with the eval-mode BatchNorm folded in (``_fold_taps`` with
+    a = gamma / sqrt(var + eps) and the running mean).
 
     Every 1x1 convolution (``start``, ``cond_layer``, the pointwise half of ``in_layers``, ``res_skip_layers``, ``end``;
     reference ``modules.py:203-235``) is ``rtts_gemm_nt`` (csrc/gemm_nt.hip) over channels-last rows: operands are padded ONCE
@@ -177,7 +219,8 @@ class _FoldedWN:
     columns), the ``end`` projection's 2 * n_half outputs to a multiple of 64 (zero rows; its consumer takes a row stride) --
     and the row count of an utterance is rounded up to 128 in the activation buffers (rows are independent: the extra rows
     are never read back).  ``in_tree`` is False for toy widths the MFMA kernel does not tile (n_channels % 64, n_half % 8 or
-    n_mel % 8 != 0): those run the same arithmetic through the library GEMM and say so once."""
+    n_mel % 8 != 0): those run the same arithmetic through the library GEMM (``gemms``: the one place that choice is made) and
+    say so once."""
 
     def __init__(self, wn: WN, fold_bn: bool = True):
         bf = torch.bfloat16
@@ -188,6 +231,7 @@ class _FoldedWN:
         w_end = wn.end_conv.weight.detach().float().squeeze(-1)
         self.n_half, self.n_mel = w_start.shape[1], w_cond.shape[1]
         self.in_tree = self.c % 64 == 0 and self.n_half % 8 == 0 and self.n_mel % 8 == 0
+        self.gemms = _MfmaGemms if self.in_tree else _LibraryGemms
         dev = w_start.device
 
         def kpad(w):            # (N, K) -> (N, K rounded up to 64) bf16, zero columns
@@ -204,75 +248,80 @@ class _FoldedWN:
         self.w_end[:w_end.shape[0]] = w_end.to(bf)
         self.b_end = torch.zeros(self.n_end, dtype=torch.float32, device=dev)
         self.b_end[:w_end.shape[0]] = wn.end_conv.bias.detach().float()
-        self.dw_w, self.dw_b, self.dw_edge, self.w_pw, self.b_pw, self.w_rs, self.b_rs = [], [], [], [], [], [], []
+        self.dw_taps, self.w_pw, self.b_pw, self.w_rs, self.b_rs = [], [], [], [], []
         for i in range(wn.n_layers):
             bn, dw, pw = wn.in_layers[i].layer
             self.w_pw.append(pw.weight.detach().float().squeeze(-1).to(bf).contiguous())
             self.b_pw.append(pw.bias.detach().float().contiguous())
             self.w_rs.append(_normed(wn.res_skip_layers[i]).to(bf).contiguous())
             self.b_rs.append(wn.res_skip_layers[i].bias.detach().float().contiguous())
-            if not fold_bn:          # a training step folds its own batch statistics (_TrainWN): no depthwise taps here
-                continue
-            a = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
-            cst = bn.bias.detach().float() - bn.running_mean.float() * a
-            w = dw.weight.detach().float().squeeze(1)                          # (C, 3)
-            self.dw_w.append((w * a[:, None]).contiguous())
-            self.dw_b.append((dw.bias.detach().float() + w.sum(1) * cst).contiguous())
-            # at l = 0 the tap k = 0 sees the zero padding of bn(x), not c; at l = L-1 the tap k = 2 likewise
-            self.dw_edge.append(((w[:, 0] * cst).contiguous(), (w[:, 2] * cst).contiguous()))
+            if fold_bn:              # a training step folds its own batch statistics (_TrainWN): no depthwise taps here
+                a = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
+                self.dw_taps.append(_fold_taps(bn, dw, a, bn.running_mean.float()))
 
-    def condition(self, mel: torch.Tensor, seg: _Segments) -> torch.Tensor:
-        """mel fp32 (B*Lm, n_mel) rows -> (rows, 2c * n_layers) bf16: the conditioning of all layers in one GEMM."""
-        if not self.in_tree:
-            return torch.addmm(self.b_cond.to(torch.bfloat16), mel.to(torch.bfloat16), self.w_cond.t())
-        from ..engine import gemm
-        mp, kp = _pad(seg.b * seg.mel_len, 128), self.w_cond.shape[1]
-        x = torch.empty(mp, kp, dtype=torch.bfloat16, device=mel.device)
-        _lib.call("rtts_to_halo", mel.data_ptr(), mel.stride(0), 0, self.n_mel, 1, seg.b, seg.mel_len, 0, kp, x.data_ptr(), 0, mp, _s())
-        return gemm(x, self.w_cond, bias=self.b_cond)
+    def forward(self, audio: torch.Tensor, mel: _MelRows, seg: _Segments) -> torch.Tensor:
+        """The block in eval mode, arguments and result as ``walk``: the taps folded from the running statistics, nothing kept."""
+        return self.walk(audio, mel, seg, lambda i, h, seg: self.dw_taps[i])
 
-    def forward(self, audio: torch.Tensor, mel: torch.Tensor, seg: _Segments) -> torch.Tensor:
-        """audio fp32 (seg.rows, n_rem) rows (the first n_half channels condition the block), mel fp32 (B*Lm, n_mel) rows
-        -> fp32 (rows >= seg.rows, n_end >= 2*n_half) = [s | b | zero columns].  Only the depthwise convolution looks
-        across rows: it is the one launch that differs between a uniform and a packed batch."""
-        dev, c = audio.device, self.c
-        b, length, mel_len, up = seg.b, seg.length, seg.mel_len, seg.up
-        m = seg.rows
-        cond = self.condition(mel, seg)
+    def walk(self, audio: torch.Tensor, mel: _MelRows, seg: _Segments, taps_of, stash=None) -> torch.Tensor:
+        """The launch list of a WN block (``WN.forward``, reference ``modules.py:203-235``): audio fp32 (seg.rows, n_rem) rows
+        (the first n_half channels condition the block), the call's mel rows -> fp32 (rows >= seg.rows,
+        n_end >= 2*n_half) = [log_s | b | zero columns].  The conditioning of all layers is one GEMM; only the depthwise
+        convolution looks across rows: it is the one launch that differs between a uniform and a packed batch.
+
+        ``taps_of(i, h, seg)`` gives layer i's depthwise (taps, bias, lo, hi) for the residual stream ``h`` in front of it,
+        followed by whatever else the stash is to keep with that layer.  ``stash`` (training): the object that gets what the
+        backward needs as attributes -- ``xmel`` (widened, like ``a0``, to the weight-gradient GEMM's K granule), ``cond``,
+        ``a0``, ``hb``, ``mp`` and ``layers``, per layer ``(h, dwo, pw, acts, *what taps_of added)`` -- so the residual epilogue
+        writes a fresh buffer instead of ``h`` in place, and padding rows (the activation buffers are rounded up to 128 rows)
+        are zeroed wherever a buffer is written by a kernel that stops at the real rows: the weight-gradient GEMMs and column
+        sums run over all rows.  Without it buffers are plain ``torch.empty`` and nothing is zeroed."""
+        dev, c, bf, mm = audio.device, self.c, torch.bfloat16, self.gemms.mm
+        b, length, mel_len, up, m = seg.b, seg.length, seg.mel_len, seg.up, seg.rows
+        keep = stash is not None
+        xmel = mel.bf16(self, wide=keep)
         if self.in_tree:
-            from ..engine import gemm
+            cond = mm(xmel[:, :self.w_cond.shape[1]], self.w_cond, self.b_cond)  # (rows, 2c * n_layers) bf16
             mp, kp = _pad(m, 128), self.w_start.shape[1]
-            a0 = torch.empty(mp, kp, dtype=torch.bfloat16, device=dev)        # bf16 copy of the conditioning half, zero padded
+            a0 = torch.empty(mp, kp, dtype=bf, device=dev)                     # bf16 copy of the conditioning half, zero padded
             _lib.call("rtts_to_halo", audio.data_ptr(), audio.stride(0), 0, self.n_half, 1, b, length, 0, kp, a0.data_ptr(), 0, mp, _s())
-            h = gemm(a0, self.w_start, bias=self.b_start, out_f32=True)        # (mp, c) fp32: the WN residual stream
-            mm = lambda x, w, bias=None, f32=False: gemm(x, w, bias=bias, out_f32=f32)     # noqa: E731
-        else:
+            h = mm(a0, self.w_start, self.b_start, True)                       # (mp, c) fp32: the WN residual stream
+            a0 = _k128(a0) if keep else a0
+        else:                                                                  # the toy path keeps start_conv's input in fp32
             _lib.note_general_path("SqueezeWave WN block", f"widths (n_channels {c}, n_half {self.n_half}, n_mel {self.n_mel}) the MFMA GEMM "
                                    "does not tile (n_channels % 64, n_half % 8, n_mel % 8): library GEMM")
+            cond = torch.addmm(self.b_cond.to(bf), xmel, self.w_cond.t())
             mp = m
             a0 = audio[:, :self.n_half].contiguous()
             h = torch.addmm(self.b_start, a0, self.w_start.float().t())
 
-            def mm(x, w, bias=None, f32=False):
-                y = torch.mm(x, w.t(), out_dtype=torch.float32)
-                y = y if bias is None else y + bias
-                return y if f32 else y.to(torch.bfloat16)
+        def rows(width, dtype):
+            t = torch.empty(mp, width, dtype=dtype, device=dev)
+            return _zero_tail(t, m) if keep else t
+
+        layers = []
         for i in range(self.nl):
-            dw = torch.empty(mp, c, dtype=torch.bfloat16, device=dev)
-            lo, hi = self.dw_edge[i]                                             # zero padding pads bn(x): no folded constant there
+            taps, bias, lo, hi, *kept = taps_of(i, h, seg)                     # zero padding pads bn(x): no folded constant there
+            dwo = rows(c, bf)
             if seg.moff is None:
-                _lib.call("rtts_sw_depthwise_k3", h.data_ptr(), self.dw_w[i].data_ptr(), self.dw_b[i].data_ptr(), b, length, c, dw.data_ptr(),
-                          lo.data_ptr(), hi.data_ptr(), _s())
+                _lib.call("rtts_sw_depthwise_k3", h.data_ptr(), taps.data_ptr(), bias.data_ptr(), b, length, c, dwo.data_ptr(), lo.data_ptr(),
+                          hi.data_ptr(), _s())
             else:
-                _lib.call("rtts_sw_depthwise_k3_seg", h.data_ptr(), self.dw_w[i].data_ptr(), self.dw_b[i].data_ptr(), seg.moff.data_ptr(),
-                          seg.nseg, up, m, c, dw.data_ptr(), lo.data_ptr(), hi.data_ptr(), _s())
-            pw = mm(dw, self.w_pw[i], self.b_pw[i])                                # (mp, 2c) bf16
-            acts = torch.empty(mp, c, dtype=torch.bfloat16, device=dev)
+                _lib.call("rtts_sw_depthwise_k3_seg", h.data_ptr(), taps.data_ptr(), bias.data_ptr(), seg.moff.data_ptr(), seg.nseg, up, m, c,
+                          dwo.data_ptr(), lo.data_ptr(), hi.data_ptr(), _s())
+            pw = mm(dwo, self.w_pw[i], self.b_pw[i])                           # (mp, 2c) bf16
+            acts = rows(c, bf)
             _lib.call("rtts_sw_gate", pw.data_ptr(), cond.data_ptr(), cond.stride(0), i * 2 * c, up, b, length, mel_len, c, acts.data_ptr(), _s())
             rs = mm(acts, self.w_rs[i])
-            _lib.call("rtts_residual_epilogue", h.data_ptr(), rs.data_ptr(), self.b_rs[i].data_ptr(), 1.0, h.data_ptr(), m, c, 0.0, 0, None, _s())
-        hb = torch.empty(mp, c, dtype=torch.bfloat16, device=dev)
+            nxt = rows(c, torch.float32) if keep else h
+            _lib.call("rtts_residual_epilogue", h.data_ptr(), rs.data_ptr(), self.b_rs[i].data_ptr(), 1.0, nxt.data_ptr(), m, c, 0.0, 0, None, _s())
+            if keep:
+                layers.append((h, dwo, pw, acts, *kept))
+            h = nxt
+        hb = rows(c, bf)
         _lib.call("rtts_cast_f32_bf16", h.data_ptr(), hb.data_ptr(), m * c, _s())
+        if keep:
+            stash.xmel, stash.cond, stash.a0, stash.hb, stash.mp, stash.layers = xmel, cond, a0, hb, mp, layers
         return mm(hb, self.w_end, self.b_end, True)
 
 
@@ -296,42 +345,22 @@ def _k128(x: torch.Tensor) -> torch.Tensor:
 TRAIN_WIDTHS = (128, 256, 512, 1024)     # n_channels the in-tree backward tiles: rtts_gemm_tn's 128 granule, the column-sum kernels' widths
 
 
-class _TrainWN:
-    """One WN block of a training step (``WN.forward``, reference ``modules.py:203-235``, in ``.train()``): the sequence of
-    ``_FoldedWN.forward`` with two differences.  In front of each depthwise convolution the statistics of the fp32 residual
-    stream over the B * L real rows are taken (``rtts_bn_moments`` / ``rtts_bn_from_moments``, which also maintain the running
-    statistics) and folded into the depthwise taps and edge corrections on the device (C-sized torch ops, no host read); and
-    every layer's input, depthwise output, pointwise output, gate output and statistics are kept for ``backward``.
+class _MfmaGemms:
+    """The GEMM forms of a WN block, forward and backward, on the in-tree kernels: bf16 operands, fp32 accumulation."""
 
-    Padding rows (the activation buffers are rounded up to 128 rows) are zeroed wherever a buffer is written by a kernel that
-    stops at the real rows: the weight-gradient GEMMs and column sums run over all rows.  Toy widths (``in_tree`` False) run
-    the same arithmetic through ``torch.mm``, as the forward does."""
+    @staticmethod
+    def mm(x, w, bias=None, f32=False):
+        """y = x @ w^T (+ bias), w (N, K): bf16, or the unrounded fp32 result."""
+        return gemm(x, w, bias=bias, out_f32=f32)
 
-    def __init__(self, wn: WN, f: _FoldedWN):
-        self.wn, self.f = wn, f                 # widths: SqueezeWave._train_widths has refused what the backward does not tile
-
-    # ---- the GEMM forms of the backward: bf16 operands, fp32 accumulation
-    def _mm(self, x, w, bias=None, f32=False):
-        if self.f.in_tree:
-            from ..engine import gemm
-            return gemm(x, w, bias=bias, out_f32=f32)
-        y = torch.mm(x, w.t(), out_dtype=torch.float32)
-        y = y if bias is None else y + bias
-        return y if f32 else y.to(torch.bfloat16)
-
-    def _dgrad(self, dy, w, f32=False):
+    @staticmethod
+    def dgrad(dy, w, f32=False):
         """dx = dy @ w, w (N, K) as the forward holds it."""
-        if self.f.in_tree:
-            from ..engine import gemm
-            return gemm(dy, w, kn=True, out_f32=f32)
-        dx = torch.mm(dy, w, out_dtype=torch.float32)
-        return dx if f32 else dx.to(torch.bfloat16)
+        return gemm(dy, w, kn=True, out_f32=f32)
 
-    def _wgrad(self, dy, x):
+    @staticmethod
+    def wgrad(dy, x):
         """dW (N, K) fp32 = dy^T @ x over ALL rows (padding rows of dy are zero, of x finite)."""
-        if not self.f.in_tree:
-            return torch.mm(dy.t(), x, out_dtype=torch.float32)
-        from ..engine import _slab_ws
         n, k = dy.shape[1], x.shape[1]
         out = torch.empty(n, k, dtype=torch.float32, device=dy.device)
         ws = _slab_ws(dy.device)
@@ -339,79 +368,75 @@ class _TrainWN:
                   ws.numel(), _s())
         return out
 
-    def _cast_colsum(self, d):
+    @staticmethod
+    def cast_colsum(d):
         """fp32 (M, d) -> (its bf16 copy, its column sums fp32 (d,))."""
-        if not self.f.in_tree:
-            return d.to(torch.bfloat16), d.sum(0)
-        from ..engine import _WS
         m, w = d.shape
         db = torch.empty(m, w, dtype=torch.bfloat16, device=d.device)
         out = torch.zeros(w, dtype=torch.float32, device=d.device)
         _lib.call("rtts_cast_colsum", d.data_ptr(), db.data_ptr(), out.data_ptr(), _WS.partial(d.device, w).data_ptr(), m, w, 0.0, 0, None, None, _s())
         return db, out
 
-    def _colsum(self, d, col0: int, width: int, out: torch.Tensor):
+    @staticmethod
+    def colsum(d, col0: int, width: int, out: torch.Tensor):
         """out (width,) fp32 += column sums of columns [col0, col0 + width) of the bf16 rows ``d``."""
-        if not self.f.in_tree:
-            out += d[:, col0:col0 + width].float().sum(0)
-            return
-        from ..engine import _WS
         view = d[:, col0:col0 + width]
         _lib.call("rtts_colsum_bf16", view.data_ptr(), None, d.stride(0), out.data_ptr(), _WS.partial(d.device, width).data_ptr(), d.shape[0], width,
                   0, 1.0, None, _s())
 
-    def forward(self, audio: torch.Tensor, xmel: torch.Tensor, seg: _Segments) -> torch.Tensor:
-        """audio fp32 (seg.rows, n_rem) rows, xmel the bf16 mel rows (``SqueezeWave._train_mel``) -> fp32 (rows >= seg.rows,
-        n_end) = [log_s | b | zero columns]; everything ``backward`` needs stays on ``self``."""
-        from ..edges import _ws
-        f, wn = self.f, self.wn
-        dev, c, bf = audio.device, f.c, torch.bfloat16
-        b, length, mel_len, m = seg.b, seg.length, seg.mel_len, seg.rows
-        self.xmel = xmel
-        if f.in_tree:
-            self.cond = self._mm(xmel[:, :f.w_cond.shape[1]], f.w_cond, f.b_cond)
-            mp, kp = _pad(m, 128), f.w_start.shape[1]
-            a0 = torch.empty(mp, kp, dtype=bf, device=dev)
-            _lib.call("rtts_to_halo", audio.data_ptr(), audio.stride(0), 0, f.n_half, 1, b, length, 0, kp, a0.data_ptr(), 0, mp, _s())
-            h = self._mm(a0, f.w_start, f.b_start, True)
-            self.a0 = _k128(a0)
-        else:
-            _lib.note_general_path("SqueezeWave WN block", f"widths (n_channels {c}, n_half {f.n_half}, n_mel {f.n_mel}) the MFMA GEMM "
-                                   "does not tile (n_channels % 64, n_half % 8, n_mel % 8): library GEMM")
-            self.cond = torch.addmm(f.b_cond.to(bf), xmel, f.w_cond.t())
-            mp = m
-            self.a0 = audio[:, :f.n_half].contiguous()
-            h = torch.addmm(f.b_start, self.a0, f.w_start.float().t())
-        self.mp, self.layers = mp, []
-        rows = lambda width, dtype: _zero_tail(torch.empty(mp, width, dtype=dtype, device=dev), m)     # noqa: E731
-        for i in range(f.nl):
-            bn, dwc, _ = wn.in_layers[i].layer
-            mom = torch.empty(2 * c + 1, dtype=torch.float32, device=dev)
-            mean, rstd = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
-            _lib.call("rtts_bn_moments", h.data_ptr(), b, length, 0, c, mom.data_ptr(), _ws(dev, c).data_ptr(), _s())
-            _lib.call("rtts_bn_from_moments", mom.data_ptr(), m, c, mean.data_ptr(), rstd.data_ptr(), bn.running_mean.data_ptr(),
-                      bn.running_var.data_ptr(), None, bn.num_batches_tracked.data_ptr(), _s())
-            # dw(bn(h)) with a = gamma * rstd, c0 = beta - mean * a folded into the taps, as _FoldedWN folds the running statistics
-            a = bn.weight.detach() * rstd
-            c0 = bn.bias.detach() - mean * a
-            w = dwc.weight.detach().squeeze(1)                                     # (C, 3)
-            taps, bias = (w * a[:, None]).contiguous(), dwc.bias.detach() + w.sum(1) * c0
-            lo, hi = (w[:, 0] * c0).contiguous(), (w[:, 2] * c0).contiguous()
-            dwo = rows(c, bf)
-            _lib.call("rtts_sw_depthwise_k3", h.data_ptr(), taps.data_ptr(), bias.data_ptr(), b, length, c, dwo.data_ptr(), lo.data_ptr(),
-                      hi.data_ptr(), _s())
-            pw = self._mm(dwo, f.w_pw[i], f.b_pw[i])                               # (mp, 2c) bf16
-            acts = rows(c, bf)
-            _lib.call("rtts_sw_gate", pw.data_ptr(), self.cond.data_ptr(), self.cond.stride(0), i * 2 * c, seg.up, b, length, mel_len, c,
-                      acts.data_ptr(), _s())
-            rs = self._mm(acts, f.w_rs[i])
-            nxt = rows(c, torch.float32)
-            _lib.call("rtts_residual_epilogue", h.data_ptr(), rs.data_ptr(), f.b_rs[i].data_ptr(), 1.0, nxt.data_ptr(), m, c, 0.0, 0, None, _s())
-            self.layers.append((h, dwo, pw, acts, mean, rstd, w.contiguous()))
-            h = nxt
-        self.hb = rows(c, bf)
-        _lib.call("rtts_cast_f32_bf16", h.data_ptr(), self.hb.data_ptr(), m * c, _s())
-        return self._mm(self.hb, f.w_end, f.b_end, True)
+
+class _LibraryGemms:
+    """The same forms for toy widths the MFMA kernels do not tile: the same arithmetic (bf16 operands, fp32 accumulation)
+    through the library GEMM."""
+
+    @staticmethod
+    def mm(x, w, bias=None, f32=False):
+        y = torch.mm(x, w.t(), out_dtype=torch.float32)
+        y = y if bias is None else y + bias
+        return y if f32 else y.to(torch.bfloat16)
+
+    @staticmethod
+    def dgrad(dy, w, f32=False):
+        dx = torch.mm(dy, w, out_dtype=torch.float32)
+        return dx if f32 else dx.to(torch.bfloat16)
+
+    @staticmethod
+    def wgrad(dy, x):
+        return torch.mm(dy.t(), x, out_dtype=torch.float32)
+
+    @staticmethod
+    def cast_colsum(d):
+        return d.to(torch.bfloat16), d.sum(0)
+
+    @staticmethod
+    def colsum(d, col0: int, width: int, out: torch.Tensor):
+        out += d[:, col0:col0 + width].float().sum(0)
+
+
+class _TrainWN:
+    """One WN block of a training step (``WN.forward`` in ``.train()``): ``_FoldedWN.walk`` with its two arguments.  The taps:
+    in front of each depthwise convolution the statistics of the fp32 residual stream over the B * L real rows are taken
+    (``rtts_bn_moments`` / ``rtts_bn_from_moments``, which also maintain the running statistics) and folded into the depthwise
+    taps and edge corrections on the device (C-sized torch ops, no host read).  The stash: this object; every layer's input,
+    depthwise output, pointwise output, gate output and statistics are kept for ``backward``.  Toy widths (``in_tree`` False)
+    run the same arithmetic through ``torch.mm``, as the forward does."""
+
+    def __init__(self, wn: WN, f: _FoldedWN):
+        self.wn, self.f = wn, f                 # widths: SqueezeWave._train_widths has refused what the backward does not tile
+
+    def _batch_taps(self, i: int, h: torch.Tensor, seg: _Segments):
+        bn, dwc, _ = self.wn.in_layers[i].layer
+        dev, c = h.device, self.f.c
+        mom = torch.empty(2 * c + 1, dtype=torch.float32, device=dev)
+        mean, rstd = torch.empty(c, dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev)
+        _lib.call("rtts_bn_moments", h.data_ptr(), seg.b, seg.length, 0, c, mom.data_ptr(), _ws(dev, c).data_ptr(), _s())
+        _lib.call("rtts_bn_from_moments", mom.data_ptr(), seg.rows, c, mean.data_ptr(), rstd.data_ptr(), bn.running_mean.data_ptr(),
+                  bn.running_var.data_ptr(), None, bn.num_batches_tracked.data_ptr(), _s())
+        return (*_fold_taps(bn, dwc, bn.weight.detach() * rstd, mean), mean, rstd, dwc.weight.detach().squeeze(1).contiguous())
+
+    def forward(self, audio: torch.Tensor, mel: _MelRows, seg: _Segments) -> torch.Tensor:
+        """-> fp32 [log_s | b | zero columns], as ``_FoldedWN.forward``; everything ``backward`` needs stays on ``self``."""
+        return self.f.walk(audio, mel, seg, self._batch_taps, stash=self)
 
     def new_dwn(self, seg: _Segments) -> torch.Tensor:
         """The buffer ``rtts_sw_boundary_bwd`` writes d [log_s | b] into: 128 columns wide and zero outside the real rows and
@@ -438,14 +463,14 @@ class _TrainWN:
     def backward(self, dwn: torch.Tensor, seg: _Segments, grads: list) -> torch.Tensor:
         """dwn = d loss / d [log_s | b] (``new_dwn``) -> d loss / d (the conditioning half of the block's input) fp32 (seg.rows,
         n_half); appends (parameter, gradient) for every parameter of the block to ``grads``."""
-        f, wn = self.f, self.wn
+        f, wn, g = self.f, self.wn, self.f.gemms
         dev, c, nh, bf = dwn.device, f.c, f.n_half, torch.bfloat16
         b, length, mel_len, m, mp = seg.b, seg.length, seg.mel_len, seg.rows, self.mp
-        dwn_b, db_end = self._cast_colsum(dwn)
-        dw_end = self._wgrad(dwn_b, self.hb)
+        dwn_b, db_end = g.cast_colsum(dwn)
+        dw_end = g.wgrad(dwn_b, self.hb)
         grads.append((wn.end_conv.weight, dw_end[:2 * nh].unsqueeze(-1)))
         grads.append((wn.end_conv.bias, db_end[:2 * nh]))
-        dh = self._dgrad(dwn_b[:, :f.w_end.shape[0]], f.w_end, True)              # (mp, c) fp32, zero in the padding rows
+        dh = g.dgrad(dwn_b[:, :f.w_end.shape[0]], f.w_end, True)              # (mp, c) fp32, zero in the padding rows
         dcond = _zero_tail(torch.empty(self.cond.shape, dtype=bf, device=dev), b * mel_len)
         db_cond = torch.zeros(self.cond.shape[1], dtype=torch.float32, device=dev)
         n_part = _lib.load().rtts_sw_dwbn_bwd_partial_floats(m, c)
@@ -453,19 +478,19 @@ class _TrainWN:
         for i in reversed(range(f.nl)):
             h_in, dwo, pw, acts, mean, rstd, w = self.layers[i]
             bn, dwc, pwc = wn.in_layers[i].layer
-            drs, db_rs = self._cast_colsum(dh)
-            self._weight_norm_grads(wn.res_skip_layers[i], self._wgrad(drs, acts), grads)
+            drs, db_rs = g.cast_colsum(dh)
+            self._weight_norm_grads(wn.res_skip_layers[i], g.wgrad(drs, acts), grads)
             grads.append((wn.res_skip_layers[i].bias, db_rs))
-            dacts = self._dgrad(drs, f.w_rs[i])
+            dacts = g.dgrad(drs, f.w_rs[i])
             dpw = _zero_tail(torch.empty(mp, 2 * c, dtype=bf, device=dev), m)
             _lib.call("rtts_sw_gate_bwd", pw.data_ptr(), self.cond.data_ptr(), self.cond.stride(0), i * 2 * c, seg.up, b, length, mel_len, c,
                       dacts.data_ptr(), dpw.data_ptr(), dcond.data_ptr(), dcond.stride(0), _s())
-            self._colsum(dcond, i * 2 * c, 2 * c, db_cond[i * 2 * c:(i + 1) * 2 * c])
+            g.colsum(dcond, i * 2 * c, 2 * c, db_cond[i * 2 * c:(i + 1) * 2 * c])
             db_pw = torch.zeros(2 * c, dtype=torch.float32, device=dev)
-            self._colsum(dpw, 0, 2 * c, db_pw)
-            grads.append((pwc.weight, self._wgrad(dpw, dwo).unsqueeze(-1)))
+            g.colsum(dpw, 0, 2 * c, db_pw)
+            grads.append((pwc.weight, g.wgrad(dpw, dwo).unsqueeze(-1)))
             grads.append((pwc.bias, db_pw))
-            ddw = self._dgrad(dpw, f.w_pw[i])                                      # (mp, c) bf16
+            ddw = g.dgrad(dpw, f.w_pw[i])                                      # (mp, c) bf16
             sums = torch.empty(6, c, dtype=torch.float32, device=dev)
             stats = (mean.data_ptr(), rstd.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), w.data_ptr())
             _lib.call("rtts_sw_dwbn_bwd_sums", h_in.data_ptr(), ddw.data_ptr(), *stats, b, length, c, sums.data_ptr(), part.data_ptr(), _s())
@@ -474,12 +499,12 @@ class _TrainWN:
             grads.append((dwc.bias, sums[3]))
             grads.append((bn.weight, sums[4]))
             grads.append((bn.bias, sums[5]))
-        self._weight_norm_grads(wn.cond_layer, self._wgrad(dcond, self.xmel)[:, :f.n_mel], grads)
+        self._weight_norm_grads(wn.cond_layer, g.wgrad(dcond, self.xmel)[:, :f.n_mel], grads)
         grads.append((wn.cond_layer.bias, db_cond))
         if f.in_tree:
-            dhs, db_start = self._cast_colsum(dh)
-            dw_start = self._wgrad(dhs, self.a0)[:, :nh]
-            da0 = self._dgrad(dhs, f.w_start, True)[:m, :nh]
+            dhs, db_start = g.cast_colsum(dh)
+            dw_start = g.wgrad(dhs, self.a0)[:, :nh]
+            da0 = g.dgrad(dhs, f.w_start, True)[:m, :nh]
         else:                                                                      # the toy path keeps start_conv's input in fp32
             db_start, dw_start, da0 = dh.sum(0), torch.mm(dh.t(), self.a0), torch.mm(dh, f.w_start.float())
         self._weight_norm_grads(wn.start_conv, dw_start, grads)
@@ -555,11 +580,13 @@ class SqueezeWave(nn.Module):
 
     def _flows(self, folded: List[_FoldedWN], mel_rows: torch.Tensor, seg: _Segments, draws, sigma: float) -> torch.Tensor:
         """The executor of ``infer`` (modules.py:340-376) over rows: ``draws`` yields the Gaussian draws as fp32
-        (seg.rows, C) rows in the order they are consumed -> clamped audio rows (seg.rows, n_audio_channels)."""
+        (seg.rows, C) rows in the order they are consumed -> clamped audio rows (seg.rows, n_audio_channels).  The bf16 mel
+        rows are made once (``_MelRows``); every flow's conditioning GEMM reads them."""
+        mel = _MelRows(mel_rows, seg)
         audio = next(draws)                                                        # (rows, n_remaining) fp32
         for k in reversed(range(self.n_flows)):
             n = audio.shape[1]
-            wn_out = folded[k].forward(audio, mel_rows, seg)                       # [s | b | padding], row stride n_end
+            wn_out = folded[k].forward(audio, mel, seg)                            # [s | b | padding], row stride n_end
             nxt = torch.empty_like(audio)
             # inverse coupling + inverse 1x1 convolution in one fp32 launch (modules.py:353-361)
             _lib.call("rtts_sw_coupling_inv1x1", audio.data_ptr(), audio.stride(0), wn_out.data_ptr(), wn_out.stride(0),
@@ -577,16 +604,15 @@ class SqueezeWave(nn.Module):
         folded = self._fold()
         mel = mel_spectrogram.to(dev)
         b, n_mel, mel_len = mel.shape
-        length = mel_len * (256 // self.n_audio_channels)
-        if folded[0].up * mel_len != length:
-            raise ValueError("mel_upsample_scale must equal 256 // n_audio_channels")
+        up = self._up()
+        length = up * mel_len
         shapes = self.noise_shapes(b, mel_len)
         if noise is None:
             noise = [torch.randn(s, device=dev) for s in shapes]
         assert [tuple(z.shape) for z in noise] == shapes, "noise tensors do not match noise_shapes()"
         rows = lambda z: z.to(dev, torch.float32).permute(0, 2, 1).reshape(b * length, -1).contiguous()    # noqa: E731
         mel_rows = mel.to(torch.float32).permute(0, 2, 1).reshape(b * mel_len, n_mel).contiguous()
-        audio = self._flows(folded, mel_rows, _Segments.uniform(b, mel_len, folded[0].up), (rows(z) for z in noise), sigma)
+        audio = self._flows(folded, mel_rows, _Segments.uniform(b, mel_len, up), (rows(z) for z in noise), sigma)
         return audio.view(b, length * audio.shape[1])
 
     def _pack_mel(self, mel: torch.Tensor, lens: List[int], moff: torch.Tensor, capacity_frames: int, out: Optional[torch.Tensor] = None):
@@ -660,19 +686,9 @@ class SqueezeWave(nn.Module):
         replayed without host work; eager inference is launch-bound: 14 ms whether B is 1 or 8).  Per call the mel is
         copied into the graph's input buffer and fresh Gaussian noise is drawn inside the graph (the default CUDA
         generator is graph-safe).  The returned audio tensor is the graph's output buffer: copy it before the next call."""
-        dev = self.inv_conv_layers[0].conv.weight.device
-        mel_buf = torch.zeros(batch, self.wn_layers[0].cond_layer.weight_v.shape[1] if hasattr(self.wn_layers[0].cond_layer, "weight_v")
-                              else self.wn_layers[0].cond_layer.weight.shape[1], mel_len, device=dev)
-        shapes = self.noise_shapes(batch, mel_len)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self.infer(mel_buf, sigma)                         # warm-up: folding, allocator, lazy attributes
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with capturing(graph):
-            out = self.infer(mel_buf, sigma, noise=[torch.randn(s, device=dev) for s in shapes])
+        dev = self._device("capture")
+        mel_buf = torch.zeros(batch, self._n_mel(), mel_len, device=dev)
+        graph, out = warm_capture(lambda: self.infer(mel_buf, sigma))          # infer draws its noise on the device
 
         def run(mel: torch.Tensor) -> torch.Tensor:
             mel_buf.copy_(mel, non_blocking=True)
@@ -702,16 +718,12 @@ class SqueezeWave(nn.Module):
         mel_rows = torch.zeros(cap, self._n_mel(), device=dev)
         moff = torch.zeros(batch + 1, dtype=torch.int32, device=dev)        # every row padding until a call sets the table
         seg = _Segments.packed(moff, cap, up)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                          # warm-up: allocator, lazy attributes
-            self._flows(folded, mel_rows, seg, iter([torch.randn(up * cap, w, device=dev) for w in widths]), sigma)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with capturing(graph):
+
+        def flows():
             draws = [torch.randn(up * cap, w, device=dev) for w in widths]
-            out = self._flows(folded, mel_rows, seg, iter(draws), sigma).view(-1)
+            return draws, self._flows(folded, mel_rows, seg, iter(draws), sigma).view(-1)
+
+        graph, (draws, out) = warm_capture(flows)
 
         def run(mel: torch.Tensor, lengths):
             lens = host_lengths(lengths)
@@ -756,13 +768,16 @@ class SqueezeWave(nn.Module):
             raise _lib.RttsError(f"SqueezeWave.{what} runs on the GPU only: {name} is on {getattr(t, 'device', type(t).__name__)}, the model on {dev}")
         return t
 
-    def _flows_fwd(self, folded: List[_FoldedWN], mel_rows: torch.Tensor, seg: _Segments, audio_rows: torch.Tensor, keep: bool):
-        """The executor of ``forward`` (modules.py:308-331) over rows: audio rows fp32 (seg.rows, n_audio_channels) ->
+    def _flows_fwd(self, blocks, mel_rows: torch.Tensor, seg: _Segments, audio_rows: torch.Tensor, keep: bool, bnd: Optional[list] = None):
+        """The executor of ``forward`` (modules.py:308-331) over rows, in eval mode (``blocks``: the ``_FoldedWN`` of every flow)
+        and in a training step (the ``_TrainWN``): mel rows fp32 (B*Lm, n_mel), audio rows fp32 (seg.rows, n_audio_channels) ->
         (z rows (seg.rows, n_audio_channels): the early blocks in flow order, then the remainder; ls_row (seg.rows,): every
-        row's sum of log_s over all flows; the WN outputs [log_s | b | padding] per flow if ``keep``).  Per flow: one
-        boundary launch (the previous flow's coupling, this flow's early split and 1x1 convolution), then the WN block;
-        a last launch applies the final coupling."""
+        row's sum of log_s over all flows; the WN outputs [log_s | b | padding] per flow if ``keep``).  The bf16 mel rows
+        are made once (``_MelRows``); then per flow one boundary launch (the previous flow's coupling, this flow's early split and 1x1
+        convolution) and the WN block; a last launch applies the final coupling.  ``bnd`` (training): every boundary's
+        (x, wn_prev, zcol, n_early, w) is appended to it for the backward walk."""
         rows, dev = seg.rows, audio_rows.device
+        mel = _MelRows(mel_rows, seg)
         z = torch.empty(rows, self.n_audio_channels, dtype=torch.float32, device=dev)
         ls_row = torch.zeros(rows, dtype=torch.float32, device=dev)
         x, wn_prev, zcol, kept = audio_rows, None, 0, []
@@ -772,6 +787,8 @@ class SqueezeWave(nn.Module):
                       0 if wn_prev is None else wn_prev.stride(0), None if w is None else w.data_ptr(), x.shape[1], n_early, rows,
                       None if out is None else out.data_ptr(), 0 if out is None else out.stride(0), z.data_ptr(), z.stride(0), zcol,
                       ls_row.data_ptr(), _s())
+            if bnd is not None:
+                bnd.append((x, wn_prev, zcol, n_early, w))
 
         for k in range(self.n_flows):
             n_early = self.early_return_size if self.return_early(k) else 0
@@ -779,7 +796,7 @@ class SqueezeWave(nn.Module):
             boundary(self._wfwd[k], n_early, out)
             zcol += n_early
             x = out
-            wn_prev = folded[k].forward(x, mel_rows, seg)                          # [log_s | b | padding], row stride n_end
+            wn_prev = blocks[k].forward(x, mel, seg)                               # [log_s | b | padding], row stride n_end
             if keep:
                 kept.append(wn_prev)
         boundary(None, x.shape[1], None)
@@ -843,17 +860,6 @@ class SqueezeWave(nn.Module):
         return self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)[1]
 
     # ------------------------------------------------------------------ training: the likelihood's gradient
-    def _train_mel(self, folded: List[_FoldedWN], mel_rows: torch.Tensor, seg: _Segments) -> torch.Tensor:
-        """The bf16 mel rows every flow's cond_layer reads (and its weight gradient reads again): zero-padded to 128 rows and
-        a width of 128 on the in-tree path."""
-        f = folded[0]
-        if not f.in_tree:
-            return mel_rows.to(torch.bfloat16)
-        mp, kp = _pad(seg.b * seg.mel_len, 128), f.w_cond.shape[1]
-        x = torch.empty(mp, kp, dtype=torch.bfloat16, device=mel_rows.device)
-        _lib.call("rtts_to_halo", mel_rows.data_ptr(), mel_rows.stride(0), 0, f.n_mel, 1, seg.b, seg.mel_len, 0, kp, x.data_ptr(), 0, mp, _s())
-        return _k128(x)
-
     def _train_widths(self):
         """Widths the forward runs on the MFMA GEMMs (``_FoldedWN.in_tree``) but the backward does not tile are refused by name:
         ``rtts_gemm_tn`` needs N, K % 128 and the column-sum kernels take 128, 256, 512, 1024 or 2048 columns."""
@@ -897,26 +903,8 @@ class SqueezeWave(nn.Module):
         rows, dev, c = seg.rows, audio_rows.device, self.n_audio_channels
         f32 = torch.float32
         blocks = [_TrainWN(wn, f) for wn, f in zip(self.wn_layers, folded)]
-        xmel = self._train_mel(folded, mel_rows, seg)
-        z = torch.empty(rows, c, dtype=f32, device=dev)
-        ls_row = torch.zeros(rows, dtype=f32, device=dev)
-        x, wn_prev, zcol, bnd = audio_rows, None, 0, []
-
-        def boundary(w, n_early, out):
-            _lib.call("rtts_sw_coupling_fwd1x1", x.data_ptr(), x.stride(0), None if wn_prev is None else wn_prev.data_ptr(),
-                      0 if wn_prev is None else wn_prev.stride(0), None if w is None else w.data_ptr(), x.shape[1], n_early, rows,
-                      None if out is None else out.data_ptr(), 0 if out is None else out.stride(0), z.data_ptr(), z.stride(0), zcol,
-                      ls_row.data_ptr(), _s())
-            bnd.append((x, wn_prev, zcol, n_early, w))
-
-        for k in range(self.n_flows):
-            n_early = self.early_return_size if self.return_early(k) else 0
-            out = torch.empty(rows, x.shape[1] - n_early, dtype=f32, device=dev)
-            boundary(self._wfwd[k], n_early, out)
-            zcol += n_early
-            x = out
-            wn_prev = blocks[k].forward(x, xmel, seg)
-        boundary(None, x.shape[1], None)
+        bnd = []                               # the forward: the likelihood's walk over training blocks, every boundary recorded
+        z, ls_row, _ = self._flows_fwd(blocks, mel_rows, seg, audio_rows, False, bnd)
         nrows = torch.full((seg.b,), float(seg.length), dtype=torch.float64, device=dev)
         loss = self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)[1]
         if after_forward is not None:
@@ -1061,15 +1049,7 @@ class SqueezeWave(nn.Module):
             nrows = (moff[1:] - moff[:-1]).to(torch.float64) * up
             return self._nll_from_sums(self._reduce(z, ls_row, seg), nrows, sigma, logdet)
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                          # warm-up: allocator, lazy attributes
-            score()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with capturing(graph):
-            per, total_loss = score()
+        graph, (per, total_loss) = warm_capture(score)
 
         def run(mel: torch.Tensor, frames, audio: torch.Tensor, sample_offsets=None):
             if self.training:
