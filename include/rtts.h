@@ -590,6 +590,22 @@ int rtts_sw_boundary_bwd_blocks(int64_t rows);
 int rtts_sw_boundary_bwd(const float* x, int64_t ld_x, const float* wn_out, int64_t ld_wn, const float* w, int n_in, int n_early,
                          int64_t rows, const float* dout, int64_t ld_dout, const float* z, int64_t ld_z, int z_col, float z_scale,
                          float inv_n, float* dx, int64_t ld_dx, float* dwn, int64_t ld_dwn, float* dw, float* partial_ws, void* stream);
+/* The invertible 1x1 convolutions of a training step factored on the device (replaces torch.logdet(W), squeeze_wave/modules.py:63,
+ * and W.inverse(), :79, for ALL flows of a model in ONE launch; csrc/sw_lu.hip):
+ *   w[i]      address of W_i, (n[i], n[i]) fp32 row-major, dense;   winv[i]  address of the (n[i], n[i]) fp32 output, W_i^-1
+ *   slogdet   DEVICE buffer of 2 * count doubles: matrix i writes {sign_i, log|det W_i|}, sign in {-1, 0, +1}
+ * w, n and winv are HOST arrays (of device addresses, of sizes): they are copied by value into the kernel's argument block, no
+ * device table is allocated and a captured graph carries the addresses itself.  One workgroup per matrix: W_i widened to
+ * float64 in LDS, Gauss-Jordan elimination in place with partial (row) pivoting -- the largest |a| of the column, the LOWEST row
+ * on a tie -- entirely in float64; log|det| is the float64 sum of log|pivot| in pivot order, the sign the permutation's parity
+ * times the pivots' signs, W^-1 is rounded to fp32 once, at the store.  A pivot that is exactly 0: sign 0, log|det| = -inf and
+ * winv[i] all NaN; the other matrices of the launch are unaffected.  No atomics, fixed reduction trees: a matrix comes out bit
+ * for bit the same alone and in any batch.  Only the n[i] * n[i] words of winv[i] and the 2 * count doubles are written; winv[i]
+ * must not overlap any w[k].  Supported: 1 <= count <= RTTS_SW_FACTOR_MAX_COUNT (a model with more flows calls again), 1 <= n[i] <=
+ * RTTS_SW_FACTOR_MAX_N; anything else, or a null pointer, is rejected before any launch with a message that names the argument. */
+#define RTTS_SW_FACTOR_MAX_COUNT 16
+#define RTTS_SW_FACTOR_MAX_N 128
+int rtts_sw_inv1x1_factor(const float* const* w, const int* n, int count, float* const* winv, double* slogdet, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

@@ -55,6 +55,7 @@ class ConvPermJob(C.Structure):
 
 
 CONV_PERM_MAX_GROUP = 8
+SW_FACTOR_MAX_COUNT, SW_FACTOR_MAX_N = 16, 128      # RTTS_SW_FACTOR_MAX_COUNT / _MAX_N of include/rtts.h
 
 # name -> argtypes, exactly the prototypes of include/rtts.h
 SIGNATURES = {
@@ -143,6 +144,7 @@ SIGNATURES = {
     "rtts_sw_boundary_bwd_blocks": [_i64],
     "rtts_sw_boundary_bwd": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _i32, _f32, _f32, _vp, _i64, _vp, _i64, _vp, _vp,
                              _vp],
+    "rtts_sw_inv1x1_factor": [C.POINTER(_vp), C.POINTER(_i32), _i32, C.POINTER(_vp), _vp, _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],

@@ -3,6 +3,7 @@ pointers and the current HIP stream handed to librtts_hip.so.  PyTorch is used f
 device memory and streams only."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional, Tuple
 
 import torch
@@ -244,3 +245,33 @@ def resample(audio: torch.Tensor, in_offsets_host, out_offsets_host, offsets: to
               out.data_ptr(), _stream())
     TIMING.stop(ev, 2.0 * taps * out_offsets_host[nseg])
     return out
+
+
+def sw_inv1x1_factor(weights) -> Tuple[list, torch.Tensor]:
+    """The invertible 1x1 convolutions of a SqueezeWave factored on the device: ``weights`` = CUDA float32 (n, n) contiguous
+    matrices, 1 <= n <= 128 -> (their inverses, fp32 rounded once from the float64 elimination; slogdet (len, 2) float64 on the
+    device = {sign, log|det|} per matrix, sign 0 / -inf / an all-NaN inverse for a singular one).  One ``rtts_sw_inv1x1_factor``
+    launch per 16 matrices on the current stream; nothing is read back and no table is copied to the device (the addresses
+    travel in the kernel's argument block), so the call can be captured into a graph."""
+    weights = list(weights)
+    if not weights:
+        raise ValueError("sw_inv1x1_factor: no matrices")
+    for i, w in enumerate(weights):
+        if not (torch.is_tensor(w) and w.is_cuda and w.dtype == torch.float32):
+            raise _lib.RttsError(f"sw_inv1x1_factor runs on the GPU only: weights[{i}] must be a CUDA float32 tensor "
+                                 f"(got {getattr(w, 'dtype', type(w).__name__)} on {getattr(w, 'device', 'the host')})")
+        if not (w.dim() == 2 and w.shape[0] == w.shape[1] and w.is_contiguous()):
+            raise ValueError(f"sw_inv1x1_factor: weights[{i}] must be a contiguous square matrix (got {tuple(w.shape)})")
+    dev = weights[0].device
+    for i, w in enumerate(weights):
+        if w.device != dev:
+            raise ValueError(f"sw_inv1x1_factor: weights[{i}] is on {w.device}, weights[0] on {dev}: one launch, one device")
+    inv = [torch.empty_like(w) for w in weights]
+    slogdet = torch.empty(len(weights), 2, dtype=torch.float64, device=dev)
+    step = _lib.SW_FACTOR_MAX_COUNT
+    for lo in range(0, len(weights), step):
+        ws, outs = weights[lo:lo + step], inv[lo:lo + step]
+        cnt = len(ws)
+        _lib.call("rtts_sw_inv1x1_factor", (C.c_void_p * cnt)(*[w.data_ptr() for w in ws]), (C.c_int * cnt)(*[w.shape[0] for w in ws]), cnt,
+                  (C.c_void_p * cnt)(*[o.data_ptr() for o in outs]), slogdet[lo:].data_ptr(), _stream())
+    return inv, slogdet

@@ -28,7 +28,9 @@ Training (``LitSqueezeWave``, ``training/wrappers.py:327-418``): ``nll_backward`
 blocks -- the same ``walk``, given batch-statistics depthwise taps and a stash that keeps every layer's activations -- and walks
 it backwards -- ``rtts_sw_boundary_bwd`` per flow boundary, ``rtts_sw_gate_bwd`` and ``rtts_sw_dwbn_bwd_sums`` / ``_apply`` per
 layer, ``rtts_gemm_nt`` (input gradients) and ``rtts_gemm_tn`` (weight gradients) for every 1x1 convolution -- adding the loss's
-gradient into every parameter's ``.grad``.
+gradient into every parameter's ``.grad``.  With ``logdet="device"`` the inverses and log-determinants of the 1x1 convolutions come
+from ``rtts_sw_inv1x1_factor`` (csrc/sw_lu.hip) instead of the host's LAPACK: the step then touches the host nowhere, and
+``VocoderTrainer.capture`` replays it as one hipGraph.
 
 There is no CPU fallback: ``infer`` and ``forward`` raise off the GPU."""
 from __future__ import annotations
@@ -38,7 +40,7 @@ from typing import List, Optional
 import torch
 from torch import nn
 
-from .. import _lib
+from .. import _lib, ops
 from .._graphs import warm_capture
 from ..edges import _ws
 from ..engine import _WS, _slab_ws, gemm
@@ -536,22 +538,35 @@ class SqueezeWave(nn.Module):
     def return_early(self, flow: int) -> bool:
         return flow % self.early_return_interval == 0 and flow > 0
 
-    def _fold(self, fold_bn: bool = True):
+    def _fold(self, fold_bn: bool = True, logdet: str = "host"):
         """``fold_bn=False`` (a training step): the GEMM operands only, built anew and not kept as the inference fold -- the step
-        changes the parameters and the running statistics anyway."""
+        changes the parameters and the running statistics anyway.  ``logdet="device"`` (training folds only): the inverses and
+        log-determinants of the 1x1 convolutions come from ``rtts_sw_inv1x1_factor`` -- ``_winv`` and ``_slogdet_dev`` (n_flows, 2)
+        float64 = {sign, log|det|}, both on the device, no host read and no synchronisation; the host values (``_slogdet``) are
+        dropped, whoever needs them folds on the host again."""
+        if logdet not in ("host", "device"):
+            raise ValueError(f"logdet must be 'host' or 'device' (got {logdet!r})")
+        if logdet == "device" and fold_bn:
+            raise ValueError("logdet='device' is the training fold's (fold_bn=False); inference and the eval likelihood factor on the host")
         key = tuple((p.data_ptr(), p._version) for p in self.parameters()) + tuple((b.data_ptr(), b._version) for b in self.buffers())
         if self._folded is None or self._folded_key != key or not fold_bn:
             with torch.no_grad():
                 self._folded = [_FoldedWN(wn, fold_bn) for wn in self.wn_layers]
-                # twelve matrices of at most 128 x 128, once per parameter version: inverted on the host in float64 (LAPACK) -- no
-                # device library (rocSOLVER / hipBLAS) call anywhere in the vocoder
-                dev = self.inv_conv_layers[0].conv.weight.device
-                w64 = [conv.conv.weight.detach().squeeze(-1).double().cpu() for conv in self.inv_conv_layers]
-                self._winv = [w.inverse().float().contiguous().to(dev) for w in w64]
-                # the forward direction: W itself (fp32, as the reference's conv applies it) and log det W in float64 on the
-                # host (modules.py:63 computes it per call in fp32); (sign, log|det|) per flow, judged where it is used
+                # the forward direction: W itself (fp32, as the reference's conv applies it)
                 self._wfwd = [conv.conv.weight.detach().squeeze(-1).float().contiguous() for conv in self.inv_conv_layers]
-                self._slogdet = [tuple(float(v) for v in torch.linalg.slogdet(w)) for w in w64]
+                if logdet == "device":
+                    # one launch, float64 Gauss-Jordan in LDS (csrc/sw_lu.hip); the signs are judged by check_determinants()
+                    self._winv, self._slogdet_dev = ops.sw_inv1x1_factor(self._wfwd)
+                    self._slogdet = None
+                else:
+                    # twelve matrices of at most 128 x 128, once per parameter version: inverted on the host in float64 (LAPACK) -- no
+                    # device library (rocSOLVER / hipBLAS) call anywhere in the vocoder
+                    dev = self.inv_conv_layers[0].conv.weight.device
+                    w64 = [conv.conv.weight.detach().squeeze(-1).double().cpu() for conv in self.inv_conv_layers]
+                    self._winv = [w.inverse().float().contiguous().to(dev) for w in w64]
+                    # log det W in float64 on the host (modules.py:63 computes it per call in fp32); (sign, log|det|) per flow,
+                    # judged where it is used
+                    self._slogdet = [tuple(float(v) for v in torch.linalg.slogdet(w)) for w in w64]
             self._folded_key = key if fold_bn else None
         return self._folded
 
@@ -755,6 +770,24 @@ class SqueezeWave(nn.Module):
                                  "has no likelihood (the reference's torch.logdet would return NaN or -inf)")
         return [v for _, v in self._slogdet]
 
+    def _logdet_dev(self) -> torch.Tensor:
+        """sum_k log det W_k of the last device fold as a device float64 scalar, after ``torch.logdet`` (modules.py:63): NaN for a
+        negative determinant, -inf for a singular W (the kernel's log|det|).  No host value goes in or comes out."""
+        sign, logabs = self._slogdet_dev[:, 0], self._slogdet_dev[:, 1]
+        return torch.where(sign < 0, float("nan"), logabs).sum()
+
+    def check_determinants(self) -> None:
+        """Judge the determinants of the last device-mode fold (``nll_backward(logdet="device")``, a replay of
+        ``VocoderTrainer.capture``): ONE device -> host read of n_flows x 2 doubles, at a time the caller chooses -- the step
+        itself raises nothing and returns a non-finite loss.  Raises what the host path raises at fold time."""
+        sd = getattr(self, "_slogdet_dev", None)
+        if sd is None:
+            raise _lib.RttsError("SqueezeWave.check_determinants: no device-mode fold yet (run nll_backward(logdet='device') first)")
+        for k, sign in enumerate(sd[:, 0].cpu().tolist()):
+            if sign <= 0:
+                raise ValueError(f"inv_conv_layers.{k}: det W is {'zero' if sign == 0 else 'negative'}: log det W is undefined, the flow "
+                                 "has no likelihood (the reference's torch.logdet would return NaN or -inf)")
+
     def _likelihood_device(self, what: str) -> torch.device:
         dev = self._device(what)
         if self.training:
@@ -832,11 +865,12 @@ class SqueezeWave(nn.Module):
         ld = torch.tensor([b * length * v for v in logdet], dtype=torch.float64).to(torch.float32).to(dev)
         return z.view(b, length, -1).permute(0, 2, 1), log_s, list(ld.unbind(0))
 
-    def _nll_from_sums(self, sums: torch.Tensor, nrows: torch.Tensor, sigma: float, logdet: List[float]):
+    def _nll_from_sums(self, sums: torch.Tensor, nrows: torch.Tensor, sigma: float, logdet):
         """``loss.py:21-31`` from the per-utterance sums: sums (n, 2) float64 = {sum z^2, sum log_s}, nrows (n,) float64 = audio
-        rows per utterance -> (per-utterance loss (n,) fp32: 0 / 0 = NaN for an empty one, loss of the whole batch 0-dim fp32)."""
+        rows per utterance, ``logdet`` = log det W of every flow as host floats, or their sum as a device float64 scalar
+        (``_logdet_dev``) -> (per-utterance loss (n,) fp32: 0 / 0 = NaN for an empty one, loss of the whole batch 0-dim fp32)."""
         c = self.n_audio_channels
-        num = sums[:, 0] / (2.0 * float(sigma) ** 2) - sums[:, 1] - nrows * sum(logdet)
+        num = sums[:, 0] / (2.0 * float(sigma) ** 2) - sums[:, 1] - nrows * (logdet if torch.is_tensor(logdet) else sum(logdet))
         return (num / (nrows * c)).float(), (num.sum() / (nrows.sum() * c)).float()
 
     def _reduce(self, z: torch.Tensor, ls_row: torch.Tensor, seg: _Segments) -> torch.Tensor:
@@ -872,7 +906,8 @@ class SqueezeWave(nn.Module):
                                      "tiles (weight-gradient GEMM and column sums); inference and the likelihood take it")
 
     @torch.no_grad()
-    def nll_backward(self, mel: torch.Tensor, audio: torch.Tensor, sigma: float = 1.0, _after_forward=None) -> torch.Tensor:
+    def nll_backward(self, mel: torch.Tensor, audio: torch.Tensor, sigma: float = 1.0, logdet: str = "host",
+                     _after_forward=None) -> torch.Tensor:
         """One forward + backward of the reference's training step (``training/wrappers.py:350-359``): the loss
         ``SqueezeWaveLoss(sigma)(self((mel, audio)))`` with the BatchNorms in training mode (``modules.py:100-117``: batch
         statistics over the B * L rows), mel (B, n_mel, Lm) and audio (B, 256 * Lm) on the device -> the loss (0-dim fp32 on the
@@ -881,7 +916,11 @@ class SqueezeWave(nn.Module):
         unbiased variance).  Uniform batches only; the model must be in ``.train()``.
 
         Every layer's activations are kept for the backward (no recomputation through the inverse flow).  ``log det W_k`` and
-        ``W_k^-T`` come from ``_fold`` (host float64, one small device -> host copy per parameter version, i.e. per step).
+        ``W_k^-T`` come from ``_fold``: with ``logdet="host"`` from float64 LAPACK on the host (one small device -> host copy per
+        parameter version, i.e. per step; a determinant that is not positive raises before anything is launched); with
+        ``logdet="device"`` from ``rtts_sw_inv1x1_factor`` -- the step then reads nothing back, copies no computed value to the
+        device and can be captured into a graph.  There log det W follows ``torch.logdet`` (NaN for a negative determinant, -inf
+        for a singular W): the loss of such a step is not finite, nothing is raised, ``check_determinants()`` tells which flow.
         ``n_channels`` that the MFMA forward takes but the backward does not tile (64, 192, 320, ...: anything outside
         ``TRAIN_WIDTHS``) are refused.  ``_after_forward`` (measurement only): called once between the forward and the backward."""
         self._train_widths()
@@ -891,8 +930,8 @@ class SqueezeWave(nn.Module):
                                  "batch-statistics BatchNorm; nll scores in eval mode")
         if any(p.dtype != torch.float32 for p in self.parameters()):
             raise _lib.RttsError("SqueezeWave.nll_backward: the parameters must be fp32 (they are the optimiser's master weights)")
-        folded = self._fold(fold_bn=False)
-        logdet = self._checked_logdets()
+        folded = self._fold(fold_bn=False, logdet=logdet)
+        logdet = self._logdet_dev() if logdet == "device" else self._checked_logdets()
         mel_rows, audio_rows, seg, _, _ = self._uniform_rows(mel, audio, dev, "nll_backward")
         try:
             return self._train_step(folded, logdet, mel_rows, audio_rows, seg, float(sigma), _after_forward)

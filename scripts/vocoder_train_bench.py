@@ -8,7 +8,15 @@ After a warm-up, device-event timings over a window of at least ``--seconds``: t
 (weight norm, bf16 casts, padding, and the host float64 log-determinants / inverses of the twelve W_k with their device -> host
 copy), forward, backward and Adam.  Next to it ``model.nll`` at the same shape in eval mode (the forward-only yardstick), the
 algorithmic GEMM FLOP of a step computed from the shapes with the rate they reach over the step, and the launches of a step.
-There is no pass / fail threshold: the numbers are recorded."""
+There is no pass / fail threshold: the numbers are recorded.
+
+    python scripts/vocoder_train_bench.py --graph > profiles/vocoder_train_graph_bench.json
+
+``--graph``: three variants of the step in ONE process, interleaved round by round (each round times one step of each, so a
+drift of the box hits all three alike) -- the eager step with the host float64 factorisation (``VocoderTrainer(model)``), the
+eager step with the device factorisation (``logdet="device"``), and the replay of ``VocoderTrainer.capture`` -- each on a model of
+its own from the same seed, plus ``rtts_sw_inv1x1_factor`` alone on the twelve W_k of the model.  Medians and ranges are
+recorded; the replay is expected not to be slower than the host-mode eager step of the same run, and the JSON says whether it was."""
 import argparse
 import json
 import os
@@ -38,13 +46,91 @@ def gemm_flop(model: SqueezeWave, b: int, mel_len: int) -> float:
     return total
 
 
+def _model(dev):
+    torch.manual_seed(0)
+    model = SqueezeWave(12, 128, 80, 2, 16, WNConfig(8, 256, 3, 2)).to(dev)
+    for wn in model.wn_layers:                      # the reference starts end_conv at zero; a trained one is not
+        wn.end_conv.weight.data.normal_(0, 0.01)
+    return model.train()
+
+
+def graph_bench(args):
+    from reformer_tts_amd import ops
+    dev = torch.device("cuda:0")
+    b, lm = args.batch, args.mel_len
+    models = {k: _model(dev) for k in ("eager_host", "eager_device", "graph_replay")}
+    torch.manual_seed(1)
+    batch = {"spectrogram": torch.randn(b, 80, lm, device=dev), "audio": 0.1 * torch.randn(b, 256 * lm, device=dev)}
+    host_t = VocoderTrainer(models["eager_host"])
+    dev_t = VocoderTrainer(models["eager_device"], logdet="device")
+    graph_t = VocoderTrainer(models["graph_replay"], logdet="device")
+    run = graph_t.capture(b, lm)
+    steps = {"eager_host": lambda: host_t.training_step(batch), "eager_device": lambda: dev_t.training_step(batch),
+             "graph_replay": lambda: run(batch)}
+    ev = lambda: torch.cuda.Event(enable_timing=True)     # noqa: E731
+
+    def timed(fn):
+        a, z = ev(), ev()
+        t0 = time.perf_counter()
+        a.record()
+        loss = fn()
+        z.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(z), (time.perf_counter() - t0) * 1e3, float(loss)
+
+    losses = {k: [] for k in steps}
+    for _ in range(args.warmup):
+        for k, fn in steps.items():
+            losses[k].append(timed(fn)[2])
+    times, wall = {k: [] for k in steps}, {k: [] for k in steps}
+    t_end = time.perf_counter() + 3 * args.seconds
+    while time.perf_counter() < t_end or len(times["graph_replay"]) < 5:
+        for k, fn in steps.items():
+            t, w, loss = timed(fn)
+            times[k].append(t)
+            wall[k].append(w)
+            losses[k].append(loss)
+    graph_t.check_determinants()
+
+    # the factorisation alone: the twelve W_k of the model, one launch, device events around each launch
+    ws = [c.conv.weight.detach().squeeze(-1).contiguous() for c in models["eager_device"].inv_conv_layers]
+    for _ in range(5):
+        ops.sw_inv1x1_factor(ws)
+    lu_ms = []
+    for _ in range(50):
+        a, z = ev(), ev()
+        a.record()
+        ops.sw_inv1x1_factor(ws)
+        z.record()
+        torch.cuda.synchronize()
+        lu_ms.append(a.elapsed_time(z))
+
+    stat = lambda v: {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}     # noqa: E731
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(json.dumps({
+        "what": "VocoderTrainer step, default SqueezeWave configuration: eager host-mode, eager device-mode and the captured graph, "
+                "interleaved in one process (device events around each step; host_clock_* = host clock around the step and a synchronise)",
+        "device": torch.cuda.get_device_name(0), "batch": b, "mel_len": lm, "audio_rows": b * lm * 2, "rounds_timed": len(times["graph_replay"]),
+        **{k: stat(v) for k, v in times.items()},
+        **{"host_clock_" + k: stat(v) for k, v in wall.items()},
+        "replay_over_eager_host": round(med["graph_replay"] / med["eager_host"], 4),
+        "replay_not_slower_than_eager_host": bool(med["graph_replay"] <= med["eager_host"]),
+        "sw_inv1x1_factor_12_matrices": stat(lu_ms), "factor_sizes": [int(w.shape[0]) for w in ws],
+        "segments_per_second_graph_replay": round(b / (med["graph_replay"] * 1e-3), 1),
+        "loss_first": {k: v[0] for k, v in losses.items()}, "loss_last": {k: v[-1] for k, v in losses.items()},
+        "device_and_graph_losses_equal": losses["eager_device"] == losses["graph_replay"]}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=96)
     ap.add_argument("--mel-len", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=1.0)
+    ap.add_argument("--graph", action="store_true", help="time host-mode eager, device-mode eager and the captured step, interleaved")
     args = ap.parse_args()
+    if args.graph:
+        return graph_bench(args)
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     model = SqueezeWave(12, 128, 80, 2, 16, WNConfig(8, 256, 3, 2)).to(dev)
