@@ -606,6 +606,39 @@ int rtts_sw_boundary_bwd(const float* x, int64_t ld_x, const float* wn_out, int6
 #define RTTS_SW_FACTOR_MAX_COUNT 16
 #define RTTS_SW_FACTOR_MAX_N 128
 int rtts_sw_inv1x1_factor(const float* const* w, const int* n, int count, float* const* winv, double* slogdet, void* stream);
+/* One training batch drawn from a corpus that lives on the device (csrc/sw_corpus.hip): the fixed-length crop of
+ * SpectrogramToSpeechDataset.__getitem__ (reference dataset/interface.py:64-97) for each of the B slots of a batch, written as
+ * the rows the training step reads (training/wrappers.py:395-403 hands LitSqueezeWave.training_step the stacked crops), with the
+ * utterance and the hop chosen by the kernel: a replayed graph gets a fresh batch and the host does nothing.
+ *   audio           the utterances end to end, n_audio samples: in_format 0 = f32, 1 = int16 mono, scaled by 1 / 32768 as
+ *                   rtts_resample scales it (exact in f32)
+ *   sample_offsets  i64 (n_utt + 1), as rtts_mel_spectrogram takes them: utterance u is samples [so[u], so[u+1]), N = their count
+ *   mel, ld_mel, frame_offsets   f32 (n_mel, ld_mel) rows and i64 (n_utt + 1) offsets, exactly what rtts_mel_spectrogram wrote:
+ *                   utterance u owns columns [fo[u], fo[u+1]), T_u = fo[u+1] - fo[u]
+ *   order           i32 (n_order): the epoch's utterance order;  state  i64[2] = {cursor, epoch_seed}, only read;  seed: host word
+ *   picks_in        i32 (B, 2) = {utterance, hop} per slot, or NULL.  Given, it replaces the draw (tests, validation, replaying a
+ *                   recorded batch) and order / state may be NULL
+ *   B, seg_frames, hop, C   the batch, the crop in mel frames, samples per frame, n_audio_channels; S = seg_frames * hop samples
+ * The draw of slot b: i = cursor + b, u = order[i mod n_order]; if N >= S: max_hop = (N - S) / hop and
+ *     h = (uint64(rtts_drop_hash(seed + uint32(epoch_seed), uint32(i))) * (max_hop + 1)) >> 32      (max_hop < 2^31)
+ * else h = 0 -- a multiply-shift, not a modulo: no rejection loop, bias below (max_hop + 1) / 2^32.  Then, for j < S, t < seg_frames,
+ * m < n_mel:
+ *     audio_rows[b * S + j]                                = h * hop + j < N ? audio[so[u] + h * hop + j] : 0
+ *     mel_rows[(b * seg_frames + t) * ld_mel_rows + m]     = h + t < T_u ? mel[m * ld_mel + fo[u] + h + t] : 0
+ * which is the reference's crop for N >= S (every read in range) and its zero padding of audio AND mel for N < S (zeros, not
+ * log(clip): torch.nn.functional.pad(..., 'constant')).  audio_rows: f32, B * S contiguous = the (B * S / C, C) rows of the
+ * training step; mel_rows: f32 (B * seg_frames, ld_mel_rows) channels-last, columns past n_mel are not touched;
+ * picks_out: i32 (B, 2) = the {u, h} used.
+ * Every read is held to the utterance's own bounds.  u outside [0, n_utt) -- from order or from picks_in --, a negative hop, or
+ * offsets of u that decrease or leave [0, n_audio] / [0, ld_mel], write an all-zero segment and picks_out[b] = {-1, 0}: a bad
+ * table entry never becomes a read out of bounds.  No atomics; the kernel writes no word that it reads (the caller advances
+ * the cursor with a separate stream-ordered add), so the output depends on the arguments alone.
+ * Supported: B in 1..65535, seg_frames, hop, C >= 1 with S % C == 0, 1 <= n_mel <= 128, ld_mel_rows >= n_mel, n_utt >= 1, and
+ * n_order >= 1 when the batch is drawn; anything else, or a null pointer, is rejected before any launch by the argument's name. */
+int rtts_sw_draw_segments(const void* audio, int in_format, int64_t n_audio, const int64_t* sample_offsets, const float* mel,
+                          int64_t ld_mel, const int64_t* frame_offsets, int n_utt, const int32_t* order, int n_order,
+                          const int64_t* state, uint32_t seed, const int32_t* picks_in, int B, int seg_frames, int hop, int C,
+                          int n_mel, float* audio_rows, float* mel_rows, int64_t ld_mel_rows, int32_t* picks_out, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

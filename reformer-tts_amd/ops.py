@@ -275,3 +275,49 @@ def sw_inv1x1_factor(weights) -> Tuple[list, torch.Tensor]:
         _lib.call("rtts_sw_inv1x1_factor", (C.c_void_p * cnt)(*[w.data_ptr() for w in ws]), (C.c_int * cnt)(*[w.shape[0] for w in ws]), cnt,
                   (C.c_void_p * cnt)(*[o.data_ptr() for o in outs]), slogdet[lo:].data_ptr(), _stream())
     return inv, slogdet
+
+
+def sw_draw_segments(audio: torch.Tensor, sample_offsets: torch.Tensor, mel: torch.Tensor, frame_offsets: torch.Tensor,
+                     order: Optional[torch.Tensor], state: Optional[torch.Tensor], seed: int, picks_in: Optional[torch.Tensor],
+                     batch: int, seg_frames: int, hop: int, n_audio_channels: int, audio_rows: torch.Tensor, mel_rows: torch.Tensor,
+                     picks_out: torch.Tensor):
+    """One vocoder training batch drawn from a device-resident corpus (``rtts_sw_draw_segments``): audio = the utterances end to
+    end, flat f32 or int16; sample_offsets / frame_offsets int64 (n_utt + 1,); mel f32 (n_mel, frames) rows as
+    ``rtts_mel_spectrogram`` writes them; order int32 (n_order,) and state int64 (2,) = {cursor, epoch_seed}, or picks_in int32
+    (batch, 2) = {utterance, hop} in their place -> audio_rows f32 (batch * seg_frames * hop / C, C), mel_rows f32
+    (batch * seg_frames, >= n_mel) channels-last, picks_out int32 (batch, 2).  All on one device; one launch on the current
+    stream, nothing read back, so the call can be captured into a graph."""
+    named = (("audio", audio, (torch.float32, torch.int16)), ("sample_offsets", sample_offsets, (torch.int64,)), ("mel", mel, (torch.float32,)),
+             ("frame_offsets", frame_offsets, (torch.int64,)), ("order", order, (torch.int32,)), ("state", state, (torch.int64,)),
+             ("picks_in", picks_in, (torch.int32,)), ("audio_rows", audio_rows, (torch.float32,)), ("mel_rows", mel_rows, (torch.float32,)),
+             ("picks_out", picks_out, (torch.int32,)))
+    dev = audio.device if torch.is_tensor(audio) else None
+    for name, t, dts in named:
+        if t is None and name in ("order", "state", "picks_in"):
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype in dts and t.device == dev):
+            raise _lib.RttsError(f"sw_draw_segments runs on the GPU only: {name} must be a CUDA {' or '.join(str(d) for d in dts)} tensor on "
+                                 f"{dev} (got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+    if picks_in is None and (order is None or state is None):
+        raise ValueError("sw_draw_segments: a drawn batch needs order and state (or give picks_in)")
+    n_utt = sample_offsets.numel() - 1
+    s = seg_frames * hop
+    if not (audio.dim() == 1 and audio.is_contiguous() and sample_offsets.dim() == 1 and sample_offsets.is_contiguous() and n_utt >= 1
+            and tuple(frame_offsets.shape) == (n_utt + 1,) and frame_offsets.is_contiguous() and mel.dim() == 2 and mel.stride(1) == 1):
+        raise ValueError("sw_draw_segments: audio flat, sample_offsets and frame_offsets (n_utt + 1,), mel (n_mel, frames) rows")
+    n_mel = mel.shape[0]
+    if not ((order is None or (order.dim() == 1 and order.is_contiguous())) and (state is None or (tuple(state.shape) == (2,) and state.is_contiguous()))
+            and (picks_in is None or (tuple(picks_in.shape) == (batch, 2) and picks_in.is_contiguous()))
+            and tuple(picks_out.shape) == (batch, 2) and picks_out.is_contiguous()):
+        raise ValueError(f"sw_draw_segments: order (n_order,), state (2,), picks_in / picks_out ({batch}, 2), all contiguous")
+    if not (audio_rows.is_contiguous() and audio_rows.numel() == batch * s and mel_rows.dim() == 2 and mel_rows.shape[0] == batch * seg_frames
+            and mel_rows.shape[1] >= n_mel and mel_rows.stride(1) == 1):
+        raise ValueError(f"sw_draw_segments: audio_rows holds {audio_rows.numel()} values for {batch} x {s} samples, mel_rows is "
+                         f"{tuple(mel_rows.shape)} for ({batch * seg_frames}, >= {n_mel})")
+    ev = TIMING.start("rtts_sw_draw_segments")
+    _lib.call("rtts_sw_draw_segments", audio.data_ptr(), 0 if audio.dtype == torch.float32 else 1, audio.numel(), sample_offsets.data_ptr(),
+              mel.data_ptr(), mel.stride(0), frame_offsets.data_ptr(), n_utt, _ptr(order), 0 if order is None else order.numel(), _ptr(state),
+              int(seed) & 0xFFFFFFFF, _ptr(picks_in), batch, seg_frames, hop, n_audio_channels, n_mel, audio_rows.data_ptr(), mel_rows.data_ptr(),
+              mel_rows.stride(0), picks_out.data_ptr(), _stream())
+    TIMING.stop(ev, 0.0)
+    return audio_rows, mel_rows, picks_out

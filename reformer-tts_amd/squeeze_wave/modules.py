@@ -923,6 +923,30 @@ class SqueezeWave(nn.Module):
         for a singular W): the loss of such a step is not finite, nothing is raised, ``check_determinants()`` tells which flow.
         ``n_channels`` that the MFMA forward takes but the backward does not tile (64, 192, 320, ...: anything outside
         ``TRAIN_WIDTHS``) are refused.  ``_after_forward`` (measurement only): called once between the forward and the backward."""
+        return self._nll_backward(lambda dev: self._uniform_rows(mel, audio, dev, "nll_backward")[:3], sigma, logdet, _after_forward)
+
+    @torch.no_grad()
+    def nll_backward_rows(self, mel_rows: torch.Tensor, audio_rows: torch.Tensor, batch: int, mel_len: int, sigma: float = 1.0,
+                          logdet: str = "host", _after_forward=None) -> torch.Tensor:
+        """``nll_backward`` for a batch that already is in the step's row layout: mel_rows fp32 (batch * mel_len, n_mel)
+        channels-last and audio_rows fp32 (batch * 256 * mel_len / n_audio_channels, n_audio_channels), both contiguous on the
+        device -- what ``nll_backward`` makes of (mel, audio) with a permute and a copy, and what ``rtts_sw_draw_segments`` writes
+        directly.  Everything else is ``nll_backward``: same launches, same gradients bit for bit for the same rows."""
+        batch, mel_len = int(batch), int(mel_len)
+
+        def rows_of(dev):
+            up, c = self._up(), self.n_audio_channels
+            for name, t, shape in (("mel_rows", mel_rows, (batch * mel_len, self._n_mel())), ("audio_rows", audio_rows, (batch * up * mel_len, c))):
+                self._on_device(t, dev, "nll_backward_rows", name)
+                if batch < 1 or mel_len < 1 or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"SqueezeWave.nll_backward_rows: {name} must be contiguous fp32 {shape} for batch {batch}, mel_len {mel_len} "
+                                     f"(got {t.dtype} {tuple(t.shape)})")
+            return mel_rows, audio_rows, _Segments.uniform(batch, mel_len, up)
+        return self._nll_backward(rows_of, sigma, logdet, _after_forward)
+
+    def _nll_backward(self, rows_of, sigma: float, logdet: str, after_forward) -> torch.Tensor:
+        """The body of ``nll_backward``: ``rows_of(dev)`` -> (mel rows, audio rows, segments), called once the model has been checked and
+        folded."""
         self._train_widths()
         dev = self._device("nll_backward")
         if not self.training:
@@ -932,9 +956,9 @@ class SqueezeWave(nn.Module):
             raise _lib.RttsError("SqueezeWave.nll_backward: the parameters must be fp32 (they are the optimiser's master weights)")
         folded = self._fold(fold_bn=False, logdet=logdet)
         logdet = self._logdet_dev() if logdet == "device" else self._checked_logdets()
-        mel_rows, audio_rows, seg, _, _ = self._uniform_rows(mel, audio, dev, "nll_backward")
+        mel_rows, audio_rows, seg = rows_of(dev)
         try:
-            return self._train_step(folded, logdet, mel_rows, audio_rows, seg, float(sigma), _after_forward)
+            return self._train_step(folded, logdet, mel_rows, audio_rows, seg, float(sigma), after_forward)
         finally:
             self._folded, self._folded_key = None, None      # not an inference fold, and the running statistics changed in place
 
