@@ -64,6 +64,20 @@ int rtts_lsh_hash_sort(const void* qk, int64_t ld_qk, const float* rotations, in
  * workgroup per (head, round)) for short sequences.  Same results bit for bit. */
 int rtts_lsh_hash_sort_launches(int T);
 
+/* The same stages of HuggingFace's LSHSelfAttention (implementation="huggingface_transformers"): replaces
+ * `buckets = self._hash_vectors(...)` and `self._get_sorted_bucket_idx_and_undo_sorted_bucket_idx(...)` of transformers'
+ * models/reformer/modeling_reformer.py (LSHSelfAttention.forward), the layer built at reformer_tts/model/reformer.py:202-213
+ * and called at :219.
+ *   rotations f32 (H, dh, n_hashes, n_buckets/2): per head, shared over the batch (row = bh % H)
+ *   mask      u8 (B,T) 1 = valid, or NULL.  With a mask, masked tokens take the extra bucket n_buckets and round r is
+ *             offset by r * (n_buckets + 1) (the stride does not change the sorted order, so it is used whenever a mask is
+ *             given, whether it hides a token or not); without one the offset is r * n_buckets
+ *   n_buckets even, 2 .. 256, independent of T / chunk; T % chunk == 0, T % 128 == 0, dh == 64
+ *   buckets / st / undo as above.  Same k-ordered fp32 fmaf chain: tests/hf_lsh_ref.py reproduces the buckets bit for bit. */
+int rtts_lsh_hash_sort_hf(const void* qk, int64_t ld_qk, const float* rotations, const uint8_t* mask,
+                          int B, int H, int T, int dh, int n_hashes, int chunk, int n_buckets,
+                          int32_t* buckets, int32_t* st, int32_t* undo, void* stream);
+
 /* ---- LSH attention: chunked attention forward (Appendix B steps 4-10) ----------------
  *   qk, v  bf16 rows as above (common stride ld)
  *   mask   u8 (B,T) 1 = valid token, or NULL

@@ -719,6 +719,10 @@ class LSHExec:
     def __init__(self, withnorm):
         self.norm = withnorm.norm
         self.layer: LSHSelfAttention = withnorm.fn.layer
+        # HuggingFace's layer (model/hf_lsh_attention.py): its own hash, query_key | value in place of toqk | tov, and NO output
+        # projection -- f(x) is the attention output itself: it enters the residual add without a bias, the stream gradient IS
+        # the gradient of the attention output, and delta comes from rtts_lsh_bwd_delta
+        self.hf = bool(getattr(self.layer, "hf", False))
         # What a forward leaves for ITS backward lives in a per-call slot (a dict owned by FusedStackFn's ctx), never on the
         # executor: a second forward before the first backward (two losses, an eval forward in between, two models sharing
         # layers) must not hand the first backward the second forward's permutation / stash / dropout seed.  Keys:
@@ -732,16 +736,25 @@ class LSHExec:
         # rtts_gemm_nt launches: K = d and N = d, 2d must be multiples of its 64-wide stages / tiles
         return withnorm.fn.layer.dim % 64 == 0
 
-    def _wqkv(self):
+    def _qk_v(self):
+        """The two projection parameters: toqk / tov, or query_key / value of the HuggingFace layer (``self.hf``)."""
         lyr = self.layer
-        a, b = _bf16(lyr.toqk.weight), _bf16(lyr.tov.weight)
+        return (lyr.query_key.weight, lyr.value.weight) if self.hf else (lyr.toqk.weight, lyr.tov.weight)
+
+    def _wqkv(self, scaled: bool = True):
+        """(2d, d) bf16 [qk | v] weights.  HuggingFace layer, ``scaled``: the qk half times sqrt(dh) = 8 (exact in bf16), which
+        turns the kernels' logit q.k / (8 |k|) into that layer's q.k / |k| (model/hf_lsh_attention.py); its backward reads the
+        unscaled weights against the gradient of the scaled projection times 8."""
+        a, b = (_bf16(p) for p in self._qk_v())
+        if self.hf and scaled:
+            from .model.hf_lsh_attention import QK_SCALE
+            return torch.cat([a * QK_SCALE, b], dim=0)
         if _adjacent(a, b):                                        # neighbours in the flat mirror: zero-copy (2d, d) view
             return torch.as_strided(a, (2 * a.shape[0], a.shape[1]), (a.shape[1], 1))
         return torch.cat([a, b], dim=0)
 
     def _wqkv_grad(self):
-        lyr = self.layer
-        ga, gb = _grad(lyr.toqk.weight), _grad(lyr.tov.weight)
+        ga, gb = (_grad(p) for p in self._qk_v())
         if _adjacent(ga, gb):
             return torch.as_strided(ga, (2 * ga.shape[0], ga.shape[1]), (ga.shape[1], 1)), None
         return None, (ga, gb)
@@ -749,13 +762,17 @@ class LSHExec:
     def _internals(self, inp, b, t, mask, st, stash=None, g=None, pre=None, qkv=None, adrop=None):
         lyr = self.layer
         e = lyr.dim
-        if t <= lyr.full_attn_thres:
+        if self.hf:
+            lyr.check_length(t)
+        elif t <= lyr.full_attn_thres:
             raise NotImplementedError("full-attention shortcut (T <= full_attn_thres) is outside the HIP path")
         xn, mean, rstd = pre if pre is not None else ln_fwd(inp, self.norm)
         wqkv = self._wqkv()
         if qkv is None:
             qkv = gemm(xn, wqkv).view(b, t, 2 * e)
-        if st is None:
+        if st is None and self.hf:
+            st = lyr.hash_sort(qkv[..., :e], lyr._rotations(qkv, lyr.resolve_num_buckets(t)), mask)
+        elif st is None:
             rot = lyr._rotations(qkv, t // lyr.bucket_size)
             st, _, _ = ops.lsh_hash_sort(qkv[..., :e], rot, lyr.heads, lyr.bucket_size)
         lyr.last_st = st
@@ -765,7 +782,7 @@ class LSHExec:
             o, lse = ops.lsh_attn_fwd(qkv[..., :e], qkv[..., e:], st, lyr.heads, lyr.bucket_size, lyr.causal, mask, adrop)
             out, lse_tot = ops.lsh_combine_fwd(o, lse, b, lyr.heads)
         if g is None:
-            g = gemm(out.view(b * t, e), _bf16(lyr.to_out.weight))
+            g = out.view(b * t, e) if self.hf else gemm(out.view(b * t, e), _bf16(lyr.to_out.weight))
         return xn, mean, rstd, wqkv, qkv, st, out, lse_tot, g
 
     def forward(self, acc, inp, b, t, mask=None, pre=None, next_norm=None, slot=None, keep_streams=False, fresh_acc=False, **_):
@@ -774,11 +791,12 @@ class LSHExec:
         pa = getattr(self.layer, "dropout", 0.0) if self.layer.training else 0.0
         adrop = (pa, next_seed()) if pa > 0.0 else None
         xn, mean, rstd, _, qkv, st, out, lse_tot, g = self._internals(inp, b, t, mask, None, pre=pre, adrop=adrop)
-        p = self.layer.post_attn_dropout.p if self.layer.training else 0.0
+        p = self.layer.post_attn_dropout.p if (self.layer.training and not self.hf) else 0.0
         slot.clear()
         slot.update(st=st, stash=(out, lse_tot) if STASH_ATTENTION else None, g=g if STASH_BLOCK_OUTPUT else None,
                     qkv=qkv if STASH_PROJECTIONS else None, drop=(p, next_seed()) if p > 0.0 else None, adrop=adrop)
-        return residual(acc, g, self.layer.to_out.bias, 1.0, next_norm, slot["drop"], out=_keep_streams(keep_streams, slot, acc, inp, xn, mean, rstd, fresh_acc))
+        return residual(acc, g, None if self.hf else self.layer.to_out.bias, 1.0, next_norm, slot["drop"],
+                        out=_keep_streams(keep_streams, slot, acc, inp, xn, mean, rstd, fresh_acc))
 
     def backward(self, acc, inp, d_acc, d_inp, b, t, mask=None, pre=None, next_norm=None, pre_cast=None, next_cast=None, slot=None,
                  d_src=None, join=None, **_):
@@ -795,6 +813,18 @@ class LSHExec:
                                                                          _NO_G if kept else slot["g"], pre, slot["qkv"], adrop)
         drop = slot["drop"]
         slot.clear()
+        if self.hf:
+            post = None if kept else residual(acc, g, None, -1.0, next_norm, None)           # reconstruct the stream
+            dyb = pre_cast[0] if pre_cast is not None else cast_colsum(d_acc, None)          # no bias: the column sums are not taken
+            dqkv = torch.empty_like(qkv)
+            ops.lsh_attn_bwd(qkv[..., :e], qkv[..., e:], st, out, dyb.view(b, t, e), lse_tot, lyr.heads, lyr.bucket_size, lyr.causal, mask,
+                             dqkv=(dqkv[..., :e], dqkv[..., e:]), drop=adrop)
+            # d(8 qk) -> 8 d(8 qk): against the UNSCALED weights this is both the gradient of query_key.weight (x^T .) and the
+            # input gradient (. W); exact in bf16 (a power of two)
+            from .model.hf_lsh_attention import QK_SCALE
+            dqkv[..., :e].mul_(QK_SCALE)
+            wqkv = self._wqkv(scaled=False)
+            return post, self._projection_backward(dqkv.view(b * t, 2 * e), xn, wqkv, inp, mean, rstd, d_inp, next_cast, d_src, join)
         post = None if kept else residual(acc, g, lyr.to_out.bias, -1.0, next_norm, drop)   # reconstruct the stream (same dropout mask)
         dyb = _out_grad(d_acc, _grad(lyr.to_out.bias), drop, pre_cast)
         out2 = out.view(b * t, e)
@@ -808,17 +838,22 @@ class LSHExec:
         dqkv = torch.empty_like(qkv)
         ops.lsh_attn_bwd(qkv[..., :e], qkv[..., e:], st, out, dout, lse_tot, lyr.heads, lyr.bucket_size, lyr.causal, mask,
                          dqkv=(dqkv[..., :e], dqkv[..., e:]), drop=adrop, delta=delta)
-        dqkv2 = dqkv.view(b * t, 2 * e)
+        return post, self._projection_backward(dqkv.view(b * t, 2 * e), xn, wqkv, inp, mean, rstd, d_inp, next_cast, d_src, join)
+
+    def _projection_backward(self, dqkv2, xn, wqkv, inp, mean, rstd, d_inp, next_cast, d_src, join):
+        """Weight gradients of qk | v (ONE rtts_gemm_tn problem over the stacked gradient), input gradient, LayerNorm backward."""
+        e = self.layer.dim
         gview, pair = self._wqkv_grad()
         if gview is not None:
             wgrad(gview, dqkv2, xn)
         else:
-            _lib.note_general_path("weight gradient", "toqk / tov gradients are not neighbours in one buffer: library GEMM")
+            _lib.note_general_path("weight gradient", ("query_key / value" if self.hf else "toqk / tov") +
+                                   " gradients are not neighbours in one buffer: library GEMM")
             full = torch.mm(dqkv2.t(), xn, out_dtype=torch.float32)
             pair[0].add_(full[:e])
             pair[1].add_(full[e:])
         dxn = gemm(dqkv2, wqkv, kn=True)
-        return post, ln_bwd(dxn, inp, mean, rstd, self.norm, d_inp, next_cast, dx_in=d_src, join=join)
+        return ln_bwd(dxn, inp, mean, rstd, self.norm, d_inp, next_cast, dx_in=d_src, join=join)
 
 
 class FFNExec:

@@ -175,6 +175,16 @@ def baseline_model_config() -> ReformerTTSConfig:
         postnet_kwargs=dict(depth=2, dropout=0.1)))
 
 
+def huggingface_lsh_model_config() -> ReformerTTSConfig:
+    """``config/huggingface-lsh.yml`` model section resolved: the baseline with HuggingFace's LSH layer in both stacks."""
+    return model_config_from_dict(dict(
+        dict_size=76, num_mel_coeffs=80, scp_encoding_dropout=0.05, pad_base=256,
+        enc_prenet_kwargs=dict(dropout=0.05), dec_prenet_kwargs=dict(dropout=0.05),
+        enc_reformer_kwargs=dict(depth=3, attn_kwargs=dict(implementation="huggingface_transformers")),
+        dec_reformer_kwargs=dict(depth=3, self_attn_kwargs=dict(implementation="huggingface_transformers", bucket_size=128)),
+        postnet_kwargs=dict(depth=2, dropout=0.1)))
+
+
 def baseline_training_config() -> TTSTrainingConfig:
     return _merge(TTSTrainingConfig(), dict(batch_size=12, weight_decay=1e-7, accumulate_grad_batches=5,
                                             gradient_clip_val=1.0, warmup_steps=320))

@@ -153,6 +153,10 @@ class LSHSelfAttention(nn.Module):
 
     rotation_pool = None       # (flat fp32 normal samples, [next offset]) while a graph-mode training forward runs, else None
 
+    def _rotation_rows(self, x) -> int:
+        """Leading dimension of a drawn rotation tensor: one matrix for all heads, or one per (batch, head)."""
+        return x.shape[0] * self.heads if self.random_rotations_per_head else 1
+
     def _rotations(self, x, n_buckets, default_generator: bool = False):
         if self.forced_rotations is not None and hasattr(self.forced_rotations, "__next__"):
             return next(self.forced_rotations).to(device=x.device, dtype=torch.float32).contiguous()   # tests: one per call
@@ -165,7 +169,7 @@ class LSHSelfAttention(nn.Module):
             if self.forced_rotations.device != x.device or self.forced_rotations.dtype != torch.float32:
                 self.forced_rotations = self.forced_rotations.to(device=x.device, dtype=torch.float32).contiguous()
             return self.forced_rotations
-        rows = x.shape[0] * self.heads if self.random_rotations_per_head else 1
+        rows = self._rotation_rows(x)
         shape = (rows, self.dim // self.heads, self.n_hashes, n_buckets // 2)
         if default_generator or getattr(self, "use_default_generator", False):   # graph-safe, and what Deterministic replays
             pool = LSHSelfAttention.rotation_pool             # one randn per training step for all layers (trainer.forward_loss)

@@ -8,6 +8,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from .hf_lsh_attention import HFLSHSelfAttention
 from .lsh_attention import LSHSelfAttention
 from .modules import FeedForward
 from .reversible import ReversibleBlock, ReversibleHalfResidual, ReversibleSequence, ReversibleSwap
@@ -43,8 +44,9 @@ class Chunk(nn.Module):
 
 class LSHSelfAttentionWrapper(nn.Module):
     """``reformer.py:189-220``: picks the attention class by ``kwargs["implementation"]``.  This
-    package adds ``"hip"``; the reference's two values name third-party eager implementations that
-    are not part of it."""
+    package adds ``"hip"`` (``reformer_pytorch``'s arithmetic and parameter names in HIP) and provides
+    ``"huggingface_transformers"`` as ``HFLSHSelfAttention`` (HuggingFace's arithmetic and parameter names in HIP);
+    ``"reformer_pytorch"`` names the third-party eager implementation itself, which is not part of it."""
     accepts_recompute = True
 
     def __init__(self, dim: int, causal: bool, **kwargs):
@@ -52,10 +54,14 @@ class LSHSelfAttentionWrapper(nn.Module):
         assert "implementation" in kwargs
         assert kwargs["implementation"] in {"hip", "huggingface_transformers", "reformer_pytorch"}
         self.implementation = kwargs.pop("implementation")
+        if self.implementation == "huggingface_transformers":
+            # reformer.py:204-212 reads heads, n_hashes, dropout and bucket_size; every other knob is ignored on this branch
+            self.layer = HFLSHSelfAttention(dim, causal=causal, **kwargs)
+            return
         if self.implementation != "hip":
             raise NotImplementedError(
                 f"implementation={self.implementation!r} is the reference's eager third-party path; "
-                "this package provides implementation='hip'")
+                "this package provides implementation='hip' and 'huggingface_transformers'")
         self.layer = LSHSelfAttention(dim, causal=causal, **kwargs)
 
     def forward(self, x: torch.Tensor, input_mask: torch.Tensor = None, recompute: bool = False):

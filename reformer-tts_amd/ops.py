@@ -97,6 +97,30 @@ def lsh_hash_sort(qk: torch.Tensor, rotations: torch.Tensor, heads: int, bucket_
     return st, buckets, undo
 
 
+def lsh_hash_sort_hf(qk: torch.Tensor, rotations: torch.Tensor, heads: int, chunk: int, n_buckets: int,
+                     mask: Optional[torch.Tensor] = None, want_buckets: bool = False, want_undo: bool = False):
+    """HuggingFace's hash and sort: qk (B,T,H*dh) bf16, rotations (H, dh, R, n_buckets/2) f32 (per head, shared over the batch),
+    mask (B,T) 1 = valid or None -> st (B*H,R,T) i32 [, buckets, undo].  With a mask the masked tokens share bucket
+    ``n_buckets`` and the round offsets of ``buckets`` are r * (n_buckets + 1)."""
+    ld = _check_rows(qk, "qk")
+    b, t, d = qk.shape
+    dh = d // heads
+    if not (rotations.is_cuda and rotations.dtype == torch.float32 and rotations.is_contiguous() and rotations.dim() == 4):
+        raise ValueError("rotations: expected a contiguous CUDA float32 (heads, dh, n_hashes, n_buckets/2) tensor")
+    rows, rdh, n_hashes, half = rotations.shape
+    if rows != heads or rdh != dh or (2 * half != n_buckets and n_buckets % 2 == 0):
+        raise ValueError(f"rotations shape {tuple(rotations.shape)} does not match heads={heads}, dh={dh}, n_buckets={n_buckets}")
+    mask = _check_mask(mask, b, t, qk.device)
+    st = torch.empty(b * heads, n_hashes, t, dtype=torch.int32, device=qk.device)
+    buckets = torch.empty_like(st) if want_buckets else None
+    undo = torch.empty_like(st) if want_undo else None
+    ev = TIMING.start(f"rtts_lsh_hash_sort_hf/nb{n_buckets}")
+    _lib.call("rtts_lsh_hash_sort_hf", qk.data_ptr(), ld, rotations.data_ptr(), _ptr(mask), b, heads, t, dh, n_hashes, chunk, n_buckets,
+              _ptr(buckets), st.data_ptr(), _ptr(undo), _stream())
+    TIMING.stop(ev, float(b * heads * t) * (dh * 2 + n_hashes * 4 + n_hashes * 8))
+    return st, buckets, undo
+
+
 def _check_mask(mask: Optional[torch.Tensor], b: int, t: int, device) -> Optional[torch.Tensor]:
     if mask is None:
         return None

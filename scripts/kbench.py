@@ -101,6 +101,14 @@ def main():
         if not only or "hash" in only:
             us = timeit(lambda: ops.lsh_hash_sort(qk, rot, h, bs), args.iters)
             res["hash_sort"] = (us, f"{tok * (128 + nh * 4) / us / 1e3:8.1f} GB/s alg")
+            # HuggingFace's hash (rtts_lsh_hash_sort_hf) at the equal shape: the same bucket count, rotations per head, and with
+            # the validity mask (one more bin, the padding bucket)
+            nb = t // bs
+            rot_h = torch.randn(h, dh, nh, nb // 2, generator=torch.Generator().manual_seed(1)).to(dev)
+            us = timeit(lambda: ops.lsh_hash_sort_hf(qk, rot_h, h, bs, nb), args.iters)
+            res["hash_sort_hf"] = (us, f"{tok * (128 + nh * 4) / us / 1e3:8.1f} GB/s alg")
+            us = timeit(lambda: ops.lsh_hash_sort_hf(qk, rot_h, h, bs, nb, mask), args.iters)
+            res["hash_sort_hf+m"] = (us, f"{tok * (129 + nh * 4) / us / 1e3:8.1f} GB/s alg")
         if not only or "fwd" in only:
             us = timeit(lambda: ops.lsh_attn_fwd(qk, v, st, h, bs, causal, mask), args.iters)
             res["attn_fwd"] = (us, f"{2 * pair_flops / us / 1e6:8.1f} TFLOP/s")
