@@ -30,10 +30,18 @@
 //   2  PERSISTENT: problems of several tiles per CU (N >= 1024 at M = 12288) run on a grid of resident workgroups that walk the
 //      tiles; the LDS ring keeps turning across a tile boundary -- the first NST stages of the next tile are in flight while the
 //      current tile's accumulators are stored -- so the 1.8 us launch-to-first-stage latency is paid once per workgroup, not per tile.
+//   3  CONVOLUTION (conv_cpt > 0, where the images fit LDS; not 256 x 256): the input rows [m0 - 2, m0 + BM + 2) of all channel
+//      blocks stay in LDS, one image per 64-channel block, and the five taps read them at five row shifts -- the plain loop brings
+//      the same BM x 64 block of rows in once per tap.  K order and results are the plain loop's, bit for bit; the stages of taps
+//      1..4 ingest the weight tile only (8 of 24 KB on the 128 x 64 tile).  conv_taps.h holds the piece -> row arithmetic.
+//      MEASURED (profiles/conv_taps_ab.log, us per launch inside a replayed graph, plain loop -> this form): encoder prenet
+//      (M = 3328, 512 -> 512, 128 x 64) forward 30.0 -> 20.5, input gradient 33.3 -> 24.1; postnet 512 -> 128 forward 29.3 -> 20.2,
+//      128 -> 512 input gradient 33.2 -> 23.9.  The postnet's 512 -> 512 (256 x 128: 8 images of 33 KB do not fit) keeps the plain loop.
 // More epilogues: 4 with `accum` (fp32 C += result: the keys' gradient accumulates over the decoder layers without a separate add
 // launch) and 5 (input gradient of to_out / out_proj + delta = rowsum(out * dout) per (token, head) for the attention backward: the
 // separate rtts_lsh_bwd_delta launch and its re-read of dout are gone).
 #include "rtts_common.h"
+#include "conv_taps.h"
 #include <stdlib.h>
 #include <atomic>
 
@@ -264,7 +272,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     gn_v2i wl0[TN], wh0[TN], wl1[TN], wh1[TN];
     (void)w0; (void)w1; (void)wl0; (void)wh0; (void)wl1; (void)wh1;
     constexpr int RD_PER_KS = (W_KN ? 2 * TN : TN) + TM;
-#define GN_READ(AF, WF, WL, WH, sb_, KS)                                                                                   \
+#define GN_READ_W(WF, WL, WH, sb_, KS)                                                                                     \
     do {                                                                                                                   \
         if constexpr (!W_KN) {                                                                                             \
             const uint32_t aw_ = (sb_) + offW[KS];                                                                         \
@@ -277,6 +285,10 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
                 gn_rdtr<(32 * KS + 4) * RP>(WH[j], aw_);                                                                   \
             });                                                                                                            \
         }                                                                                                                  \
+    } while (0)
+#define GN_READ(AF, WF, WL, WH, sb_, KS)                                                                                   \
+    do {                                                                                                                   \
+        GN_READ_W(WF, WL, WH, sb_, KS);                                                                                    \
         const uint32_t aa_ = (sb_) + (KS ? offA1 : offA0);                                                                 \
         gn_static_for<0, TM>([&](auto ic) { constexpr int i = decltype(ic)::value; gn_rd128<i * 2048>(AF[i], aa_); });     \
     } while (0)
@@ -308,7 +320,10 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcW0 + (q - PA) * pstepW + kw_),
                                              (RTTS_LDS void*)(sb_ + A_BYTES + (wave + NW * (q - PA)) * 1024), 16, 0, 0);
     };
-#define GN_MFMA(AF, WF, WL, WH, COND_, ST_, BUF_, Q0, Q1)                                                                  \
+#define GN_MFMA(AF, WF, WL, WH, COND_, ST_, BUF_, Q0, Q1) \
+    GN_MFMA_I(AF, WF, WL, WH, COND_, [&](auto qc_) { issue_piece(qc_, (ST_), (BUF_)); }, GAP, Q0, Q1)
+    // (ISSUE_: what issues DMA piece q, called with q as an integral_constant; GAP_: MFMAs between two pieces)
+#define GN_MFMA_I(AF, WF, WL, WH, COND_, ISSUE_, GAP_, Q0, Q1)                                                             \
     do {                                                                                                                   \
         bf16x8 wfr_[TN], afr_[TM];                                                                                         \
         _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                                   \
@@ -324,9 +339,9 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
         gn_static_for<0, TM * TN>([&](auto xc) {                                                                           \
             constexpr int x = decltype(xc)::value, i = x / TN, j = x % TN;                                                 \
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfr_[j], afr_[i], acc[i][j], 0, 0, 0);                     \
-            if constexpr (x % GAP == GAP - 1 && (Q0) + x / GAP < (Q1)) {                                                   \
+            if constexpr (x % (GAP_) == (GAP_) - 1 && (Q0) + x / (GAP_) < (Q1)) {                                          \
                 __builtin_amdgcn_sched_barrier(0);                                                                         \
-                if (cond_) issue_piece(std::integral_constant<int, (Q0) + x / GAP>{}, (ST_), (BUF_));                      \
+                if (cond_) (ISSUE_)(std::integral_constant<int, (Q0) + x / (GAP_)>{});                                     \
                 __builtin_amdgcn_sched_barrier(0);                                                                         \
             }                                                                                                              \
         });                                                                                                                \
@@ -342,14 +357,16 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     } while (0)
     static_assert(NST >= 2 && NST <= 4 && 3 * PER <= 63, "ring depth");
 
-#pragma unroll
-    for (int i = 0; i < NST; ++i)
-        if (i < nk) GN_ISSUE(i, i);
-    GN_WAIT_STAGE(min(NST - 1, nk - 1));
-    asm volatile("s_barrier" ::: "memory");
-    GN_STAMP(1);
     const uint32_t smem_base = (uint32_t)(uintptr_t)(RTTS_LDS unsigned char*)smem;
-    GN_READ(a0, w0, wl0, wh0, smem_base, 0);
+    if constexpr (MODE != 3) {                       // (the convolution form has a prologue of its own, in front of its loop)
+#pragma unroll
+        for (int i = 0; i < NST; ++i)
+            if (i < nk) GN_ISSUE(i, i);
+        GN_WAIT_STAGE(min(NST - 1, nk - 1));
+        asm volatile("s_barrier" ::: "memory");
+    }
+    GN_STAMP(1);
+    if constexpr (MODE != 3) GN_READ(a0, w0, wl0, wh0, smem_base, 0);
     int buf = 0;
 #ifdef GN_ABL_NOLDS          // timing-only builds (scripts/gemm_nt_stamps.py): results are wrong by construction
 #undef GN_READ
@@ -382,6 +399,109 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
             nxtW = W_KN ? (int64_t)(n0n - n0) : (int64_t)(n0n - n0) * ldw;
         }
     }
+    if constexpr (MODE == 3) {
+        // ---- CONVOLUTION FORM (conv_cpt > 0, where gn_conv_fits()): the input rows [m0 - 2, m0 + BM + 2) of ALL conv_cpt channel
+        // blocks stay in LDS -- one image per channel block, conv_taps.h has the piece -> row arithmetic, checked on the CPU -- and the
+        // five taps read every image at five row shifts instead of fetching BM rows per tap.  K keeps the plain loop's order (stage s
+        // = tap s / cpt, channel block s % cpt; the weight offsets are w_off's), so every accumulator sees the same fp32 additions in
+        // the same order: the results are the plain loop's, bit for bit.  LDS: cpt images, then a ring of NST weight stages.
+        // The DMA group of stage X = its PW weight pieces + (X < cpt: the PAc pieces of image X), issued like the plain loop's groups
+        // (first SPBC pieces under the second burst of stage X - NST, the rest under the first burst of stage X - NST + 1); returns
+        // are in order, so the counted wait in front of stage X covers image X.  Behind tap 0 a stage ingests the weight tile only.
+        constexpr int IMG = gn_conv_image_bytes(BM), PAc = gn_conv_pa(BM, NW), TS = gn_conv_plain_pieces(BM, NW), NCL = PAc - TS;
+        constexpr int PERC = PW + PAc, SPBC = (PERC + 1) / 2, GAPC = (TM * TN) / SPBC > 0 ? (TM * TN) / SPBC : 1;
+        static_assert(gn_conv_family_ok(BM, NW) && NST == GN_CONV_NST && NST == 3 && NCL >= 0 && NCL <= 1, "convolution form: image / ring geometry");
+        static_assert(IMG >= A_BYTES && (IMG % 1024) == 0 && 2 * PERC <= 63, "convolution form: LDS layout, vmcnt range");
+        const int cpt = conv_cpt;
+        const bool fwd = P.conv_sign > 0;
+        const uint32_t wbase = (uint32_t)cpt * IMG;                  // the weight ring lies behind the images
+        // A source of this lane: image row j0 = 8 wave + (lane >> 3) of piece 0 is input row m0 - 2 + j0.  Piece t < TS lies 8 NW t
+        // rows further on (the swizzle key depends on lane >> 3 alone); the last piece of a wave may reach image rows the tile never
+        // reads, or repeat the image's last piece: its lanes take their source row from gn_conv_src_row -- a per-lane offset.
+        const int jr = lane >> 3, j0 = 8 * wave + jr;
+        const bf16_t* cA = P.a + ((int64_t)(m0 - 2 + j0) * lda + (int64_t)(((lane & 7) ^ gn_conv_swz(j0)) * 8));
+        int64_t aclamp[NCL > 0 ? NCL : 1];
+#pragma unroll
+        for (int t = TS; t < PAc; ++t) aclamp[t - TS] = (int64_t)(gn_conv_src_row(BM, NW, wave, t, jr, m0, P.M) - j0) * lda;
+        (void)aclamp;
+        auto issue_a = [&](auto tc, int cb) {                        // piece t of this wave of channel block cb's image
+            constexpr int t = decltype(tc)::value;
+            const bf16_t* src = cA + (int64_t)cb * GN_BK;
+            if constexpr (t < TS) src += t * pstepA;
+            else src += aclamp[t - TS];
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                             (RTTS_LDS void*)(smem + cb * IMG + gn_conv_piece(BM, NW, wave, t) * 1024), 16, 0, 0);
+        };
+        auto issue_c = [&](auto qc, int stage_, int bufi) {          // piece q of the DMA group of stage `stage_` (ring slot bufi)
+            constexpr int q = decltype(qc)::value;
+            if constexpr (q < PW) {
+                if (stage_ < nk)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcW0 + q * pstepW + w_off(stage_)),
+                                                     (RTTS_LDS void*)(smem + wbase + bufi * W_BYTES + (wave + NW * q) * 1024), 16, 0, 0);
+            } else {
+                if (stage_ < cpt) issue_a(std::integral_constant<int, q - PW>{}, stage_);
+            }
+        };
+        // A fragment reads: tile row i of a tap that reads at shift u is image row i + u (forward: u = tap, x[m + tap - 2]; input
+        // gradient: u = 4 - tap, dy[m + 2 - tap]) -- one per-lane offset per tap.  Bank conflicts: the image has a key of its own,
+        // gn_conv_swz (conv_taps.h), under which the 16 lanes of every ds_read_b128 lane group land in 16 distinct 16-byte slots
+        // at EVERY row shift (the plain form's (row >> 1) & 7 is conflict-free for shifts 0 and 4 only).
+        uint32_t offT[GN_CONV_TAPS];
+#pragma unroll
+        for (int tap = 0; tap < GN_CONV_TAPS; ++tap) {
+            const int u = fwd ? tap : GN_CONV_TAPS - 1 - tap;
+            offT[tap] = (uint32_t)((wm * (BM / WM) + r + u) * 128 + ((g ^ gn_conv_swz(r + u)) << 4));
+        }
+        static_assert((BM / WM) % 16 == 0, "wave row base must not touch the swizzle key");
+#define GN_READ_AC(AF, aaddr_, KS)                                                                                         \
+    do {                                                                                                                   \
+        const uint32_t aa_ = (aaddr_) ^ ((KS) ? 64u : 0u);                                                                 \
+        gn_static_for<0, TM>([&](auto ic) { constexpr int i = decltype(ic)::value; gn_rd128<i * 2048>(AF[i], aa_); });     \
+    } while (0)
+        // prologue: the DMA groups of stages 0 .. NST - 1 (nk >= 5 > NST); group 0 has landed once only groups 1 and 2 are outstanding
+        gn_static_for<0, NST>([&](auto ic) {
+            gn_static_for<0, PERC>([&](auto qc) { issue_c(qc, decltype(ic)::value, decltype(ic)::value); });
+        });
+        if (cpt >= 3) gn_wait_vm<2 * PERC>();
+        else if (cpt == 2) gn_wait_vm<2 * PW + PAc>();
+        else gn_wait_vm<2 * PW>();
+        asm volatile("s_barrier" ::: "memory");
+        GN_READ_W(w0, wl0, wh0, smem_base + wbase - A_BYTES, 0);     // (offW carries the plain form's A_BYTES)
+        GN_READ_AC(a0, smem_base + offT[0], 0);
+        gn_static_for<0, GN_CONV_TAPS>([&](auto tapc) {
+            constexpr int tap = decltype(tapc)::value;
+            for (int cb = 0; cb < cpt; ++cb) {
+                const int s = tap * cpt + cb;
+                const uint32_t wsb = smem_base + wbase + buf * W_BYTES - A_BYTES;
+                const int nb = buf + 1 == NST ? 0 : buf + 1;
+                GN_READ_W(w1, wl1, wh1, wsb, 1);
+                GN_READ_AC(a1, smem_base + cb * IMG + offT[tap], 1);
+                gn_wait_lgkm<(RD_PER_KS < 15 ? RD_PER_KS : 15)>();          // F0 is back
+                __builtin_amdgcn_sched_barrier(0);
+                // first burst: the rest of the DMA group of stage s - 1 + NST (ring slot of stage s - 1)
+                GN_MFMA_I(a0, w0, wl0, wh0, s >= 1, [&](auto qc_) { issue_c(qc_, s - 1 + NST, pbuf); }, GAPC, SPBC, PERC);
+                __builtin_amdgcn_sched_barrier(0);
+                gn_wait_lgkm<0>();                                           // F1 is back: no read of stage s left
+                if (s + 1 < nk) {
+                    // younger than group s + 1: group s + 2 alone (NST = 3), with or without an image
+                    if (s + 2 < cpt) gn_wait_vm<PERC>();
+                    else if (s + 2 < nk) gn_wait_vm<PW>();
+                    else gn_wait_vm<0>();
+                    asm volatile("s_barrier" ::: "memory");                  // stage s + 1 complete in LDS; everybody is done reading stage s
+                    GN_READ_W(w0, wl0, wh0, smem_base + wbase + nb * W_BYTES - A_BYTES, 0);
+                    const uint32_t an = cb + 1 < cpt ? (uint32_t)((cb + 1) * IMG) + offT[tap] : offT[tap + 1 < GN_CONV_TAPS ? tap + 1 : tap];
+                    GN_READ_AC(a0, smem_base + an, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                // second burst: the first pieces of the DMA group of stage s + NST into the ring slot of stage s (behind the barrier)
+                GN_MFMA_I(a1, w1, wl1, wh1, true, [&](auto qc_) { issue_c(qc_, s + NST, buf); }, GAPC, 0, SPBC);
+                __builtin_amdgcn_sched_barrier(0);
+                pbuf = buf;
+                buf = nb;
+            }
+        });
+#undef GN_READ_AC
+    } else
     for (int s = 0; s < nk; ++s) {
         const uint32_t sb = smem_base + buf * STAGE;
         int nb = buf + 1 == NST ? 0 : buf + 1;
@@ -624,7 +744,9 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     }
   }
 #undef GN_READ
+#undef GN_READ_W
 #undef GN_MFMA
+#undef GN_MFMA_I
 #undef GN_WAIT_STAGE
 #undef GN_ISSUE
 #ifdef GN_STAMPS
@@ -652,11 +774,13 @@ constexpr int gn_nst() { return (4 * (BM + BN) * 128 <= 160 * 1024) ? 4 : ((3 * 
 // deepest ring, one workgroup per CU.  Process-wide, atomic; no environment is read on the launch path.
 static std::atomic<int> g_gn_mode{0};
 static std::atomic<int> g_gn_store{-1};
+static std::atomic<int> g_gn_conv{0};            // main loop of the convolutions: see gn_conv_form()
 extern "C" int rtts_debug_set_gemm_mode(int mode) {
     // 0..3: launch form (see above); 10 + s: store form s of the bf16 epilogues (0 = 8-byte, 1 = 16-byte, 2 = 16-byte write-through),
     // 9 = the library's pick of the store form again
     if (mode >= 9 && mode <= 12) { g_gn_store.store(mode - 10, std::memory_order_relaxed); return 0; }
-    if (mode < 0 || mode > 3) { rtts_set_error("rtts_debug_set_gemm_mode: 0..3 or 9..12 (got %d)", mode); return -1; }
+    if (mode >= 20 && mode <= 22) { g_gn_conv.store(mode - 20, std::memory_order_relaxed); return 0; }
+    if (mode < 0 || mode > 3) { rtts_set_error("rtts_debug_set_gemm_mode: 0..3, 9..12 or 20..22 (got %d)", mode); return -1; }
     g_gn_mode.store(mode, std::memory_order_relaxed);
     return 0;
 }
@@ -667,6 +791,19 @@ extern "C" int rtts_debug_set_gemm_mode(int mode) {
 // at the kernel boundary (B / 6 TB/s on top of the boundary itself: MI355X_MICROARCH.md, price list, "boundary"); written through,
 // it leaves while the MFMAs still run -- the fabric is idle under an ingest-bound GEMM -- and nothing is left to flush.  No consumer
 // loses an L2 hit: the next kernel's workgroups sit on all eight XCDs and read through their own L2 either way.
+// Main loop of the convolutions (rtts_conv1d_k5*): true = the convolution form (MODE 3: the input rows of all channel blocks stay
+// in LDS and serve the five taps), false = the plain loop, which fetches them once per tap.  Same K order, same results bit for bit.
+// The form needs conv_cpt images + the weight ring in LDS (gn_conv_fits): C_in <= 512 on the 4-wave tiles, <= 192 on 256 x 128,
+// <= 256 on 192 x 128; the other convolutions -- the postnet's 512 -> 512 on 256 x 128 among them -- keep the plain loop.
+// rtts_debug_set_gemm_mode(20) = the library's pick, 21 = the plain loop everywhere, 22 = the form wherever it fits (A/B runs, tests).
+static bool gn_conv_form(int bm, int bn, int cpt) {
+    // 256 x 256 (convolutions of M >= 32768 rows only) stays on the plain loop: with the per-tap A offsets on top of its accumulators
+    // its kernel spilled registers to scratch and returned NaN in y at M = 32768, 64 -> 512.  Supposed, not shown: a fragment
+    // spilled between its ds_read (inline assembly) and the counted lgkmcnt wait is stored before it has arrived.  Not pursued --
+    // no convolution of the model reaches this tile -- and the form is not instantiated for it.
+    if ((bm == 256 && bn == 256) || !gn_conv_fits(bm, bn, cpt)) return false;
+    return g_gn_conv.load(std::memory_order_relaxed) != 1;
+}
 #ifndef GN_DEFAULT_STORE
 #define GN_DEFAULT_STORE 2
 #endif
@@ -679,7 +816,8 @@ static int gn_store_mode(const void* c, int64_t ldc) {
 
 template <int BM, int BN, int WM, int WN, bool W_KN, int EPI, int NST, int MODE>
 static int gn_launch3(const GnGroup& G, int grid, hipStream_t s) {
-    constexpr size_t lds = (size_t)NST * (BM + BN) * 128;
+    // ring of NST stages of both operands; the convolution form: conv_cpt images of the input rows and NST weight stages
+    const size_t lds = MODE == 3 ? (size_t)gn_conv_lds_bytes(BM, BN, G.p[0].conv_cpt) : (size_t)NST * (BM + BN) * 128;
     static RttsLdsState attr;                    // per device: the dynamic-LDS limit is an attribute of the loaded function
     RTTS_ENSURE_LDS("rtts_gemm_nt", (gemm_nt_kernel<BM, BN, WM, WN, W_KN, EPI, NST, MODE>), lds, attr);
     hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, W_KN, EPI, NST, MODE>), dim3(grid), dim3(64 * WM * WN), lds, s, G);
@@ -691,6 +829,11 @@ static int gn_launch2(const GnGroup& G, hipStream_t s) {
     constexpr int NST = gn_nst<BM, BN>();
     const GnArgs& P = G.p[0];
     const int tiles = (P.M / BM) * (P.N / BN);
+    // a convolution (epilogues 0, 4, 7 only) takes the convolution form of the main loop wherever gn_conv_form() says so
+    if constexpr ((EPI == 0 || EPI == 4 || EPI == 7) && !(BM == 256 && BN == 256)) {
+        if (P.conv_cpt > 0 && gn_conv_form(BM, BN, P.conv_cpt))
+            return gn_launch3<BM, BN, WM, WN, W_KN, EPI, GN_CONV_NST, 3>(G, tiles, s);
+    }
     if constexpr (BM == 192 && BN == 128 && EPI != 4 && EPI != 5 && EPI != 7) {
         // Several tiles per CU (N >= 1024 at M = 12288: 512 / 1024 tiles).  Round 3 launched them all, two workgroups per CU on a
         // 2-deep ring, so that one workgroup's prologue / epilogue fills with the other's MFMAs (N = 2048, K = 512: 37.4 vs 45.5 us
