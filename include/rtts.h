@@ -656,6 +656,41 @@ int rtts_sw_draw_segments(const void* audio, int in_format, int64_t n_audio, con
                           int64_t ld_mel, const int64_t* frame_offsets, int n_utt, const int32_t* order, int n_order,
                           const int64_t* state, uint32_t seed, const int32_t* picks_in, int B, int seg_frames, int hop, int C,
                           int n_mel, float* audio_rows, float* mel_rows, int64_t ld_mel_rows, int32_t* picks_out, void* stream);
+/* One text-to-spectrogram training batch collated from a corpus that lives on the device (csrc/tts_corpus.hip):
+ * custom_sequence_padder (reference dataset/utils.py:5-42) for the B utterances `ids` names, and the Gaussian noise on the
+ * teacher-forcing input of LitReformerTTS.forward (reference training/wrappers.py:53-63), in one launch, written in the layouts
+ * the training step reads.
+ *   mel, ld_mel, frame_offsets   f32 (n_mel, ld_mel) rows and i64 (n_utt + 1) offsets, as rtts_mel_spectrogram writes them:
+ *                   utterance u owns columns [fo[u], fo[u+1]), len = their count
+ *   phoneme_ids, n_phonemes, phoneme_offsets   i32 ids end to end and i64 (n_utt + 1) offsets: utterance u owns [po[u], po[u+1])
+ *   ids             i32 (B), DEVICE: the utterances of the batch (the caller passes plan + offset; there is no cursor word)
+ *   lm              the batch's longest utterance in frames, as the host knows it: only stored into valid_len
+ * Outputs, each nullable (a null one is skipped) and each with its own row count -- the reference's collate layout and the padded
+ * buffers of a captured step differ.  With len_b, plen_b the frames and phonemes of ids[b], for c < n_mel:
+ *   phonemes            i64 (B, LP)             [b, j]    = j < plen_b ? phoneme_ids[po + j] : 0
+ *   spectrogram_input   f32 (B, R_in, n_mel)    [b, t, c] = 1 <= t <= len_b && t < valid_in ? mel[c, fo + t - 1] + noise : 0
+ *   spectrogram_target  f32 (B, R_target, n_mel) [b, t, c] = t < len_b ? mel[c, fo + t] : 0
+ *   stop_tokens         f32 (B, R_stop)         [b, t]    = t == len_b - 1 ? 1 : 0
+ *   loss_mask           f32 (B, R_mask, n_mel)  [b, t, c] = t < len_b ? 1 : 0
+ *   valid_len           i32 [1]                 = lm (an ordinary store from one lane)
+ * R_in = valid_in = lm + 1 is the reference's `spectrogram` (B, 1 + lm, n_mel) (target = its rows 1.., R_target = lm);
+ * R_in = the padded length of a captured step's buffer with valid_in = lm is that buffer as the host path fills it from
+ * spectrogram[:, :-1]: the batch's longest utterance loses its last frame, rows >= lm are zero.
+ * noise: noise_std <= 0 means none (bit for bit the kernel without the stage).  Otherwise the live input elements get
+ * + noise_std * z(b, f = t - 1, c); the start frame, the padding and the target stay untouched.  This is deliberately NOT the
+ * reference as written: its walrus (wrappers.py:45) binds std = True, and its in-place write also lands on the target and on the
+ * padding.  z is Box-Muller on the counter hash of the dropout sites, keyed by the utterance's own element, not the padded shape:
+ *     s_b = rtts_drop_hash(seed, b);  e = f * n_mel + c;  h1 = rtts_drop_hash(s_b, 2e);  h2 = rtts_drop_hash(s_b, 2e + 1)
+ *     u1 = ((h1 >> 8) + 1) * 2^-24;  u2 = (h2 >> 8) * 2^-24;  z = sqrtf(-2 logf(u1)) * cosf(6.2831855f * u2)     (|z| <= 5.77)
+ * An id outside [0, n_utt), or one whose offsets decrease or leave [0, ld_mel] / [0, n_phonemes], is an utterance of length 0: an
+ * all-zero slot with no stop token, never a read out of bounds.  Every word of every non-null output is written exactly once,
+ * padding included; no atomics; the output depends on the arguments alone.
+ * Supported: B in 1..65535, 1 <= n_mel <= 128, n_utt >= 1, row counts and LP >= 1 for the outputs given, 1 <= valid_in <= R_in;
+ * anything else, or a null input pointer, is rejected before any launch by the argument's name. */
+int rtts_tts_collate(const float* mel, int64_t ld_mel, const int64_t* frame_offsets, const int32_t* phoneme_ids, int64_t n_phonemes,
+                     const int64_t* phoneme_offsets, int n_utt, const int32_t* ids, int B, int n_mel, int lm, int64_t* phonemes, int LP,
+                     float* spectrogram_input, int R_in, int valid_in, float* spectrogram_target, int R_target, float* stop_tokens,
+                     int R_stop, float* loss_mask, int R_mask, int32_t* valid_len, float noise_std, uint32_t seed, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

@@ -148,6 +148,8 @@ SIGNATURES = {
     "rtts_sw_inv1x1_factor": [C.POINTER(_vp), C.POINTER(_i32), _i32, C.POINTER(_vp), _vp, _vp],
     "rtts_sw_draw_segments": [_vp, _i32, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _u32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
                               _vp, _vp],
+    "rtts_tts_collate": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32,
+                         _vp, _f32, _u32, _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],

@@ -117,6 +117,9 @@ class TTSTrainingConfig:
     post_pred_loss_weight: float = 1.0
     stop_loss_weight: float = 1.0
     spectrogram_loss: str = "mse"
+    # ``training/config.py``: std of the Gaussian noise on the teacher-forcing input.  Applied by ``Trainer.fit_corpus`` (inside
+    # the collate launch, to the valid input frames only: dataset/corpus.py says how that differs from the reference as written)
+    noise_std: Optional[float] = None
     # this package's addition (not a key of the reference's TTSTrainingConfig): under data parallelism, BatchNorm statistics
     # over the GLOBAL batch (what the reference's single-process BatchNorm sees) instead of each rank's own rows
     sync_batchnorm: bool = False
@@ -154,8 +157,8 @@ def load_yaml(path: str):
     model = model_config_from_dict(raw.get("model", {}))
     exp = raw.get("experiment", {})
     tr = dict(exp.get("tts_training", {}))
-    for k in ("num_visualizations", "early_stopping_epochs", "noise_std"):      # plotting / early stopping / input noise: the
-        tr.pop(k, None)                                                         # harness around the step, not the step
+    for k in ("num_visualizations", "early_stopping_epochs"):                   # plotting / early stopping: the harness around
+        tr.pop(k, None)                                                         # the step, not the step
     sched = tr.pop("lr_scheduler", None)
     cfg = _merge(TTSTrainingConfig(), tr)
     if sched is not None:

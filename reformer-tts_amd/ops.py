@@ -345,3 +345,51 @@ def sw_draw_segments(audio: torch.Tensor, sample_offsets: torch.Tensor, mel: tor
               mel_rows.stride(0), picks_out.data_ptr(), _stream())
     TIMING.stop(ev, 0.0)
     return audio_rows, mel_rows, picks_out
+
+
+def tts_collate(mel: torch.Tensor, frame_offsets: torch.Tensor, phoneme_ids: torch.Tensor, phoneme_offsets: torch.Tensor, ids: torch.Tensor,
+                lm: int, *, phonemes: Optional[torch.Tensor] = None, spectrogram_input: Optional[torch.Tensor] = None,
+                valid_in: Optional[int] = None, spectrogram_target: Optional[torch.Tensor] = None, stop_tokens: Optional[torch.Tensor] = None,
+                loss_mask: Optional[torch.Tensor] = None, valid_len: Optional[torch.Tensor] = None, noise_std: float = 0.0,
+                seed: int = 0) -> None:
+    """One text-to-spectrogram batch collated from a device-resident corpus (``rtts_tts_collate``): mel f32 (n_mel, frames) rows as
+    ``rtts_mel_spectrogram`` writes them with frame_offsets int64 (n + 1,); phoneme_ids int32 flat with phoneme_offsets int64
+    (n + 1,); ids int32 (B,) ON THE DEVICE (a slice of an uploaded plan); ``lm`` the batch's longest utterance, a host int ->
+    the outputs given, each written in full, padding included: phonemes int64 (B, LP), spectrogram_input f32 (B, R_in, n_mel)
+    live below row ``valid_in`` (default R_in), spectrogram_target f32 (B, R, n_mel), stop_tokens f32 (B, R), loss_mask f32
+    (B, R, n_mel), valid_len int32 (1,) = lm.  ``noise_std`` > 0: Gaussian noise on the live input frames, keyed by
+    (seed, slot, frame, channel).  All on one device; one launch on the current stream, nothing read back."""
+    named = (("mel", mel, torch.float32, False), ("frame_offsets", frame_offsets, torch.int64, False), ("phoneme_ids", phoneme_ids, torch.int32, False),
+             ("phoneme_offsets", phoneme_offsets, torch.int64, False), ("ids", ids, torch.int32, False), ("phonemes", phonemes, torch.int64, True),
+             ("spectrogram_input", spectrogram_input, torch.float32, True), ("spectrogram_target", spectrogram_target, torch.float32, True),
+             ("stop_tokens", stop_tokens, torch.float32, True), ("loss_mask", loss_mask, torch.float32, True), ("valid_len", valid_len, torch.int32, True))
+    dev = mel.device if torch.is_tensor(mel) else None
+    for name, t, dt, optional in named:
+        if t is None and optional:
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.device == dev):
+            raise _lib.RttsError(f"tts_collate runs on the GPU only: {name} must be a CUDA {dt} tensor on {dev} "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+    n_utt = frame_offsets.numel() - 1
+    if not (mel.dim() == 2 and mel.is_contiguous() and frame_offsets.dim() == 1 and frame_offsets.is_contiguous() and n_utt >= 1
+            and phoneme_ids.dim() == 1 and phoneme_ids.is_contiguous() and tuple(phoneme_offsets.shape) == (n_utt + 1,)
+            and phoneme_offsets.is_contiguous() and ids.dim() == 1 and ids.is_contiguous()):
+        raise ValueError("tts_collate: mel (n_mel, frames) contiguous, phoneme_ids flat, frame_offsets and phoneme_offsets (n + 1,), ids (B,)")
+    n_mel, b = mel.shape[0], ids.numel()
+    want = dict(phonemes=(b, None), spectrogram_input=(b, None, n_mel), spectrogram_target=(b, None, n_mel), stop_tokens=(b, None),
+                loss_mask=(b, None, n_mel), valid_len=(1,))
+    for name, t, _, optional in named:
+        if optional and t is not None:
+            w = want[name]
+            if not (t.is_contiguous() and t.dim() == len(w) and all(x is None or x == s for x, s in zip(w, t.shape))):
+                raise ValueError(f"tts_collate: {name} must be contiguous of shape {tuple('*' if x is None else x for x in w)}, got {tuple(t.shape)}")
+
+    def rows(t):
+        return 0 if t is None else t.shape[1]
+    r_in = rows(spectrogram_input)
+    ev = TIMING.start("rtts_tts_collate")
+    _lib.call("rtts_tts_collate", mel.data_ptr(), mel.shape[1], frame_offsets.data_ptr(), phoneme_ids.data_ptr(), phoneme_ids.numel(),
+              phoneme_offsets.data_ptr(), n_utt, ids.data_ptr(), b, n_mel, int(lm), _ptr(phonemes), rows(phonemes), _ptr(spectrogram_input), r_in,
+              r_in if valid_in is None else int(valid_in), _ptr(spectrogram_target), rows(spectrogram_target), _ptr(stop_tokens), rows(stop_tokens),
+              _ptr(loss_mask), rows(loss_mask), _ptr(valid_len), float(noise_std or 0.0), int(seed) & 0xFFFFFFFF, _stream())
+    TIMING.stop(ev, 0.0)

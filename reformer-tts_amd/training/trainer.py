@@ -72,6 +72,25 @@ def stop_mae(stop_logits: torch.Tensor, stop_tokens: torch.Tensor) -> torch.Tens
     return (first - stop_tokens.argmax(dim=1)).abs().float().mean()
 
 
+class _CorpusMicro:
+    """One micro-batch of ``Trainer.fit_corpus``: utterance ids on the host and as a slice of the uploaded plan, the batch's
+    longest utterance and the key of its padded shape in the per-shape graph cache."""
+
+    def __init__(self, corpus, ids, dev_ids, lm, key, noise_std):
+        self.corpus, self.ids, self.dev_ids, self.lm, self.key, self.noise_std = corpus, ids, dev_ids, lm, key, noise_std
+
+    def entry(self, trainer):
+        """The shape's graph entry; a shape seen for the first time is captured from the collated batch."""
+        cache = trainer.__dict__.setdefault("_shape_graphs", {})
+        return cache[self.key] if self.key in cache else trainer._shape_graph(self.corpus.collate(self.ids))
+
+    def eager(self, seed):
+        """What an eager step trains on: the reference's collate, or input and target apart when the input carries noise."""
+        if self.noise_std:
+            return self.corpus.frames(self.ids, self.noise_std, seed)
+        return self.corpus.collate(self.ids)
+
+
 class Trainer:
     def __init__(self, model: ReformerTTS, cfg: TTSTrainingConfig, device, process_group=None):
         self.model, self.cfg, self.device = model, cfg, torch.device(device)
@@ -680,6 +699,8 @@ class Trainer:
         device word.  Clip + AdamW is one more graph.  A shape outside the fused edges' envelope runs eagerly.
         -> list of the (mean) total loss per optimizer step (device scalars; no per-step host sync)."""
         from ..dataset import BatchPrefetcher
+        if getattr(self.cfg, "noise_std", None):
+            _lib.note_general_path("Trainer.fit", "input noise (tts_training.noise_std) is applied by fit_corpus only: host batches train without it")
         losses, group = [], []
         acc = max(1, int(self.cfg.accumulate_grad_batches))
         from .. import edges
@@ -701,6 +722,55 @@ class Trainer:
             losses.append(step(group))
         self.end_epoch()
         return losses
+
+    def fit_corpus(self, corpus, plan, log_every: int = 0, graphs: Optional[bool] = None):
+        """One epoch of ``fit`` from a device-resident ``dataset.TTSCorpus``: ``plan`` is the epoch's list of utterance-id lists
+        (``dataset.batch_plan`` / ``variable_batch_plan``), uploaded once as one int32 tensor.  Per micro-batch the host works
+        out (B, Lp, Lm) and the padded shape from the corpus's host length lists, one ``rtts_tts_collate`` launch
+        (``corpus.fill``) writes the batch into that shape's graph buffers -- padding, ``valid_len`` and, with
+        ``cfg.noise_std``, the input noise included -- and the graph replays: no host tensors, no copies, no
+        ``_fill_shape_buffers``.  Same grouping into optimizer steps, same per-shape graph cache (shared with ``fit``) and same
+        ``end_epoch`` as ``fit``; a shape seen for the first time is captured from ``corpus.collate`` of that batch, a shape
+        without a graph runs eagerly on it.  The noise seed of a micro-batch derives from ``step_seed(global_step)`` and its
+        index in the group.  -> list of the (mean) total loss per optimizer step (device scalars)."""
+        from .. import edges
+        plan = [[int(i) for i in ids] for ids in plan]
+        if not plan or any(not ids for ids in plan):
+            raise ValueError("fit_corpus: the plan must be a non-empty list of non-empty utterance-id lists")
+        use_graphs = (self.device.type == "cuda" and self.use_fused_edges and edges.SYNC_BN is None) if graphs is None else bool(graphs)
+        flat = torch.tensor([i for ids in plan for i in ids], dtype=torch.int32).to(corpus.device)
+        acc = max(1, int(self.cfg.accumulate_grad_batches))
+        pb = self.model.pad_base
+        losses, group, at = [], [], 0
+
+        def step(micros):
+            if use_graphs:
+                return self._train_group_graphed(micros)
+            batches = [m.eager(self._noise_seed(i)) for i, m in enumerate(micros)]
+            return self.train_step(batches[0])[0] if len(batches) == 1 else self.train_accumulated(batches)
+
+        for ids in plan:
+            lp, lm = corpus._shape(ids)
+            group.append(_CorpusMicro(corpus, ids, flat[at:at + len(ids)], lm, (len(ids), -(-lp // pb), -(-lm // pb)),
+                                      getattr(self.cfg, "noise_std", None)))
+            at += len(ids)
+            if len(group) == acc:
+                losses.append(step(group))
+                group = []
+                if log_every and len(losses) % log_every == 0:
+                    print(f"step {self.global_step}: loss {float(losses[-1]):.4f}", flush=True)
+        if group:                                              # a trailing partial group still makes a step
+            losses.append(step(group))
+        self.end_epoch()
+        return losses
+
+    def _noise_seed(self, micro: int) -> int:
+        """Seed word of the input noise of micro-batch ``micro`` of the optimizer step about to run."""
+        return (self.step_seed(self.global_step) * 2654435761 + 40503 * micro + 0x5bd1e995) & 0xFFFFFFFF
+
+    def validate_corpus(self, corpus, ids, return_attention: bool = False):
+        """``validate`` on the utterances ``ids`` of a ``dataset.TTSCorpus``, collated on the device; never with input noise."""
+        return self.validate(corpus.collate(ids), return_attention=return_attention)
 
     # ------------------------------------------------------------------ per-shape graph cache (real, ragged batches)
     MAX_SHAPE_GRAPHS = 32          # LJSpeech at pad_base 256: text 1-2 x mel 1-4 multiples x (full | last) batch size
@@ -800,7 +870,8 @@ class Trainer:
         from .._seeds import seed_base
         n = len(batches)
         self.model.train()
-        entries = [self._shape_graph(b) for b in batches]      # captures first: a capture must not see a half-built gradient
+        # captures first: a capture must not see a half-built gradient
+        entries = [b.entry(self) if isinstance(b, _CorpusMicro) else self._shape_graph(b) for b in batches]
         self.zero_grad()
         if getattr(self, "_acc_scale", None) is not None:
             self._acc_scale.fill_(1.0 / n)
@@ -823,14 +894,18 @@ class Trainer:
         self.set_step_hyper(self.global_step)                  # lr, Adam step size, dropout seed of this optimizer step
         total = None
         for i, (batch, entry) in enumerate(zip(batches, entries)):
+            corpus_seed = self._noise_seed(i) if isinstance(batch, _CorpusMicro) else None
             if entry is None:
                 self._accumulating = True                      # the exchange happens once, below
-                loss = self.forward_loss(batch)[0]
+                loss = self.forward_loss(batch if corpus_seed is None else batch.eager(corpus_seed))[0]
                 self._run_backward(loss * (1.0 / n))
                 self._accumulating = False
                 loss = loss.detach()
             else:
-                self._fill_shape_buffers(entry, batch)
+                if corpus_seed is None:
+                    self._fill_shape_buffers(entry, batch)
+                else:                                          # one launch: the batch, its padding, valid_len and the input noise
+                    batch.corpus.fill(entry["bufs"], batch.dev_ids, batch.noise_std, corpus_seed, lm=batch.lm)
                 if i:                                          # the graph's dropout sites are frozen constants + this device word:
                     seed_base(self.device).add_(7919)          # micro-batches of one step must not repeat each other's masks
                 entry["graph"].replay()
