@@ -691,6 +691,41 @@ int rtts_tts_collate(const float* mel, int64_t ld_mel, const int64_t* frame_offs
                      const int64_t* phoneme_offsets, int n_utt, const int32_t* ids, int B, int n_mel, int lm, int64_t* phonemes, int LP,
                      float* spectrogram_input, int R_in, int valid_in, float* spectrogram_target, int R_target, float* stop_tokens,
                      int R_stop, float* loss_mask, int R_mask, int32_t* valid_len, float noise_std, uint32_t seed, void* stream);
+/* B generated spectrograms scored against their truths where both already live (csrc/infer_metrics.hip): the inference_pred_mse
+ * and inference_stop_mae of LitReformerTTS.validate_inference (reference training/wrappers.py:188-195) and the per-utterance
+ * squared error behind predict_samples' mse_loss and cutoff (reference cli.py:150-152).  Two kernels on `stream`, nothing read back.
+ *   gen             f32, element (b, m, t) at gen[b gs_b + m gs_mel + t gs_t], L >= 0 frames (null only with L = 0): ReformerTTS.infer's
+ *                   (B, n_mel, L) and the teacher-forced forward's (B, T, n_mel) are both taken as they are
+ *   gen_stop        i64 (B), nullable: infer's stop indices
+ *   truth           f32, channel m of frame f at truth[m ts_mel + f ts_t], f < truth_frames.  Slot b owns frames [f0_b, f0_b + len_b)
+ *                   by exactly ONE of two descriptions:
+ *                     corpus        frame_offsets i64 (n_utt + 1) + ids i32 (B), DEVICE; ids null: slot b is utterance b; ids may
+ *                                   repeat and come in any order.  f0_b = fo[u], len_b = fo[u + 1] - fo[u]
+ *                     padded batch  starts i64 (B) + lengths i32 (B), DEVICE, in frames (a collate batch's spectrogram[:, 1:] viewed
+ *                                   as (B (lm + 1), n_mel) rows: starts[b] = b (lm + 1) + 1, ts_t = n_mel, ts_mel = 1)
+ *   lm              the batch's longest truth in frames (true_mel.shape[-1] of the reference), a host int >= 1
+ *   longest         the longest len_b where the host knows it (must not exceed lm), 0 where it does not
+ *   partials        f64 workspace of B * rtts_infer_metrics_tiles(lm) words, overwritten
+ * Outputs, f64, with g(b, m, t) = t < L ? gen(b, m, t) : 0 widened to f64 BEFORE the subtraction:
+ *   sse[b]      = sum_{t < len_b} sum_m (g(b, m, t) - truth_b(m, t))^2
+ *   stop_err[b] = | gen_stop[b] - (len_b - 1) |                     (0 when gen_stop is null)
+ *   totals[0]   = sum_b sse[b] / (B n_mel lm)        totals[1] = mean_b stop_err[b]      (0 when gen_stop is null)
+ * With gen = infer's spectrogram, totals are wrappers.py:188-195 exactly: the reference divides by the PADDED element count
+ * (mse_loss over zeros_like(true_mel)), truth frames past L count against a prediction of zero, and generated frames past an
+ * utterance's own stop still count up to len_b; frames at or past len_b are masked on both sides and are not read here, so a NaN
+ * there reaches nothing, while one in a counted frame reaches sse[b] and totals[0].  sse[b] / (len_b n_mel) is cli.py:150's B = 1
+ * mse_loss of utterance b.
+ * Every sum has one fixed order (per-workgroup partials folded by index, no atomics) that depends on (B, n_mel, lm, the lengths)
+ * alone -- not on the strides: the same numbers in another layout, and a second call, give the same bits.
+ * A slot whose description leaves [0, truth_frames] (or an id outside [0, n_utt)) is never read: its sse and stop_err, and the
+ * totals with them, are NaN.
+ * Supported: B in 1..65535, 1 <= n_mel <= 128, lm >= 1, L >= 0, every len_b >= 1; anything else, a null pointer, neither or both
+ * truth descriptions, or longest > lm is rejected before any launch by the argument's name. */
+int rtts_infer_metrics_tiles(int lm);
+int rtts_infer_metrics(const float* gen, int64_t gs_b, int64_t gs_mel, int64_t gs_t, int L, const int64_t* gen_stop, const float* truth,
+                       int64_t ts_mel, int64_t ts_t, int64_t truth_frames, const int64_t* frame_offsets, int n_utt, const int32_t* ids,
+                       const int64_t* starts, const int32_t* lengths, int B, int n_mel, int lm, int longest, double* partials, double* sse,
+                       double* stop_err, double* totals, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

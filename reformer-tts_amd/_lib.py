@@ -150,6 +150,9 @@ SIGNATURES = {
                               _vp, _vp],
     "rtts_tts_collate": [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp, _i32,
                          _vp, _f32, _u32, _vp],
+    "rtts_infer_metrics_tiles": [_i32],
+    "rtts_infer_metrics": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                           _vp, _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],

@@ -393,3 +393,58 @@ def tts_collate(mel: torch.Tensor, frame_offsets: torch.Tensor, phoneme_ids: tor
               r_in if valid_in is None else int(valid_in), _ptr(spectrogram_target), rows(spectrogram_target), _ptr(stop_tokens), rows(stop_tokens),
               _ptr(loss_mask), rows(loss_mask), _ptr(valid_len), float(noise_std or 0.0), int(seed) & 0xFFFFFFFF, _stream())
     TIMING.stop(ev, 0.0)
+
+
+def infer_metrics(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: torch.Tensor, lm: int, *, gen_frames_last: bool = True,
+                  truth_frames_last: bool = True, frame_offsets: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None,
+                  starts: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None, longest: int = 0):
+    """B generated spectrograms scored against their truths in place (``rtts_infer_metrics``): ``gen`` f32 3-D with any strides,
+    (B, n_mel, L) as ``ReformerTTS.infer`` returns it or, with ``gen_frames_last=False``, (B, T, n_mel) as the teacher-forced
+    forward does; ``gen_stop`` int64 (B,) or None; ``truth`` f32 2-D, (n_mel, frames) as a ``TTSCorpus`` packs it or, with
+    ``truth_frames_last=False``, (frames, n_mel) rows.  Slot b's truth frames are named by exactly one of ``frame_offsets`` int64
+    (n + 1,) with ``ids`` int32 (B,) (None: slot b is utterance b), or ``starts`` int64 (B,) with ``lengths`` int32 (B,), all ON THE
+    DEVICE.  ``lm``: the batch's longest truth, a host int; ``longest``: the longest length where the host knows it (checked
+    against ``lm``), else 0.  -> (sse f64 (B,), stop_err f64 (B,), totals f64 (2,) = [Σ sse / (B n_mel lm), mean stop_err]);
+    ``gen_stop=None`` leaves stop_err and totals[1] zero.  One call on the current stream, nothing read back: capturable."""
+    corpus, padded = frame_offsets is not None, (starts is not None or lengths is not None)
+    if corpus == padded or (padded and (starts is None or lengths is None)) or (ids is not None and not corpus):
+        raise ValueError("infer_metrics: describe the truth by frame_offsets (+ ids) or by starts + lengths: exactly one of the two")
+    named = (("gen", gen, torch.float32, False), ("gen_stop", gen_stop, torch.int64, True), ("truth", truth, torch.float32, False),
+             ("frame_offsets", frame_offsets, torch.int64, True), ("ids", ids, torch.int32, True), ("starts", starts, torch.int64, True),
+             ("lengths", lengths, torch.int32, True))
+    for name, t, dt, optional in named:
+        if t is None and optional:
+            continue
+        if not (torch.is_tensor(t) and t.dtype == dt):
+            raise ValueError(f"infer_metrics: {name} must be a {dt} tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+    dev = gen.device
+    for name, t, dt, optional in named:
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise _lib.RttsError(f"infer_metrics runs on the GPU only: {name} must be a CUDA {dt} tensor on {dev} (got one on {t.device})")
+    if gen.dim() != 3 or truth.dim() != 2:
+        raise ValueError(f"infer_metrics: gen must be 3-D and truth 2-D (got {tuple(gen.shape)} and {tuple(truth.shape)})")
+    b = gen.shape[0]
+    n_mel, frames, gs_mel, gs_t = (gen.shape[1], gen.shape[2], gen.stride(1), gen.stride(2)) if gen_frames_last else \
+        (gen.shape[2], gen.shape[1], gen.stride(2), gen.stride(1))
+    t_mel, t_frames, ts_mel, ts_t = (truth.shape[0], truth.shape[1], truth.stride(0), truth.stride(1)) if truth_frames_last else \
+        (truth.shape[1], truth.shape[0], truth.stride(1), truth.stride(0))
+    if t_mel != n_mel:
+        raise ValueError(f"infer_metrics: gen has {n_mel} mel channels, truth {t_mel}")
+    for name, t in (("gen_stop", gen_stop), ("ids", ids), ("starts", starts), ("lengths", lengths)):
+        if t is not None and not (tuple(t.shape) == (b,) and t.is_contiguous()):
+            raise ValueError(f"infer_metrics: {name} must be contiguous of shape ({b},), got {tuple(t.shape)}")
+    n_utt = 0
+    if corpus:
+        n_utt = frame_offsets.numel() - 1
+        if not (frame_offsets.dim() == 1 and frame_offsets.is_contiguous() and n_utt >= 1):
+            raise ValueError("infer_metrics: frame_offsets must be contiguous of shape (n + 1,), n >= 1")
+    lm = int(lm)
+    tiles = _lib.load().rtts_infer_metrics_tiles(lm)
+    out = torch.empty(2 * b + 2 + b * tiles, dtype=torch.float64, device=dev)
+    sse, stop_err, totals, partials = out[:b], out[b:2 * b], out[2 * b:2 * b + 2], out[2 * b + 2:]
+    ev = TIMING.start("rtts_infer_metrics")
+    _lib.call("rtts_infer_metrics", gen.data_ptr() if frames else None, gen.stride(0), gs_mel, gs_t, frames, _ptr(gen_stop), truth.data_ptr(),
+              ts_mel, ts_t, t_frames, _ptr(frame_offsets), n_utt, _ptr(ids), _ptr(starts), _ptr(lengths), b, n_mel, lm, int(longest),
+              partials.data_ptr(), sse.data_ptr(), stop_err.data_ptr(), totals.data_ptr(), _stream())
+    TIMING.stop(ev, 0.0)
+    return sse, stop_err, totals

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import math
 import os
+import time
 from typing import Dict, List, Optional
 
 import torch
@@ -771,6 +772,150 @@ class Trainer:
     def validate_corpus(self, corpus, ids, return_attention: bool = False):
         """``validate`` on the utterances ``ids`` of a ``dataset.TTSCorpus``, collated on the device; never with input noise."""
         return self.validate(corpus.collate(ids), return_attention=return_attention)
+
+    # ------------------------------------------------------------------ the generating half of validation
+    def _eval_flags(self):
+        """What an eval-mode run may flip, to be put back by ``_restore_flags``."""
+        stacks = (self.model.enc.reformer.layers, self.model.dec.reformer.layers)
+        return self.model.training, self.model.dec.reformer.collect_attention, [(st, st.fused_in_eval) for st in stacks]
+
+    def _restore_flags(self, flags):
+        was_training, was_collect, fused = flags
+        for st, f in fused:
+            st.fused_in_eval = f
+        self.model.dec.reformer.collect_attention = was_collect
+        self.model.train(was_training)
+
+    def _validate_inference(self, phonemes, truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder, return_outputs):
+        from .. import ops
+        if combine_strategy not in ("concat", "replace"):
+            raise ValueError(f"validate_inference: combine_strategy must be 'concat' or 'replace' (got {combine_strategy!r})")
+        if use_graph is None:
+            use_graph = combine_strategy == "concat" and self.device.type == "cuda"
+        flags = self._eval_flags()
+        try:
+            start = time.perf_counter()
+            spec, stop = self.model.infer(phonemes, combine_strategy=combine_strategy, max_len=max_len, stop_threshold=stop_threshold,
+                                          stop_at_stop_token=self.cfg.stop_loss_weight != 0., cache_encoder=cache_encoder,
+                                          use_graph=bool(use_graph) and combine_strategy == "concat")
+            torch.cuda.synchronize(spec.device)
+            inference_time = time.perf_counter() - start
+        finally:
+            self._restore_flags(flags)
+        sse, stop_err, totals = ops.infer_metrics(spec, stop, lm=lm, **truth_kw)
+        out = {f"{combine_strategy}_inference_pred_mse": totals[0], f"{combine_strategy}_inference_stop_mae": totals[1],
+               f"{combine_strategy}_inference_time": inference_time, "sse": sse, "stop_err": stop_err}
+        if return_outputs:
+            out["spectrogram"], out["stop"] = spec, stop
+        return out
+
+    @torch.no_grad()
+    def validate_inference(self, batch, combine_strategy: str = "concat", *, max_len: int = 1024, stop_threshold: float = 0.25,
+                           use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False) -> dict:
+        """``LitReformerTTS.validate_inference`` (``wrappers.py:165-211``) without the plots, on a device batch in the reference's
+        collate layout: ``model.infer`` on the batch's phonemes with ``stop_at_stop_token = (cfg.stop_loss_weight != 0)``
+        (``:180``), then ONE ``rtts_infer_metrics`` call that scores the generated spectrogram against
+        ``batch["spectrogram"][:, 1:]`` where it lies (lengths from ``stop_tokens``, on the device): no ``zeros_like``, transposes,
+        copy or mask multiply.  -> the reference's three entries under its names -- ``f"{strategy}_inference_pred_mse"`` and
+        ``f"{strategy}_inference_stop_mae"`` as f64 DEVICE scalars, ``f"{strategy}_inference_time"`` a host float -- plus the
+        per-utterance ``sse`` and ``stop_err`` (f64, (B,)), and with ``return_outputs`` ``infer``'s ``spectrogram`` and ``stop``.
+
+        What the numbers count (``:188-195``): the squared error over every utterance's own frames, a missing generated frame
+        counting as zero and frames generated past an utterance's stop still counting up to its truth length, divided by the
+        PADDED element count B * n_mel * Lm; and the mean distance in frames between ``infer``'s stop index and the stop token.
+        ``inference_time`` is the host clock around ``infer`` AND one synchronise: the reference's clock (``:179-186``) stops
+        without a synchronise, i.e. it times the launches of whatever the device has not finished yet.
+
+        ``use_graph`` (default: on for "concat" on the GPU) generates with one hipGraph replay per frame; "replace" runs the eager
+        loop.  Parameters, Adam moments, ``global_step``, the train/eval mode, ``collect_attention``, the stacks' executor flags
+        and the per-shape training graph cache are left as they were."""
+        spec = batch["spectrogram"]
+        b, rows, n_mel = spec.shape
+        spec = spec if spec.is_contiguous() else spec.contiguous()
+        truth_kw = dict(truth=spec.view(b * rows, n_mel), truth_frames_last=False,
+                        starts=torch.arange(b, dtype=torch.int64, device=spec.device) * rows + 1,
+                        lengths=(batch["stop_tokens"].argmax(dim=1) + 1).to(torch.int32))
+        return self._validate_inference(batch["phonemes"], truth_kw, rows - 1, combine_strategy, max_len, stop_threshold, use_graph,
+                                        cache_encoder, return_outputs)
+
+    @torch.no_grad()
+    def validate_inference_corpus(self, corpus, ids, combine_strategy: str = "concat", *, max_len: int = 1024, stop_threshold: float = 0.25,
+                                  use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False) -> dict:
+        """``validate_inference`` on the utterances ``ids`` (host ints) of a ``dataset.TTSCorpus``: ``rtts_tts_collate`` writes the
+        padded phonemes alone, and the generated spectrogram is scored against ``corpus.mel`` in place through the corpus's
+        frame offsets and the ids -- no padded truth batch is built.  Same dictionary, same bits as the batch form."""
+        ids = [int(i) for i in ids]
+        lp, lm = corpus._shape(ids)
+        dev_ids = torch.tensor(ids, dtype=torch.int32).to(corpus.device)
+        phonemes = torch.empty(len(ids), max(lp, 1), dtype=torch.int64, device=corpus.device)
+        corpus._launch(dev_ids, lm, None, 0, phonemes=phonemes)
+        truth_kw = dict(truth=corpus.mel, frame_offsets=corpus.tables[0], ids=dev_ids, longest=lm)
+        return self._validate_inference(phonemes[:, :lp], truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder,
+                                        return_outputs)
+
+    @torch.no_grad()
+    def validation_epoch(self, corpus, ids, batch_size: Optional[int] = None, inference: bool = True, **inference_kwargs) -> Dict[str, float]:
+        """The reference's validation epoch without the plotting: ``val_dataloader`` (``wrappers.py:224-232``: batches of
+        ``batch_size``, default ``cfg.batch_size``, in order, the incomplete last batch dropped), ``validation_step`` on each
+        (``validate_corpus``), ``validation_epoch_end``'s mean over batches of the five values (``:131-158``) and, with
+        ``inference``, ``validate_inference_corpus`` on the first ``batch_size`` ids (``:166-168``; ``inference_kwargs``, e.g.
+        ``max_len``, pass through to it).  -> the reference's log dictionary as host floats: ``val_loss``, ``val_stop_loss``,
+        ``val_raw_pred_loss``, ``val_post_pred_loss``, ``val_stop_mae`` and the three ``concat_inference_*`` entries.  Everything
+        is accumulated on the device and read once."""
+        ids = [int(i) for i in ids]
+        bs = int(self.cfg.batch_size if batch_size is None else batch_size)
+        if bs < 1 or len(ids) < bs:
+            raise ValueError(f"validation_epoch: {len(ids)} utterances make no batch of {bs}")
+        acc, n = None, len(ids) // bs
+        for k in range(n):
+            row = torch.stack(self.validate_corpus(corpus, ids[k * bs:(k + 1) * bs]))      # total, raw, post, stop, stop_mae
+            acc = row if acc is None else acc + row
+        values = (acc / n).double()
+        names = ["val_loss", "val_raw_pred_loss", "val_post_pred_loss", "val_stop_loss", "val_stop_mae"]
+        inference_time = None
+        if inference:
+            inf = self.validate_inference_corpus(corpus, ids[:bs], "concat", **inference_kwargs)
+            values = torch.cat([values, torch.stack([inf["concat_inference_pred_mse"], inf["concat_inference_stop_mae"]])])
+            names += ["concat_inference_pred_mse", "concat_inference_stop_mae"]
+            inference_time = inf["concat_inference_time"]
+        logs = dict(zip(names, values.cpu().tolist()))
+        if inference:
+            logs["concat_inference_time"] = inference_time
+        return logs
+
+    @torch.no_grad()
+    def predict_corpus(self, corpus, ids) -> Dict[str, torch.Tensor]:
+        """The device-side core of the reference's ``predict_samples`` (``cli.py:93-166``) for a batch: one teacher-forced eval
+        forward of the utterances ``ids``, the post-net prediction scored by ``rtts_infer_metrics`` in its own (B, T, n_mel)
+        layout against ``corpus.mel``.  -> ``{"spectrogram": (B, n_mel, Lm) f32, "mse": (B,) f64, "cutoff": (B,) int64}``:
+        ``mse[b] = sse[b] / (len_b * n_mel)`` is the reference's B = 1 ``mse_loss`` over the utterance's own frames
+        (``cli.py:150``) and ``cutoff[b]`` the argmax of the stop logits over them (``cli.py:152``), in the layout
+        ``synthesis.vocode_trimmed(vocoder, spectrogram, cutoff)`` takes: one ragged vocoder call finishes what the reference
+        does sample by sample.
+
+        ``cli.py:149`` as written calls ``LitReformerTTS.forward`` with two of its four arguments (and unpacks two of its four
+        results); what is built here is its evident intent -- phonemes and the shifted spectrogram in, post-net spectrogram and
+        stop logits out, each utterance masked to its own frames as a B = 1 call has them."""
+        from .. import ops
+        ids = [int(i) for i in ids]
+        batch = corpus.collate(ids)
+        lm = batch["stop_tokens"].shape[1]
+        lens = torch.tensor([corpus.frame_lengths[i] for i in ids], dtype=torch.int64).to(corpus.device)
+        flags = self._eval_flags()
+        self.model.eval()
+        for st, _ in flags[2]:
+            st.fused_in_eval = True
+        self.model.dec.reformer.collect_attention = False
+        try:
+            _, post, stop, _ = self.model(batch["phonemes"], batch["spectrogram"][:, :-1], spectrogram_mask=batch["loss_mask"].mean(dim=-1))
+        finally:
+            self._restore_flags(flags)
+        post = post if post.dtype == torch.float32 else post.float()
+        sse, _, _ = ops.infer_metrics(post, None, corpus.mel, lm, gen_frames_last=False, frame_offsets=corpus.tables[0],
+                                      ids=torch.tensor(ids, dtype=torch.int32).to(corpus.device), longest=lm)
+        own = torch.arange(lm, device=post.device).unsqueeze(0) < lens.unsqueeze(1)
+        cutoff = stop.reshape(len(ids), -1).float().masked_fill(~own, float("-inf")).argmax(dim=1)
+        return {"spectrogram": post.transpose(1, 2).contiguous(), "mse": sse / (lens * corpus.n_mel).double(), "cutoff": cutoff}
 
     # ------------------------------------------------------------------ per-shape graph cache (real, ragged batches)
     MAX_SHAPE_GRAPHS = 32          # LJSpeech at pad_base 256: text 1-2 x mel 1-4 multiples x (full | last) batch size
