@@ -792,6 +792,35 @@ int rtts_resample(const void* audio, int in_format, int channels, const int64_t*
                   const int64_t* in_offsets, const int64_t* out_offsets, int nseg, const int32_t* first, const float* taps_table,
                   int orig_red, int new_red, int taps, float* out, void* stream);
 
+/* ---- Vocoder denoiser (the last stage of synthesis in the WaveGlow / SqueezeWave family) -------
+ * Subtracts the vocoder's bias spectrum from the STFT magnitudes of generated audio and resynthesises with the original phase, for
+ * a RAGGED batch of utterances in one launch.  One utterance x of n samples, n_fft = 1024, hop = 256, w = periodic Hann of n_fft,
+ * T = rtts_mel_frames(n, hop) frames, xpad = x reflect-padded by n_fft / 2 on both sides (so n > n_fft / 2):
+ *     X[k][t] = sum_m w[m] xpad[t hop + m] exp(-2 pi i k m / n_fft)                        k = 0 .. n_fft / 2
+ *     g[k][t] = max(|X[k][t]| - strength * bias[k], 0) / |X[k][t]|                         (0 where |X| = 0)
+ *     f[t][m] = irfft(g[.][t] X[.][t])[m]
+ *     y[p]    = sum_t w[q - t hop] f[t][q - t hop] / sum_t w[q - t hop]^2,   q = p + n_fft / 2,   p = 0 .. n - 1
+ * both sums over the frames 0 <= t < T that cover q, in ascending t: torch.istft(torch.stft(x, center=True, pad_mode="reflect") * g,
+ * center=True, length=n).  All arithmetic is f32 (v_mfma_f32_32x32x2_f32, bit for bit a k-ordered fmaf chain, then one fixed-order
+ * sum per sample): an utterance's output is bitwise the same alone and anywhere in a batch, and from call to call.
+ *   audio, out      f32, the utterances end to end over the SAME offsets: utterance s is samples [sample_offsets[s], sample_offsets[s+1])
+ *                   of both (what rtts_resample writes, rtts_mel_spectrogram reads and the ragged vocoder returns).  out must not
+ *                   overlap audio (a workgroup reads the input of its neighbours' samples); samples outside the offsets are
+ *                   neither read nor written
+ *   sample_offsets  i64 (nseg + 1): the DEVICE table the kernel reads, and the same values in sample_offsets_host, which the entry
+ *                   point validates and sizes the grid by.  The two copies MUST hold the same values, as for rtts_mel_spectrogram
+ *   dft_basis       f32 (n_fft, n_fft), the basis of rtts_mel_spectrogram (analysis window folded in; column 0 is the window)
+ *   idft_basis      f32 (n_fft, n_fft) row-major, its inverse with the synthesis window folded in: row = column of dft_basis,
+ *                   column m = sample of the frame: w[m] / n_fft for bin 0, w[m] cos(pi m) / n_fft for the Nyquist row n_fft / 2,
+ *                   2 w[m] cos(2 pi k m / n_fft) / n_fft and 2 w[m] sin(2 pi k m / n_fft) / n_fft for rows k and n_fft / 2 + k
+ *                   (dataset/audio.py idft_basis: float64 on the host, rounded once)
+ *   bias            f32 (n_fft / 2 + 1), the vocoder's bias magnitudes per bin, device
+ * Supported: n_fft = 1024, hop = 256, 1 <= nseg <= 65535, strength finite and >= 0, every utterance longer than n_fft / 2.  Anything
+ * else, a null pointer or an out that overlaps audio is rejected before any launch. */
+int rtts_denoise(const float* audio, const int64_t* sample_offsets_host, const int64_t* sample_offsets, int nseg,
+                 const float* dft_basis, const float* idft_basis, const float* bias /* n_fft/2+1 */, float strength, int n_fft,
+                 int hop, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,7 @@ SIGNATURES = {
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
     "rtts_resample_len": [_i64, _i32, _i32],
     "rtts_resample": [_vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "rtts_denoise": [_vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp],
 }
 
 _lib = None

@@ -84,11 +84,11 @@ def hann_window(win_length: int, n_fft: int) -> np.ndarray:
     return w
 
 
-def dft_basis(n_fft: int, win_length: int) -> torch.Tensor:
+def dft_basis(n_fft: int, win_length: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """f32 (n_fft, n_fft), the ``dft_basis`` of ``rtts_mel_spectrogram``: row n = sample of the frame, window folded in;
     column k < n_fft/2 = w[n] cos(2 pi n k / n_fft), column n_fft/2 + k = w[n] sin(2 pi n k / n_fft) (1 <= k < n_fft/2), column
     n_fft/2 = w[n] cos(pi n), the Nyquist bin.  Built in float64 with the angle reduced in integers ((n k) mod n_fft, so every
-    argument lies in [0, 2 pi)), rounded once to f32."""
+    argument lies in [0, 2 pi)), rounded once to f32 (``dtype=torch.float64``: the unrounded matrix)."""
     half = n_fft // 2
     n = np.arange(n_fft, dtype=np.int64)[:, None]
     k = np.arange(half, dtype=np.int64)[None, :]
@@ -98,7 +98,27 @@ def dft_basis(n_fft: int, win_length: int) -> torch.Tensor:
     basis[:, half:] = np.sin(ang)
     basis[:, half] = 1.0 - 2.0 * (np.arange(n_fft) % 2)           # cos(pi n), exactly
     basis *= hann_window(win_length, n_fft)[:, None]
-    return torch.from_numpy(basis.astype(np.float32))
+    return torch.from_numpy(basis.astype(np.float32)) if dtype == torch.float32 else torch.from_numpy(basis).to(dtype)
+
+
+def idft_basis(n_fft: int, win_length: int, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """f32 (n_fft, n_fft), the ``idft_basis`` of ``rtts_denoise``: the inverse of the real DFT in the column order of ``dft_basis``,
+    with the synthesis window folded in.  Row = column of ``dft_basis``, column m = sample of the frame: row 0 = w[m] / n_fft,
+    row n_fft/2 = w[m] cos(pi m) / n_fft (the Nyquist bin), row k = 2 w[m] cos(2 pi k m / n_fft) / n_fft and row n_fft/2 + k =
+    2 w[m] sin(2 pi k m / n_fft) / n_fft for 1 <= k < n_fft/2.  So ``dft_basis @ idft_basis = diag(w) diag(w)``: a frame goes
+    through both windows and nothing else.  Angles reduced in integers, float64, rounded once to f32, as ``dft_basis``
+    (``dtype=torch.float64``: the unrounded matrix)."""
+    half = n_fft // 2
+    m = np.arange(n_fft, dtype=np.int64)[None, :]
+    k = np.arange(half, dtype=np.int64)[:, None]
+    ang = (2.0 * np.pi / n_fft) * ((k * m) % n_fft).astype(np.float64)
+    inv = np.empty((n_fft, n_fft), dtype=np.float64)
+    inv[:half] = 2.0 * np.cos(ang)
+    inv[half:] = 2.0 * np.sin(ang)
+    inv[0] = 1.0
+    inv[half] = 1.0 - 2.0 * (np.arange(n_fft) % 2)                # cos(pi m), exactly
+    inv *= hann_window(win_length, n_fft)[None, :] / n_fft
+    return torch.from_numpy(inv.astype(np.float32)) if dtype == torch.float32 else torch.from_numpy(inv).to(dtype)
 
 
 def mel_frames(n_samples: int, hop_length: int) -> int:

@@ -271,6 +271,32 @@ def resample(audio: torch.Tensor, in_offsets_host, out_offsets_host, offsets: to
     return out
 
 
+def denoise(audio: torch.Tensor, sample_offsets_host, offsets: torch.Tensor, nseg: int, dft_basis: torch.Tensor,
+            idft_basis: torch.Tensor, bias: torch.Tensor, strength: float, n_fft: int, hop: int, out: torch.Tensor) -> torch.Tensor:
+    """audio: the utterances end to end (flat f32); offsets: (nseg + 1,) i64 device table of sample offsets and the same values as
+    a host ``ctypes.c_int64`` array; dft_basis / idft_basis (n_fft, n_fft) f32 from ``dataset.audio``; bias (n_fft/2 + 1,) f32 ->
+    out, flat f32 over the same offsets (it must not overlap audio) = each utterance with ``strength * bias`` taken off its STFT
+    magnitudes: one ``rtts_denoise`` launch on the current stream."""
+    for name, t in (("audio", audio), ("dft_basis", dft_basis), ("idft_basis", idft_basis), ("bias", bias), ("out", out)):
+        if not (t.is_cuda and t.dtype == torch.float32):
+            raise _lib.RttsError(f"denoise runs on the GPU only: {name} must be a CUDA float32 tensor (got {t.dtype} on {t.device})")
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.shape == (nseg + 1,) and offsets.is_contiguous()):
+        raise ValueError(f"offsets: expected a contiguous CUDA int64 ({nseg + 1},) table")
+    if not (audio.dim() == 1 and audio.is_contiguous() and out.dim() == 1 and out.is_contiguous() and dft_basis.is_contiguous()
+            and idft_basis.is_contiguous() and tuple(dft_basis.shape) == (n_fft, n_fft) and tuple(idft_basis.shape) == (n_fft, n_fft)):
+        raise ValueError("denoise: audio and out flat, dft_basis and idft_basis (n_fft, n_fft)")
+    if not (bias.dim() == 1 and bias.is_contiguous() and bias.numel() == n_fft // 2 + 1):
+        raise ValueError(f"denoise: bias must hold n_fft / 2 + 1 = {n_fft // 2 + 1} magnitudes (got shape {tuple(bias.shape)})")
+    if audio.numel() < sample_offsets_host[nseg] or out.numel() < sample_offsets_host[nseg]:
+        raise ValueError(f"denoise: {audio.numel()} input / {out.numel()} output samples for offsets ending at {sample_offsets_host[nseg]}")
+    frames = sum((sample_offsets_host[s + 1] - sample_offsets_host[s]) // hop + 1 for s in range(nseg)) if hop > 0 else 0
+    ev = TIMING.start(f"rtts_denoise/n{n_fft}")
+    _lib.call("rtts_denoise", audio.data_ptr(), sample_offsets_host, offsets.data_ptr(), nseg, dft_basis.data_ptr(), idft_basis.data_ptr(),
+              bias.data_ptr(), float(strength), n_fft, hop, out.data_ptr(), _stream())
+    TIMING.stop(ev, 4.0 * frames * n_fft * n_fft)
+    return out
+
+
 def sw_inv1x1_factor(weights) -> Tuple[list, torch.Tensor]:
     """The invertible 1x1 convolutions of a SqueezeWave factored on the device: ``weights`` = CUDA float32 (n, n) contiguous
     matrices, 1 <= n <= 128 -> (their inverses, fp32 rounded once from the float64 elimination; slogdet (len, 2) float64 on the

@@ -55,25 +55,34 @@ def capacity_frames(total: int) -> int:
 
 
 def vocode_trimmed(vocoder, spectrogram: torch.Tensor, stop, *, sigma: float = 0.6, noise=None, use_graph: bool = False,
-                   max_len: Optional[int] = None) -> List[torch.Tensor]:
+                   max_len: Optional[int] = None, denoiser=None, denoiser_strength: float = 0.01) -> List[torch.Tensor]:
     """The step after ``infer``: utterance i of ``spectrogram`` (B, n_mel, L) keeps ``frame_counts(stop, L)[i]`` frames and
     is vocoded as ``vocoder.infer(spectrogram[i:i+1, :, :frames_i])`` would vocode it -> B waveforms of 256 * frames_i
     samples.  ``stop``: (B,) on any device (read back once).  ``noise``: per-utterance draws (``noise_shapes(1, frames_i)``
     each; eager path only).  ``use_graph``: replay the vocoder's ``capture_ragged`` graph for the bucket
-    ``capacity_frames(sum frames)`` (captured on first use, then reused)."""
+    ``capacity_frames(sum frames)`` (captured on first use, then reused).  ``denoiser``: a ``squeeze_wave.denoiser.Denoiser``;
+    the packed audio the vocoder wrote goes through its ``forward_packed(strength=denoiser_strength)`` -- one more launch --
+    before it is split, so every waveform is what ``denoiser.forward`` makes of the waveform without it (utterances of one or
+    two frames are too short to denoise and come back as vocoded)."""
     frames = frame_counts(stop.cpu() if torch.is_tensor(stop) else stop, spectrogram.shape[2], max_len)
     if not use_graph or noise is not None or sum(frames) == 0:
-        _, waves = vocoder.infer_ragged(spectrogram, frames, sigma=sigma, noise=noise)
-        return waves
+        packed, waves = vocoder.infer_ragged(spectrogram, frames, sigma=sigma, noise=noise)
+        if denoiser is None or sum(frames) == 0:
+            return waves
+        packed, _ = denoiser.forward_packed(packed, [256 * n for n in frames], strength=denoiser_strength)
+        return vocoder.split_packed(packed, segment_offsets(frames))
     run = vocoder.capture_ragged(len(frames), capacity_frames(sum(frames)), sigma=sigma)
     out, _ = run(spectrogram, frames)
-    out = out.clone()                                  # the graph's buffer is overwritten by its next replay
+    if denoiser is None:
+        out = out.clone()                              # the graph's buffer is overwritten by its next replay
+    else:                                              # read from the graph's buffer, written to a tensor of its own
+        out, _ = denoiser.forward_packed(out, [256 * n for n in frames], strength=denoiser_strength)
     return vocoder.split_packed(out, segment_offsets(frames))
 
 
 @torch.no_grad()
 def synthesize(tts, vocoder, phonemes: Sequence[torch.Tensor], *, sigma: float = 0.6, use_graph: bool = False,
-               **infer_kwargs) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
+               denoiser=None, denoiser_strength: float = 0.01, **infer_kwargs) -> Tuple[List[torch.Tensor], torch.Tensor, torch.Tensor]:
     """Text -> audio for B utterances: ``phonemes`` (list of 1-D id tensors) -> (B waveforms in [-1, 1] of 256 * frames_i
     samples, the spectrogram (B, n_mel, L) of ``tts.infer``, its stop indices (B,)).
 
@@ -81,10 +90,12 @@ def synthesize(tts, vocoder, phonemes: Sequence[torch.Tensor], *, sigma: float =
     max_len, stop_threshold, ... -- pass through), the per-utterance trim of ``cli.py:241`` (``frame_counts``), and one
     ragged vocoder call.  ``use_graph=True``: the graphed generation loop ("concat") and a ``capture_ragged`` vocoder graph
     per capacity bucket, cached on the vocoder; between the stages the host only reads the B stop indices (they size the
-    waveforms), and the offset table goes to the device without waiting for it."""
+    waveforms), and the offset table goes to the device without waiting for it.  ``denoiser`` / ``denoiser_strength``: see
+    ``vocode_trimmed``; the default ``None`` leaves the vocoder's audio as it is."""
     batch = pad_phonemes(phonemes)
     spectrogram, stop = tts.infer(batch, use_graph=use_graph, **infer_kwargs)
-    waves = vocode_trimmed(vocoder, spectrogram, stop, sigma=sigma, use_graph=use_graph, max_len=infer_kwargs.get("max_len"))
+    waves = vocode_trimmed(vocoder, spectrogram, stop, sigma=sigma, use_graph=use_graph, max_len=infer_kwargs.get("max_len"),
+                           denoiser=denoiser, denoiser_strength=denoiser_strength)
     return waves, spectrogram, stop
 
 
