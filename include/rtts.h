@@ -236,6 +236,11 @@ int rtts_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
  *   normaliser; the backward gives every chunk its own workgroups (P = exp(s - lse) needs only the forward's lse), which
  *   write their shares of dQ to dq_chunks (chunks, B*Tq, H*dh) bf16 -- summed into dq (ld_dq == H*dh) by the same call;
  *   one chunk: dq_chunks may be NULL
+ *   dh = 64 or 128 (nn.MultiheadAttention num_heads 8 or 4 at embedding_dim 512; the reference's
+ *   config/legacy/attention-depth-3-heads-4.yml and attention-depth-3-heads-3.yml set num_heads 4); the score scale is
+ *   1 / sqrt(dh).  At dh = 128 the backward holds 128 keys at a time, so the number of chunks its dq_chunks needs is
+ *   rtts_xattn_bwd_key_chunks(T_k, dh) = T_k / 128 (dh = 64: rtts_xattn_key_chunks(T_k)); -1 outside the envelope (T_k a
+ *   multiple of 128 up to 2048, dh 64 or 128).  rtts_lsh_bwd_delta takes dh = 128 for this delta.
  *   A sample WITHOUT ANY valid key (kvalid all 0): its normaliser is 0, so rtts_xattn_fwd writes o = NaN (0 * inf) and
  *   lse = -inf for its rows, as nn.MultiheadAttention does; rtts_lsh_bwd_delta then gives delta = NaN and rtts_xattn_bwd
  *   dq = NaN and dk = NaN (dS = P * (dP - delta) with P = 0, delta = NaN), while dv is exactly 0 (P is taken as 0 where
@@ -243,6 +248,7 @@ int rtts_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
  *   batch are bit-identical to a call in which that sample has valid keys (tests/test_xattn_hip.py).  A padded key of a
  *   sample that has valid keys gets dk = dv = 0 exactly. */
 int rtts_xattn_key_chunks(int Tk);
+int rtts_xattn_bwd_key_chunks(int Tk, int dh);
 int rtts_xattn_fwd(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
                    int B, int H, int Tq, int Tk, int dh, void* o, int64_t ld_o, float* lse,
                    float drop_p, uint32_t seed, const uint32_t* seed_dev, void* stream);

@@ -60,6 +60,8 @@ __global__ __launch_bounds__(256) void lsh_combine_fwd_kernel(const bf16_t* __re
     if (piece == 0) lse_tot[row] = m + logf(wsum);
 }
 
+// DH = 128 (the cross attention's wide heads): the row's 8 lanes take two 16-byte pieces each, 64 columns apart
+template <int DH>
 __global__ __launch_bounds__(256) void lsh_bwd_delta_kernel(const bf16_t* __restrict__ out, int64_t ld_out,
                                                             const bf16_t* __restrict__ dout, int64_t ld_do, int H, int T,
                                                             size_t rows, float* __restrict__ delta) {
@@ -70,11 +72,14 @@ __global__ __launch_bounds__(256) void lsh_bwd_delta_kernel(const bf16_t* __rest
     if (row < rows) {
         const int bh = row / T, t = row % T;
         const int b = bh / H, h = bh % H;
-        float a[8], g[8];
-        unpack8(*reinterpret_cast<const uint4*>(out + ((size_t)b * T + t) * ld_out + h * CB_DH + piece * 8), a);
-        unpack8(*reinterpret_cast<const uint4*>(dout + ((size_t)b * T + t) * ld_do + h * CB_DH + piece * 8), g);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) s = __builtin_fmaf(a[k], g[k], s);
+        for (int pl = 0; pl < DH / 64; ++pl) {
+            float a[8], g[8];
+            unpack8(*reinterpret_cast<const uint4*>(out + ((size_t)b * T + t) * ld_out + h * DH + pl * 64 + piece * 8), a);
+            unpack8(*reinterpret_cast<const uint4*>(dout + ((size_t)b * T + t) * ld_do + h * DH + pl * 64 + piece * 8), g);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s = __builtin_fmaf(a[k], g[k], s);
+        }
     }
     s = rtts_sum8(s);
     if (row < rows && piece == 0) delta[row] = s;
@@ -130,14 +135,18 @@ extern "C" int rtts_lsh_bwd_delta(const void* out, int64_t ld_out, const void* d
                                   float* delta, void* stream) {
     RTTS_ENTER(stream);
     RTTS_REQUIRE(out && dout && delta, "rtts_lsh_bwd_delta: null pointer");
-    RTTS_REQUIRE(dh == CB_DH && B > 0 && H > 0 && T > 0, "rtts_lsh_bwd_delta: need dh == 64");
+    RTTS_REQUIRE((dh == CB_DH || dh == 128) && B > 0 && H > 0 && T > 0, "rtts_lsh_bwd_delta: need dh == 64 or 128");
     RTTS_REQUIRE(ld_out >= (int64_t)H * dh && ld_out % 8 == 0 && ld_dout >= (int64_t)H * dh && ld_dout % 8 == 0,
                  "rtts_lsh_bwd_delta: bad strides");
     RTTS_REQUIRE((((uintptr_t)out | (uintptr_t)dout) & 15) == 0, "rtts_lsh_bwd_delta: buffers must be 16-byte aligned");
     const size_t rows = (size_t)B * H * T;
     const unsigned grid = (unsigned)((rows * 8 + 255) / 256);
-    hipLaunchKernelGGL(lsh_bwd_delta_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)out, ld_out,
-                       (const bf16_t*)dout, ld_dout, H, T, rows, delta);
+    if (dh == 128)
+        hipLaunchKernelGGL(lsh_bwd_delta_kernel<128>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)out, ld_out,
+                           (const bf16_t*)dout, ld_dout, H, T, rows, delta);
+    else
+        hipLaunchKernelGGL(lsh_bwd_delta_kernel<CB_DH>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)out, ld_out,
+                           (const bf16_t*)dout, ld_dout, H, T, rows, delta);
     RTTS_LAUNCH_CHECK("rtts_lsh_bwd_delta");
     return 0;
 }

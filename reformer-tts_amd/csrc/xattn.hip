@@ -1,5 +1,7 @@
 // Dense encoder-decoder ("cross") attention, forward and backward, for short key sequences
 // (T_k = 128 or 256 keys held entirely on chip; the text side of Reformer-TTS is padded to 256).
+// Head width DH is a template parameter: 64 (num_heads 8 at embedding_dim 512) and 128 (num_heads 4: the reference's
+// config/legacy/attention-depth-3-heads-4.yml and attention-depth-3-heads-3.yml).
 //
 // Replaces nn.MultiheadAttention as wrapped by MultiheadAttentionWrapper
 // (/root/reference/reformer_tts/model/reformer.py:161-186): scores = (q W_q)(k W_k)^T / sqrt(dh),
@@ -7,14 +9,13 @@
 //
 // Same MFMA dataflow as the LSH chunk kernels (lsh_attn_fwd.hip / lsh_attn_bwd.hip):
 //   forward : lane = query, S^T = K Q^T, in-register softmax over all keys, O^T = V^T P^T
-//   backward: lane = key, wave w owns keys [64w, 64w+64): dV, dK complete in registers for the
+//   backward: lane = key, wave w owns keys [32w, 32w+32) of the chunk (XA_KT2 = 1): dV, dK complete in registers for the
 //             workgroup's 128 queries; dS^T crosses LDS once for dQ^T = K^T dS^T.  dK/dV of the
 //             T_q/128 query blocks are written as partial slabs and summed by rtts_sum_slabs
 //             (deterministic, no atomics).
 #include "rtts_common.h"
 #include <float.h>
 
-#define XA_DH 64
 #define XA_ROWB 144
 #define XA_QB 128     // queries per workgroup
 #ifndef XA_UNROLL
@@ -36,6 +37,19 @@ __device__ __forceinline__ bf16x8 xa_tr_frag(const unsigned char* p0, const unsi
 // ds_read_b64_tr_b16 of 4 consecutive rows x 64 B are both conflict free; the dS^T image [key][128 queries] swizzles its
 // 8-byte granules by the key (conflict-free 8-byte stores of 16 consecutive keys and transposed reads of 4 keys x 64 B;
 // the padded 272-byte rows were 4-way conflicted on the read side).
+//
+// DH = 128 (256-byte rows).  A row is NOT stored as 256 contiguous bytes: every image is DH / 64 PLANES, plane p = columns
+// [64 p, 64 p + 64) of every row as a [rows][128 B] image of its own, swizzled by xa_off exactly as above.  The bank arithmetic:
+// a bank is (byte address / 4) mod 64, i.e. the address mod 256; a plane is rows x 128 B with rows a multiple of 128, so every
+// plane starts at a multiple of 16 KB and address mod 256 of (plane, row, piece) equals that of (row, piece) in the 64 kernels.
+// Every LDS instruction of these kernels addresses ONE plane (a 32x32x16 MFMA fragment is 16 or 8 consecutive dh values, which
+// never straddle a multiple of 64; a DMA wave-instruction fills 8 half-rows of one plane; the staging image holds 64 columns at a
+// time), so each instruction sees the bank pattern derived for 128-byte rows: ds_read_b128 of one piece from 16 rows, the
+// transposed read of 4 rows x 64 B, the 8-byte staging stores and 16-byte staging reads are all conflict free (degree 1), as at
+// DH = 64.  (Contiguous 256-byte rows start every row at bank 0: an unswizzled piece from 16 rows would be a 16-way conflict and the
+// 3-bit xa_sw cannot spread 16 rows over the 16 pieces of such a row; the planes keep the derivation that is already tested.)
+// The dS^T image [key][128 queries] does not depend on DH.  On the global side a half-row is one full 128-byte line, so the DMA
+// loads stay line-sized.
 __device__ __forceinline__ int xa_sw(int row) { return ((row >> 1) & 3) | ((((row >> 3) ^ (row >> 1)) & 1) << 2); }
 __device__ __forceinline__ int xa_off(int row, int piece) { return row * 128 + ((piece ^ xa_sw(row)) << 4); }
 __device__ __forceinline__ int xa_ds_off(int key, int gran) {
@@ -61,7 +75,7 @@ __device__ __forceinline__ int xa_ds_off(int key, int gran) {
 __device__ __forceinline__ int xa_stg_w(int r, int piece, int hh) { return r * 128 + ((piece ^ (r & 7)) << 4) + ((hh ^ ((r >> 3) & 1)) << 3); }
 __device__ __forceinline__ int xa_stg_r(int i, int srow, int spiece) { return (i * 8 + srow) * 128 + ((spiece ^ srow) << 4); }
 // acc[dt][4 g + j] of lane (r, hh) = element (row r, dh = 32 dt + 8 g + 4 hh + j), times `mul`  ->  32 rows of 64 bf16 at
-// dst + row * ld (16-byte aligned rows), through the wave-private 4 KB image `stg`
+// dst + row * ld (16-byte aligned rows), through the wave-private 4 KB image `stg` (DH = 128: once per 64-column plane)
 __device__ __forceinline__ void xa_store_rows(unsigned char* stg, const f32x16 (&acc)[2], float mul, bf16_t* dst, int64_t ld, int lane) {
     const int r = lane & 31, hh = lane >> 5, srow = lane >> 3, spiece = lane & 7;
 #pragma unroll
@@ -85,7 +99,34 @@ __device__ __forceinline__ void xa_store_rows(unsigned char* stg, const f32x16 (
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int TK, bool MULTI>
+// score scale 1 / sqrt(DH), applied in fp32
+template <int DH> struct xa_dh {
+    static_assert(DH == 64 || DH == 128, "head width 64 or 128");
+    static constexpr float scale = DH == 64 ? 0.125f : 0.08838834764831845f;
+    static constexpr int NP = DH / 64;       // 64-column planes of an LDS image
+    static constexpr int NKS = DH / 16;      // 16-wide k steps of a Q K^T product
+    static constexpr int NDT = DH / 32;      // 32-wide dh tiles of an output
+};
+
+// XA_PLANES(NP, statements): the statements once per 64-column plane, `pl` a constant.  Written without a loop (and the second
+// plane under `if constexpr`) so that the DH = 64 instantiations stay, statement for statement, the kernels they were before
+// the head width became a template parameter: their optimized IR is identical to the pre-template kernels'.
+#define XA_PLANES(NP_, ...)                  \
+    do {                                     \
+        {                                    \
+            constexpr int pl = 0;            \
+            __VA_ARGS__                      \
+        }                                    \
+        if constexpr ((NP_) == 2) {          \
+            constexpr int pl = 1;            \
+            __VA_ARGS__                      \
+        }                                    \
+    } while (0)
+
+// LDS per workgroup: 2 x TK x 2 DH bytes (K, V) + 4 TK (validity words): 33 / 66 KB at DH = 64 (TK = 128 / 256), 66 / 129 KB at
+// DH = 128, of the CU's 160 KB.  DH = 128 holds 256 keys only in the single-pass form (T_k = 256: 156 VGPRs + 128 AGPRs); its
+// chunk-walking form is instantiated for 128 keys alone (xa_fwd_chunk), where it needs no scratch (247 + 112 registers)
+template <int DH, int TK, bool MULTI>
 __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
                                                         int64_t ld_kv, const uint8_t* __restrict__ kvalid, int H, int Tq, int TKtot_,
                                                         bf16_t* __restrict__ o, int64_t ld_o, float* __restrict__ lse,
@@ -96,47 +137,50 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
     // and the kernel is the single-pass softmax (two waves per SIMD; the general form needs one wave's worth of registers more)
     const int TKtot = MULTI ? TKtot_ : TK;
     constexpr int NKT = TK / 32;
+    constexpr int NP = xa_dh<DH>::NP, NKS = xa_dh<DH>::NKS, PLANE = TK * 128;
+    constexpr float SC = xa_dh<DH>::scale;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* Ks = smem;                       // [TK][128] swizzled (xa_off), like V
-    unsigned char* Vs = Ks + TK * 128;
-    int* kval = reinterpret_cast<int*>(Vs + TK * 128);
+    unsigned char* Ks = smem;                       // [NP][TK][128] swizzled (xa_off), like V
+    unsigned char* Vs = Ks + NP * PLANE;
+    int* kval = reinterpret_cast<int*>(Vs + NP * PLANE);
 
     const int nqb = Tq / XA_QB;
     const uint32_t wi = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = wi / nqb, qb = wi % nqb;
     const int b = bh / H, h = bh % H;
-    const int d = H * XA_DH;
+    const int d = H * DH;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
 
     // Q fragments straight from global: lane (r, hh) holds Q[q0 + r][16 ks + 8 hh .. +8]
     const int qrow = qb * XA_QB + wave * 32 + r;
-    const bf16_t* qptr = q + ((size_t)b * Tq + qrow) * ld_q + (size_t)h * XA_DH;
-    bf16x8 qf[4];
+    const bf16_t* qptr = q + ((size_t)b * Tq + qrow) * ld_q + (size_t)h * DH;
+    bf16x8 qf[NKS];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qptr + ks * 16 + 8 * hh);
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qptr + ks * 16 + 8 * hh);
     if (thresh && seed_dev) seed += seed_dev[0];
 
     float m_run = -FLT_MAX, l_run = 0.f;
-    f32x16 oacc[2] = {{0}, {0}};
+    f32x16 oacc[NP][2] = {};
     const int trq = (lane & 15) >> 2, trp = lane & 3, trc = (lane >> 4) & 1;
 #pragma unroll 1
     for (int c0 = 0; c0 < TKtot; c0 += TK) {
-        const bf16_t* kbase = kv + ((size_t)b * TKtot + c0) * ld_kv + (size_t)h * XA_DH;
+        const bf16_t* kbase = kv + ((size_t)b * TKtot + c0) * ld_kv + (size_t)h * DH;
         const bf16_t* vbase = kbase + d;
         if (c0) __syncthreads();        // every wave is done with the previous chunk's images
         // K and V rows go global -> LDS by DMA (no staging registers, no ds_write pass): one wave-instruction fills 8 consecutive
-        // 128-byte rows in lane order, so the swizzle goes on the SOURCE side (lsh_attn_bwd.hip's gather)
+        // 128-byte rows (of one plane) in lane order, so the swizzle goes on the SOURCE side (lsh_attn_bwd.hip's gather)
         constexpr int ITERS = TK * 8 / 256;
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int rowb = it * 32 + wave * 8;                     // wave-uniform: first row of this instruction
             const int row = rowb + (lane >> 3);
             const int lp = (lane & 7) ^ xa_sw(row);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + (size_t)row * ld_kv + lp * 8),
-                                             (RTTS_LDS void*)(Ks + rowb * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + (size_t)row * ld_kv + lp * 8),
-                                             (RTTS_LDS void*)(Vs + rowb * 128), 16, 0, 0);
+            XA_PLANES(NP,
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)row * ld_kv + lp * 8),
+                                                 (RTTS_LDS void*)(Ks + pl * PLANE + rowb * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + pl * 64 + (size_t)row * ld_kv + lp * 8),
+                                                 (RTTS_LDS void*)(Vs + pl * PLANE + rowb * 128), 16, 0, 0););
         }
         for (int j = tid; j < TK; j += 256) kval[j] = kvalid ? (int)kvalid[(size_t)b * TKtot + c0 + j] : 1;
         __syncthreads();
@@ -145,11 +189,12 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             f32x16 acc = {0};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + xa_off(kt * 32 + r, ks * 2 + hh));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
-            }
+            XA_PLANES(NP,
+                _Pragma("unroll")
+                for (int ks = 0; ks < 4; ++ks) {
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + xa_off(kt * 32 + r, ks * 2 + hh));
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[pl * 4 + ks], acc, 0, 0, 0);
+                });
             s[kt] = acc;
         }
         float m = -FLT_MAX;
@@ -161,7 +206,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
                 const int vv[4] = {kvv.x, kvv.y, kvv.z, kvv.w};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float x = vv[j] ? s[kt][4 * g + j] * 0.125f : -FLT_MAX;
+                    const float x = vv[j] ? s[kt][4 * g + j] * SC : -FLT_MAX;
                     s[kt][4 * g + j] = x;
                     m = fmaxf(m, x);
                 }
@@ -182,10 +227,11 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
         l_run = l_run * alpha + rtts_xhalf_sum(l);
         m_run = m;
         if (c0) {
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oacc[dt][i] *= alpha;
+            XA_PLANES(NP,
+                _Pragma("unroll")
+                for (int dt = 0; dt < 2; ++dt)
+                    _Pragma("unroll")
+                    for (int i = 0; i < 16; ++i) oacc[pl][dt][i] *= alpha;);
         }
         if (thresh) {
             // nn.MultiheadAttention(dropout=p): dropout on the NORMALISED probabilities; the normaliser is the full one, the
@@ -204,31 +250,35 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
                 const int o8 = 8 * s2;
                 const bf16x8 pf = cvt_bf16x8(s[kt][o8], s[kt][o8 + 1], s[kt][o8 + 2], s[kt][o8 + 3], s[kt][o8 + 4], s[kt][o8 + 5],
                                              s[kt][o8 + 6], s[kt][o8 + 7]);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const int blk = (kt * 32 + 16 * s2) * 128;
-                    const int t0 = xa_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
-                    const int t1 = xa_off(4 * hh + trq, (dt ^ 1) * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);   // row + 8: sw flips bit 2
-                    const bf16x8 vf = xa_tr_frag(Vs + blk + t0, Vs + blk + 8 * 128 + t1);
-                    oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[dt], 0, 0, 0);
-                }
+                XA_PLANES(NP,
+                    _Pragma("unroll")
+                    for (int dt = 0; dt < 2; ++dt) {
+                        const int blk = (kt * 32 + 16 * s2) * 128;
+                        const int t0 = xa_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+                        const int t1 = xa_off(4 * hh + trq, (dt ^ 1) * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);   /* row + 8: sw flips bit 2 */
+                        const bf16x8 vf = xa_tr_frag(Vs + pl * PLANE + blk + t0, Vs + pl * PLANE + blk + 8 * 128 + t1);
+                        oacc[pl][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[pl][dt], 0, 0, 0);
+                    });
             }
     }
     const float inv_l = 1.f / l_run;
 #if XA_STAGED
     __syncthreads();                 // every wave is done with the K image: it becomes the waves' row staging (4 KB each)
-    xa_store_rows(Ks + wave * 4096, oacc, inv_l, o + ((size_t)b * Tq + qb * XA_QB + wave * 32) * ld_o + (size_t)h * XA_DH, ld_o, lane);
+    XA_PLANES(NP, xa_store_rows(Ks + wave * 4096, oacc[pl], inv_l,
+                                o + ((size_t)b * Tq + qb * XA_QB + wave * 32) * ld_o + (size_t)h * DH + pl * 64, ld_o, lane););
 #else
-    bf16_t* optr = o + ((size_t)b * Tq + qrow) * ld_o + (size_t)h * XA_DH;
+    bf16_t* optr = o + ((size_t)b * Tq + qrow) * ld_o + (size_t)h * DH;
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
+    for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint2 pk;
-            pk.x = pack_bf16x2(oacc[dt][4 * g] * inv_l, oacc[dt][4 * g + 1] * inv_l);
-            pk.y = pack_bf16x2(oacc[dt][4 * g + 2] * inv_l, oacc[dt][4 * g + 3] * inv_l);
-            *reinterpret_cast<uint2*>(optr + dt * 32 + 8 * g + 4 * hh) = pk;
-        }
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                uint2 pk;
+                pk.x = pack_bf16x2(oacc[pl][dt][4 * g] * inv_l, oacc[pl][dt][4 * g + 1] * inv_l);
+                pk.y = pack_bf16x2(oacc[pl][dt][4 * g + 2] * inv_l, oacc[pl][dt][4 * g + 3] * inv_l);
+                *reinterpret_cast<uint2*>(optr + pl * 64 + dt * 32 + 8 * g + 4 * hh) = pk;
+            }
 #endif
     if (hh == 0) lse[(size_t)bh * Tq + qrow] = m_run + logf(l_run);
 }
@@ -239,7 +289,10 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
 #ifndef XA_KT2
 #define XA_KT2 1
 #endif
-template <int TK, bool DROP>
+// DH = 128 is instantiated for TK = 128 only (rtts_xattn_bwd_key_chunks): four waves of 32 keys hold dK and dV in 2 x 64 fp32 per
+// lane, the accumulator count of a 64-key wave at DH = 64, and the images are K 32 KB + Q, dout 2 x 32 KB + dS^T 32 KB + 1 KB of
+// lse / delta = 129 KB of the CU's 160 KB (TK = 256 would need 64 + 64 + 64 KB).  DH = 64: 65 KB (TK = 128), 129 KB (TK = 256).
+template <int DH, int TK, bool DROP>
 __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
                                                        int64_t ld_kv, const uint8_t* __restrict__ kvalid,
                                                        const bf16_t* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
@@ -257,11 +310,14 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     constexpr int NW = NTHR / 64;
     if (DROP && seed_dev) seed += seed_dev[0];
     constexpr int DSROW = XA_QB * 2;
+    constexpr int NP = xa_dh<DH>::NP, NKS = xa_dh<DH>::NKS, NDT = xa_dh<DH>::NDT, KPL = TK * 128, QPL = XA_QB * 128;
+    constexpr float SC = xa_dh<DH>::scale;
+    static_assert(DH == 64 || TK == 128, "DH = 128 works in 128-key chunks");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* Ks = smem;                        // [TK][128]   swizzled
-    unsigned char* Qs = Ks + TK * 128;               // [128][128]  swizzled
-    unsigned char* Os = Qs + XA_QB * 128;            // [128][128]  swizzled
-    unsigned char* Ds = Os + XA_QB * 128;            // [TK][256]   dS^T (already * scale), swizzled
+    unsigned char* Ks = smem;                        // [NP][TK][128]   swizzled
+    unsigned char* Qs = Ks + NP * KPL;               // [NP][128][128]  swizzled
+    unsigned char* Os = Qs + NP * QPL;               // [NP][128][128]  swizzled
+    unsigned char* Ds = Os + NP * QPL;               // [TK][256]   dS^T (already * scale), swizzled
     float* qlse = reinterpret_cast<float*>(Ds + TK * DSROW);
     float* qdel = qlse + XA_QB;
 
@@ -269,32 +325,34 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     const uint32_t wi = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = wi / nqb, qb = wi % nqb;
     const int b = bh / H, h = bh % H;
-    const int d = H * XA_DH;
+    const int d = H * DH;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
 
-    const bf16_t* kbase = kv + ((size_t)b * TKtot + kc0) * ld_kv + (size_t)h * XA_DH;
+    const bf16_t* kbase = kv + ((size_t)b * TKtot + kc0) * ld_kv + (size_t)h * DH;
     const bf16_t* vbase = kbase + d;
-    const bf16_t* qbase = q + ((size_t)b * Tq + (size_t)qb * XA_QB) * ld_q + (size_t)h * XA_DH;
-    const bf16_t* dobase = dout + ((size_t)b * Tq + (size_t)qb * XA_QB) * ld_do + (size_t)h * XA_DH;
+    const bf16_t* qbase = q + ((size_t)b * Tq + (size_t)qb * XA_QB) * ld_q + (size_t)h * DH;
+    const bf16_t* dobase = dout + ((size_t)b * Tq + (size_t)qb * XA_QB) * ld_do + (size_t)h * DH;
 
-    // images by LDS-DMA (one wave-instruction = 8 rows of 128 B in lane order, the swizzle on the SOURCE side)
+    // images by LDS-DMA (one wave-instruction = 8 rows of 128 B of one plane in lane order, the swizzle on the SOURCE side)
     {
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 #pragma unroll
         for (int it = 0; it < TK * 8 / NTHR; ++it) {
             const int rowb = it * (NTHR / 8) + wv * 8, row = rowb + (lane >> 3);
             const int lp = (lane & 7) ^ xa_sw(row);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + (size_t)row * ld_kv + lp * 8),
-                                             (RTTS_LDS void*)(Ks + rowb * 128), 16, 0, 0);
+            XA_PLANES(NP,
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)row * ld_kv + lp * 8),
+                                                 (RTTS_LDS void*)(Ks + pl * KPL + rowb * 128), 16, 0, 0););
         }
         for (int rowb = wv * 8; rowb < XA_QB; rowb += NTHR / 8) {
             const int row = rowb + (lane >> 3);
             const int lp = (lane & 7) ^ xa_sw(row);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qbase + (size_t)row * ld_q + lp * 8),
-                                             (RTTS_LDS void*)(Qs + rowb * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(dobase + (size_t)row * ld_do + lp * 8),
-                                             (RTTS_LDS void*)(Os + rowb * 128), 16, 0, 0);
+            XA_PLANES(NP,
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qbase + pl * 64 + (size_t)row * ld_q + lp * 8),
+                                                 (RTTS_LDS void*)(Qs + pl * QPL + rowb * 128), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(dobase + pl * 64 + (size_t)row * ld_do + lp * 8),
+                                                 (RTTS_LDS void*)(Os + pl * QPL + rowb * 128), 16, 0, 0););
         }
     }
     for (int j = tid; j < XA_QB; j += NTHR) {
@@ -304,12 +362,12 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     int myrow[KT2];
 #pragma unroll
     for (int k2 = 0; k2 < KT2; ++k2) myrow[k2] = (wave * KT2 + k2) * 32 + r;
-    bf16x8 vf[KT2][4], kf[KT2][4];
+    bf16x8 vf[KT2][NKS], kf[KT2][NKS];
     int kvl[KT2];
 #pragma unroll
     for (int k2 = 0; k2 < KT2; ++k2) {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
+        for (int ks = 0; ks < NKS; ++ks) {
             vf[k2][ks] = *reinterpret_cast<const bf16x8*>(vbase + (size_t)myrow[k2] * ld_kv + ks * 16 + 8 * hh);
             kf[k2][ks] = *reinterpret_cast<const bf16x8*>(kbase + (size_t)myrow[k2] * ld_kv + ks * 16 + 8 * hh);
         }
@@ -317,14 +375,15 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     }
     __syncthreads();
 
-    f32x16 dvacc[KT2][2], gacc[KT2][2];
+    f32x16 dvacc[KT2][NP][2], gacc[KT2][NP][2];
 #pragma unroll
     for (int a = 0; a < KT2; ++a)
-#pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2) {
-            dvacc[a][c2] = (f32x16){0};
-            gacc[a][c2] = (f32x16){0};
-        }
+        XA_PLANES(NP,
+            _Pragma("unroll")
+            for (int c2 = 0; c2 < 2; ++c2) {
+                dvacc[a][pl][c2] = (f32x16){0};
+                gacc[a][pl][c2] = (f32x16){0};
+            });
     const int trq = (lane & 15) >> 2, trp = lane & 3, trc = (lane >> 4) & 1;
     int fro[4], tro[2];
 #pragma unroll
@@ -339,26 +398,28 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
 
 #pragma unroll XA_UNROLL
     for (int qt = 0; qt < XA_QB / 32; ++qt) {
-        bf16x8 qf[4], dof[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            qf[ks] = *reinterpret_cast<const bf16x8*>(Qs + qt * (32 * 128) + fro[ks]);
-            dof[ks] = *reinterpret_cast<const bf16x8*>(Os + qt * (32 * 128) + fro[ks]);
-        }
-        bf16x8 qtf[2][2], dotf[2][2];
+        bf16x8 qf[NKS], dof[NKS];
+        XA_PLANES(NP,
+            _Pragma("unroll")
+            for (int ks = 0; ks < 4; ++ks) {
+                qf[pl * 4 + ks] = *reinterpret_cast<const bf16x8*>(Qs + pl * QPL + qt * (32 * 128) + fro[ks]);
+                dof[pl * 4 + ks] = *reinterpret_cast<const bf16x8*>(Os + pl * QPL + qt * (32 * 128) + fro[ks]);
+            });
+        bf16x8 qtf[2][NDT], dotf[2][NDT];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const int blk = (qt * 32 + 16 * s2) * 128;     // second read: 8 rows on, where sw flips the piece bit dt toggles
-                qtf[s2][dt] = xa_tr_frag(Qs + blk + tro[dt], Qs + blk + 8 * 128 + tro[dt ^ 1]);
-                dotf[s2][dt] = xa_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
-            }
+            XA_PLANES(NP,
+                _Pragma("unroll")
+                for (int dt = 0; dt < 2; ++dt) {
+                    const int blk = (qt * 32 + 16 * s2) * 128;     /* second read: 8 rows on, where sw flips the piece bit dt toggles */
+                    qtf[s2][pl * 2 + dt] = xa_tr_frag(Qs + pl * QPL + blk + tro[dt], Qs + pl * QPL + blk + 8 * 128 + tro[dt ^ 1]);
+                    dotf[s2][pl * 2 + dt] = xa_tr_frag(Os + pl * QPL + blk + tro[dt], Os + pl * QPL + blk + 8 * 128 + tro[dt ^ 1]);
+                });
 #pragma unroll
         for (int k2 = 0; k2 < KT2; ++k2) {
             f32x16 sacc = {0}, pacc = {0};
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
+            for (int ks = 0; ks < NKS; ++ks) {
                 sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[ks], kf[k2][ks], sacc, 0, 0, 0);
                 pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dof[ks], vf[k2][ks], pacc, 0, 0, 0);
             }
@@ -372,14 +433,14 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int i = 4 * g + j;
-                    const float p = kvl[k2] ? __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], 0.125f * 1.4426950408889634f, -lv[j])) : 0.f;
+                    const float p = kvl[k2] ? __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[i], SC * 1.4426950408889634f, -lv[j])) : 0.f;
                     // dropout on P: O = (D*P) V  =>  dV += (D*P)^T dO,  dS = P * (D*dP - delta)   (delta = O.dO as ever);
                     // DROP is a template parameter: nn.MultiheadAttention's dropout is 0 in config/baseline.yml
                     const float keep = DROP ? rtts_drop_keep(seed, ((uint32_t)bh * (uint32_t)Tq + (uint32_t)(qb * XA_QB + q0 + j)) *
                                                                          (uint32_t)TKtot + (uint32_t)(kc0 + myrow[k2]), thresh, dscale)
                                               : 1.f;
                     pp[i] = p * keep;
-                    ds[i] = p * (pacc[i] * keep - dl[j]) * 0.125f;
+                    ds[i] = p * (pacc[i] * keep - dl[j]) * SC;
                 }
             }
 #pragma unroll
@@ -389,10 +450,10 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
                 const bf16x8 pb = cvt_bf16x8(pq[0], pq[1], pq[2], pq[3], pq[4], pq[5], pq[6], pq[7]);
                 const bf16x8 db = cvt_bf16x8(dq_[0], dq_[1], dq_[2], dq_[3], dq_[4], dq_[5], dq_[6], dq_[7]);
 #pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    dvacc[k2][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dotf[s2][dt], pb, dvacc[k2][dt], 0, 0, 0);
-                    gacc[k2][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf[s2][dt], db, gacc[k2][dt], 0, 0, 0);
-                }
+                for (int dt = 0; dt < 2; ++dt)
+                    XA_PLANES(NP,
+                        dvacc[k2][pl][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dotf[s2][pl * 2 + dt], pb, dvacc[k2][pl][dt], 0, 0, 0);
+                        gacc[k2][pl][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf[s2][pl * 2 + dt], db, gacc[k2][pl][dt], 0, 0, 0););
             }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -405,18 +466,18 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     }
 
     // dK | dV partial slab of this query block: layout (nqb, B, TKtot, 2d)
-    bf16_t* slab = dkv_part + (((size_t)qb * B + b) * TKtot + kc0) * (size_t)(2 * d) + (size_t)h * XA_DH;
+    bf16_t* slab = dkv_part + (((size_t)qb * B + b) * TKtot + kc0) * (size_t)(2 * d) + (size_t)h * DH;
 #if XA_STAGED
     __syncthreads();                 // every dS^T tile is in Ds; nobody reads the Q / dout images any more: they become the row staging
     {
-        static_assert(2 * XA_QB * 128 >= NW * 4096, "the Q and dout images must hold a 4 KB staging per wave");
+        static_assert(2 * NP * QPL >= NW * 4096, "the Q and dout images must hold a 4 KB staging per wave");
         unsigned char* stg = Qs + wave * 4096;
 #pragma unroll
         for (int k2 = 0; k2 < KT2; ++k2) {
             // rows of this wave's 32-key tile are consecutive keys: myrow[k2] = first key + r
             bf16_t* dkp = slab + (size_t)(myrow[k2] - r) * (2 * d);
-            xa_store_rows(stg, gacc[k2], 1.f, dkp, 2 * d, lane);
-            xa_store_rows(stg, dvacc[k2], 1.f, dkp + d, 2 * d, lane);
+            XA_PLANES(NP, xa_store_rows(stg, gacc[k2][pl], 1.f, dkp + pl * 64, 2 * d, lane););
+            XA_PLANES(NP, xa_store_rows(stg, dvacc[k2][pl], 1.f, dkp + d + pl * 64, 2 * d, lane););
         }
     }
 #else
@@ -425,44 +486,47 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
         bf16_t* dkp = slab + (size_t)myrow[k2] * (2 * d);
         bf16_t* dvp = dkp + d;
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
+                const f32x16& ga = gacc[k2][dt >> 1][dt & 1];
+                const f32x16& dva = dvacc[k2][dt >> 1][dt & 1];
                 uint2 pk;
-                pk.x = pack_bf16x2(gacc[k2][dt][4 * g], gacc[k2][dt][4 * g + 1]);
-                pk.y = pack_bf16x2(gacc[k2][dt][4 * g + 2], gacc[k2][dt][4 * g + 3]);
+                pk.x = pack_bf16x2(ga[4 * g], ga[4 * g + 1]);
+                pk.y = pack_bf16x2(ga[4 * g + 2], ga[4 * g + 3]);
                 *reinterpret_cast<uint2*>(dkp + dt * 32 + 8 * g + 4 * hh) = pk;
-                pk.x = pack_bf16x2(dvacc[k2][dt][4 * g], dvacc[k2][dt][4 * g + 1]);
-                pk.y = pack_bf16x2(dvacc[k2][dt][4 * g + 2], dvacc[k2][dt][4 * g + 3]);
+                pk.x = pack_bf16x2(dva[4 * g], dva[4 * g + 1]);
+                pk.y = pack_bf16x2(dva[4 * g + 2], dva[4 * g + 3]);
                 *reinterpret_cast<uint2*>(dvp + dt * 32 + 8 * g + 4 * hh) = pk;
             }
     }
     __syncthreads();
 #endif
 
-    // dQ^T[dh][q] = K^T dS^T: the 8 (query tile, dh half) outputs are dealt over the waves
-    constexpr int NOUT = (XA_QB / 32) * 2;
+    // dQ^T[dh][q] = K^T dS^T: the 8 (DH = 128: 16) (query tile, 32-wide dh tile) outputs are dealt over the waves
+    constexpr int NOUT = (XA_QB / 32) * NDT;
     for (int oi = wave; oi < NOUT; oi += NW) {
-        const int qt = oi >> 1, dt = oi & 1;
+        const int qt = oi >> NP, dt = oi & 1, dpl = NP == 2 ? (oi >> 1) & 1 : 0;      // plane dpl, 32-wide tile dt of the plane
         f32x16 dqa = {0};
         const int rl = 8 * hh + trq;                       // key row inside a 16-key step (second read: +4)
         const int gq = qt * 8 + 4 * trc + trp;             // 8-byte granule of the dS^T row
         const int do0 = xa_ds_off(rl, gq), do1 = xa_ds_off(rl + 4, gq);
         const int kpc = dt * 4 + 2 * trc + (trp >> 1);
+        const unsigned char* Kp = Ks + dpl * KPL;
         const int ko0 = xa_off(rl, kpc) + 8 * (trp & 1), ko1 = xa_off(rl + 4, kpc) + 8 * (trp & 1);
 #pragma unroll
         for (int kb = 0; kb < TK; kb += 16) {
             const bf16x8 bfrag = xa_tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
-            const bf16x8 afrag = xa_tr_frag(Ks + kb * 128 + ko0, Ks + kb * 128 + ko1);
+            const bf16x8 afrag = xa_tr_frag(Kp + kb * 128 + ko0, Kp + kb * 128 + ko1);
             dqa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag, dqa, 0, 0, 0);
         }
-        bf16_t* dqp = dq + ((size_t)b * Tq + (size_t)qb * XA_QB + qt * 32 + r) * ld_dq + (size_t)h * XA_DH;
+        bf16_t* dqp = dq + ((size_t)b * Tq + (size_t)qb * XA_QB + qt * 32 + r) * ld_dq + (size_t)h * DH;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             uint2 pk;
             pk.x = pack_bf16x2(dqa[4 * g], dqa[4 * g + 1]);
             pk.y = pack_bf16x2(dqa[4 * g + 2], dqa[4 * g + 3]);
-            *reinterpret_cast<uint2*>(dqp + dt * 32 + 8 * g + 4 * hh) = pk;
+            *reinterpret_cast<uint2*>(dqp + dpl * 64 + dt * 32 + 8 * g + 4 * hh) = pk;
         }
     }
 }
@@ -490,11 +554,12 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(const bf16_t* __restrict
     }
 }
 
-static RttsLdsState g_xa_lds[4][2];
+static RttsLdsState g_xa_lds[2][4][2];   // [dh == 128][kernel][chunk == 256]
+static RttsLdsState g_xp_lds;
 extern "C" int rtts_sum_slabs(const void* part, int nslabs, int64_t n, void* out, void* stream);
 
 static int xa_check(const char* fn, int B, int H, int Tq, int Tk, int dh, int64_t ld_q, int64_t ld_kv) {
-    RTTS_REQUIRE(dh == XA_DH, "%s: dh=%d unsupported (this build: 64)", fn, dh);
+    RTTS_REQUIRE(dh == 64 || dh == 128, "%s: dh=%d unsupported (this build: 64 or 128)", fn, dh);
     RTTS_REQUIRE(Tk >= 128 && Tk % 128 == 0 && Tk <= 2048, "%s: T_k=%d unsupported (a multiple of 128 up to 2048)", fn, Tk);
     RTTS_REQUIRE(Tq > 0 && Tq % XA_QB == 0, "%s: T_q=%d must be a multiple of 128", fn, Tq);
     RTTS_REQUIRE(B > 0 && H > 0, "%s: bad B/H", fn);
@@ -502,9 +567,17 @@ static int xa_check(const char* fn, int B, int H, int Tq, int Tk, int dh, int64_
     return 0;
 }
 
-// keys held on chip at a time: 256 when T_k is a multiple of it, else 128
+// keys held on chip at a time: 256 when T_k is a multiple of it, else 128; the backward at dh = 128 always works 128 (its
+// Q, dout and dS^T images leave room for 32 KB of K rows)
 static inline int xa_chunk(int Tk) { return Tk % 256 == 0 ? 256 : 128; }
+static inline int xa_bwd_chunk(int Tk, int dh) { return dh == 128 ? 128 : xa_chunk(Tk); }
+// the forward at dh = 128 holds 256 keys only when they are all there are (the single-pass kernel: 156 + 128 registers); its
+// chunk-walking form with 256 keys' logits, the running state and 64 output accumulators would spill, so longer T_k walk 128
+static inline int xa_fwd_chunk(int Tk, int dh) { return dh == 128 ? (Tk == 256 ? 256 : 128) : xa_chunk(Tk); }
 extern "C" int rtts_xattn_key_chunks(int Tk) { return (Tk >= 128 && Tk % 128 == 0) ? Tk / xa_chunk(Tk) : -1; }
+extern "C" int rtts_xattn_bwd_key_chunks(int Tk, int dh) {
+    return (Tk >= 128 && Tk % 128 == 0 && Tk <= 2048 && (dh == 64 || dh == 128)) ? Tk / xa_bwd_chunk(Tk, dh) : -1;
+}
 
 extern "C" int rtts_xattn_fwd(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, int B, int H, int Tq,
                               int Tk, int dh, void* o, int64_t ld_o, float* lse, float drop_p, uint32_t seed, const uint32_t* seed_dev,
@@ -515,16 +588,25 @@ extern "C" int rtts_xattn_fwd(const void* q, int64_t ld_q, const void* kv, int64
     RTTS_REQUIRE(ld_o >= (int64_t)H * dh && ld_o % 8 == 0, "rtts_xattn_fwd: bad ld_o");
     RTTS_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)o) & 15) == 0, "rtts_xattn_fwd: buffers must be 16-byte aligned");
     const dim3 grid(B * H * (Tq / XA_QB));
-    const int chunk = xa_chunk(Tk);
-    const size_t lds = 2 * (size_t)chunk * 128 + (size_t)chunk * 4;
-#define GO(TK_)                                                                                                           \
+    const int chunk = xa_fwd_chunk(Tk, dh);
+    const size_t lds = 2 * (size_t)chunk * (2 * dh) + (size_t)chunk * 4;
+#define GO(DH_, TK_)                                                                                                      \
     do {                                                                                                                  \
-        auto kern = Tk == TK_ ? xattn_fwd_kernel<TK_, false> : xattn_fwd_kernel<TK_, true>;                               \
-        RTTS_ENSURE_LDS("rtts_xattn_fwd", kern, lds, g_xa_lds[Tk == TK_ ? 0 : 3][TK_ == 256]);                            \
+        auto kern = Tk == TK_ ? xattn_fwd_kernel<DH_, TK_, false> : xattn_fwd_kernel<DH_, TK_, true>;                     \
+        RTTS_ENSURE_LDS("rtts_xattn_fwd", kern, lds, g_xa_lds[DH_ == 128][Tk == TK_ ? 0 : 3][TK_ == 256]);                \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
                            kvalid, H, Tq, Tk, (bf16_t*)o, ld_o, lse, seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p)); \
     } while (0)
-    if (chunk == 256) GO(256); else GO(128);
+#define GO1(DH_, TK_)                                                                                                     \
+    do {                                                                                                                  \
+        auto kern = xattn_fwd_kernel<DH_, TK_, false>;                                                                    \
+        RTTS_ENSURE_LDS("rtts_xattn_fwd", kern, lds, g_xa_lds[DH_ == 128][0][TK_ == 256]);                                \
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
+                           kvalid, H, Tq, Tk, (bf16_t*)o, ld_o, lse, seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p)); \
+    } while (0)
+    if (dh == 128) { if (chunk == 256) GO1(128, 256); else GO(128, 128); }
+    else { if (chunk == 256) GO(64, 256); else GO(64, 128); }
+#undef GO1
 #undef GO
     RTTS_LAUNCH_CHECK("rtts_xattn_fwd");
     return 0;
@@ -541,7 +623,7 @@ extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64
                  "rtts_xattn_bwd: bad strides");
     RTTS_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dkv_part) & 15) == 0,
                  "rtts_xattn_bwd: buffers must be 16-byte aligned");
-    const int chunk = xa_chunk(Tk), nchunks = Tk / chunk;
+    const int chunk = xa_bwd_chunk(Tk, dh), nchunks = Tk / chunk;
     // more than one key chunk: each chunk's workgroups write their share of dQ to dq_chunks (nchunks, B*Tq, H*dh) bf16 and
     // the shares are summed into dq (compact rows) by the slab-sum kernel
     RTTS_REQUIRE(nchunks == 1 || (dq_chunks && ld_dq == (int64_t)H * dh && ((uintptr_t)dq_chunks & 15) == 0),
@@ -550,16 +632,16 @@ extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64
     const dim3 grid(B * H * (Tq / XA_QB), nchunks);
     const size_t dq_stride = nchunks > 1 ? (size_t)B * Tq * H * dh : 0;
     bf16_t* dq_dst = (bf16_t*)(nchunks > 1 ? dq_chunks : dq);
-    const size_t lds = (size_t)chunk * 128 + 2 * (size_t)XA_QB * 128 + (size_t)chunk * (XA_QB * 2) + XA_QB * 8;
-#define GO(TK_)                                                                                                           \
+    const size_t lds = (size_t)chunk * (2 * dh) + 2 * (size_t)XA_QB * (2 * dh) + (size_t)chunk * (XA_QB * 2) + XA_QB * 8;
+#define GO(DH_, TK_)                                                                                                      \
     do {                                                                                                                  \
-        auto kern = drop_p > 0.f ? xattn_bwd_kernel<TK_, true> : xattn_bwd_kernel<TK_, false>;                            \
-        RTTS_ENSURE_LDS("rtts_xattn_bwd", kern, lds, g_xa_lds[1 + (drop_p > 0.f)][TK_ == 256]);                           \
+        auto kern = drop_p > 0.f ? xattn_bwd_kernel<DH_, TK_, true> : xattn_bwd_kernel<DH_, TK_, false>;                  \
+        RTTS_ENSURE_LDS("rtts_xattn_bwd", kern, lds, g_xa_lds[DH_ == 128][1 + (drop_p > 0.f)][TK_ == 256]);               \
         hipLaunchKernelGGL(kern, grid, dim3(TK_ * 2 / XA_KT2), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
                            kvalid, (const bf16_t*)dout, ld_dout, lse, delta, H, Tq, Tk, dq_dst, ld_dq, dq_stride, (bf16_t*)dkv_part, B, \
                            seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p));                               \
     } while (0)
-    if (chunk == 256) GO(256); else GO(128);
+    if (dh == 128) GO(128, 128); else if (chunk == 256) GO(64, 256); else GO(64, 128);
 #undef GO
     RTTS_LAUNCH_CHECK("rtts_xattn_bwd");
     if (nchunks > 1) return rtts_sum_slabs(dq_chunks, nchunks, (int64_t)dq_stride, dq, stream);
@@ -575,12 +657,15 @@ extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64
 // head h is worked; Q fragments and lse come straight from global (each wave reads only its own queries).
 // Layout as the forward's S^T = K Q^T: lane (r, hh) = query r, register 4 g + j = key 8 g + 4 hh + j of a 32-key tile, so a
 // register group is 4 consecutive keys of one row of `a` = one 16-byte store; the 4 groups of a tile complete 32 rows x 128 B.
+// LDS: 2 x 128 keys x 2 DH bytes + 512: 33 KB at DH = 64, 65 KB at DH = 128 (planes of 64 columns as in the kernels above).
 #define XP_KC 128     // keys per workgroup
+template <int DH>
 __global__ __launch_bounds__(256) void xattn_probs_mean_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
                                                                int64_t ld_kv, const uint8_t* __restrict__ kvalid, const float* __restrict__ lse,
                                                                int H, int Tq, int Tk, float* __restrict__ a, int64_t ld_a) {
     constexpr int NKT = XP_KC / 32;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x [XP_KC][128 B] swizzled (xa_off), kval
+    constexpr int NP = xa_dh<DH>::NP, NKS = xa_dh<DH>::NKS, PLANE = XP_KC * 128;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x [NP][XP_KC][128 B] swizzled (xa_off), kval
     const int nqb = Tq / XA_QB, nkc = Tk / XP_KC;
     const uint32_t wi = xcd_remap(blockIdx.x, gridDim.x);       // (b, query block, key chunk), key chunk fastest: the chunks of a
     const int kc = wi % nkc, qb = (wi / nkc) % nqb, b = wi / (nkc * nqb);   // query block share its Q rows in one XCD's L2
@@ -597,39 +682,41 @@ __global__ __launch_bounds__(256) void xattn_probs_mean_kernel(const bf16_t* __r
             const int rowb = it * 32 + wave * 8;
             const int row = rowb + (lane >> 3);
             const int lp = (lane & 7) ^ xa_sw(row);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + (size_t)row * ld_kv + h * XA_DH + lp * 8),
-                                             (RTTS_LDS void*)(dst + rowb * 128), 16, 0, 0);
+            XA_PLANES(NP,
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)row * ld_kv + h * DH + lp * 8),
+                                                 (RTTS_LDS void*)(dst + pl * PLANE + rowb * 128), 16, 0, 0););
         }
     };
     stage_k(0, smem);
 
-    int* kval = reinterpret_cast<int*>(smem + 2 * XP_KC * 128);  // key validity of the chunk (the head loop's first barrier publishes it)
+    int* kval = reinterpret_cast<int*>(smem + 2 * NP * PLANE);  // key validity of the chunk (the head loop's first barrier publishes it)
     for (int j = tid; j < XP_KC; j += 256) kval[j] = kvalid ? (int)kvalid[(size_t)b * Tk + c0 + j] : 1;
 
     constexpr float kLog2e = 1.4426950408889634f;
-    const float c = 0.125f * kLog2e;                            // 1 / sqrt(64), in the exp2 domain
+    const float c = xa_dh<DH>::scale * kLog2e;                  // 1 / sqrt(DH), in the exp2 domain
     f32x16 acc[NKT];
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) acc[kt] = f32x16{0};
     const bf16_t* qptr = q + ((size_t)b * Tq + qrow) * ld_q;
 #pragma unroll 1
     for (int h = 0; h < H; ++h) {
-        bf16x8 qf[4];
+        bf16x8 qf[NKS];
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qptr + h * XA_DH + ks * 16 + 8 * hh);
+        for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qptr + h * DH + ks * 16 + 8 * hh);
         const float l2 = lse[((size_t)b * H + h) * Tq + qrow] * kLog2e;
         __syncthreads();            // K of head h is in LDS, and every wave is done with the buffer head h - 1 read
-        if (h + 1 < H) stage_k(h + 1, smem + ((h + 1) & 1) * (XP_KC * 128));
-        const unsigned char* Ks = smem + (h & 1) * (XP_KC * 128);
+        if (h + 1 < H) stage_k(h + 1, smem + ((h + 1) & 1) * (NP * PLANE));
+        const unsigned char* Ks = smem + (h & 1) * (NP * PLANE);
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
             f32x16 s = {0};
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + xa_off(kt * 32 + r, ks * 2 + hh));
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s, 0, 0, 0);
-            }
-            // exp(s / 8 - lse) as one fma and v_exp_f32 (2^x); masked keys are zeroed at the store, whatever they sum to here
+            XA_PLANES(NP,
+                _Pragma("unroll")
+                for (int ks = 0; ks < 4; ++ks) {
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + xa_off(kt * 32 + r, ks * 2 + hh));
+                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[pl * 4 + ks], s, 0, 0, 0);
+                });
+            // exp(s / sqrt(DH) - lse) as one fma and v_exp_f32 (2^x); masked keys are zeroed at the store, whatever they sum to here
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[kt][i] += __builtin_amdgcn_exp2f(__builtin_fmaf(s[i], c, -l2));
         }
@@ -660,8 +747,15 @@ extern "C" int rtts_xattn_probs_mean(const void* q, int64_t ld_q, const void* kv
     RTTS_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)a) & 15) == 0, "rtts_xattn_probs_mean: q, kv and a must be 16-byte aligned");
     const size_t nwg = (size_t)B * (Tq / XA_QB) * (Tk / XP_KC);
     RTTS_REQUIRE(nwg <= 0x7fffffff, "rtts_xattn_probs_mean: grid too large");
-    hipLaunchKernelGGL(xattn_probs_mean_kernel, dim3((unsigned)nwg), dim3(256), 2 * XP_KC * 128 + XP_KC * 4, (hipStream_t)stream, (const bf16_t*)q, ld_q,
-                       (const bf16_t*)kv, ld_kv, kvalid, lse, H, Tq, Tk, a, ld_a);
+    const size_t lds = 2 * (size_t)XP_KC * (2 * dh) + XP_KC * 4;
+    if (dh == 128) {
+        RTTS_ENSURE_LDS("rtts_xattn_probs_mean", xattn_probs_mean_kernel<128>, lds, g_xp_lds);
+        hipLaunchKernelGGL(xattn_probs_mean_kernel<128>, dim3((unsigned)nwg), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q,
+                           (const bf16_t*)kv, ld_kv, kvalid, lse, H, Tq, Tk, a, ld_a);
+    } else {
+        hipLaunchKernelGGL(xattn_probs_mean_kernel<64>, dim3((unsigned)nwg), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q,
+                           (const bf16_t*)kv, ld_kv, kvalid, lse, H, Tq, Tk, a, ld_a);
+    }
     RTTS_LAUNCH_CHECK("rtts_xattn_probs_mean");
     return 0;
 }

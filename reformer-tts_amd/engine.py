@@ -938,7 +938,7 @@ class XAttnExec:
     def supported(withnorm) -> bool:
         m = withnorm.fn.layer      # dropout on the attention probabilities runs inside the kernels (counter-hash mask)
         return m.bias_k is None and not m.add_zero_attn and m._qkv_same_embed_dim and m.embed_dim % 64 == 0 and \
-            m.embed_dim // m.num_heads == 64
+            m.embed_dim % m.num_heads == 0 and m.embed_dim // m.num_heads in (64, 128)   # heads of 128: num_heads 4 at width 512
 
     def _internals(self, inp, b, t, keys_bf16, kvalid, stash=None, g=None, pre=None, drop=None, proj=None):
         m = self.mha
@@ -998,7 +998,7 @@ class XAttnExec:
         dev = inp.device
         if FUSE_DELTA and e == 64 * h and dgrad_delta_ok(b * t, e):
             do, delta = gemm_dgrad_delta(dyb, _bf16(m.out_proj.weight), o, t, h)
-        else:
+        else:                  # heads of 128 always come here: epilogue 5 sums 64-wide heads
             do = gemm(dyb, _bf16(m.out_proj.weight), kn=True)
             delta = torch.empty(b * h, t, dtype=torch.float32, device=dev)
             _lib.call("rtts_lsh_bwd_delta", o.data_ptr(), e, do.data_ptr(), e, b, h, t, e // h, delta.data_ptr(), _s())
@@ -1006,7 +1006,8 @@ class XAttnExec:
         nqb = t // 128
         part = torch.empty(nqb, b * tk, 2 * e, dtype=torch.bfloat16, device=dev)
         dp, dseed = drop if drop else (0.0, 0)
-        nkc = _lib.load().rtts_xattn_key_chunks(tk)          # > 256 keys: worked in chunks, each with its share of dQ
+        # > 256 keys (heads of 128: > 128 keys): worked in chunks, each with its share of dQ
+        nkc = _lib.load().rtts_xattn_bwd_key_chunks(tk, e // h)
         dq_chunks = torch.empty(nkc, b * t, e, dtype=torch.bfloat16, device=dev) if nkc > 1 else None
         _lib.call("rtts_xattn_bwd", q.data_ptr(), e, kv.data_ptr(), 2 * e, None if kvalid is None else kvalid.data_ptr(),
                   do.data_ptr(), e, lse.data_ptr(), delta.data_ptr(), b, h, t, tk, e // h, dq.data_ptr(), e, part.data_ptr(),

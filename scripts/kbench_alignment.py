@@ -2,7 +2,9 @@
 """Attention alignments on the eval path (GPU box only): us per launch of rtts_xattn_probs_mean and its achieved bytes per second,
 the general eval path's ATen sequence for the same matrices, and Trainer.validate with and without return_attention at the
 baseline configuration.  HIP events; medians of several timed regions.
-RTTS_LIB=<alternative build> python scripts/kbench_alignment.py   # A/B against another build on the same box"""
+RTTS_LIB=<alternative build> python scripts/kbench_alignment.py   # A/B against another build on the same box
+--dh 128: the kernel cases with 128-wide heads at the same model width (half the heads)."""
+import argparse
 import os
 import statistics
 import sys
@@ -33,8 +35,8 @@ def timed(fn, reps=50, regions=5):
     return statistics.median(out)
 
 
-def kernel_case(b, h, t, tk, valid_keys):
-    e = 64 * h
+def kernel_case(b, h, t, tk, valid_keys, dh=64):
+    e = dh * h
     g = torch.Generator().manual_seed(0)
     q = torch.randn(b * t, e, generator=g).bfloat16().to(dev)
     kv = torch.randn(b * tk, 2 * e, generator=g).bfloat16().to(dev)
@@ -45,7 +47,7 @@ def kernel_case(b, h, t, tk, valid_keys):
     a = torch.empty(b, t, tk, dtype=torch.float32, device=dev)
 
     def fwd():
-        _lib.call("rtts_xattn_fwd", q.data_ptr(), e, kv.data_ptr(), 2 * e, kvalid.data_ptr(), b, h, t, tk, 64, o.data_ptr(), e,
+        _lib.call("rtts_xattn_fwd", q.data_ptr(), e, kv.data_ptr(), 2 * e, kvalid.data_ptr(), b, h, t, tk, dh, o.data_ptr(), e,
                   lse.data_ptr(), 0.0, 0, seed_base(dev).data_ptr(), s)
 
     fwd_us = timed(fwd)
@@ -54,15 +56,15 @@ def kernel_case(b, h, t, tk, valid_keys):
     nbytes = a.numel() * 4 + q.numel() * 2 + b * tk * e * 2 + lse.numel() * 4 + kvalid.numel()
 
     def aten():                                    # model/reformer.py's general eval path for the same matrices
-        qh = q.view(b, t, h, 64).transpose(1, 2)
-        kh = kv[:, :e].view(b, tk, h, 64).transpose(1, 2)
-        sc = (qh.float() * 64 ** -0.5) @ kh.float().transpose(-1, -2)
+        qh = q.view(b, t, h, dh).transpose(1, 2)
+        kh = kv[:, :e].view(b, tk, h, dh).transpose(1, 2)
+        sc = (qh.float() * dh ** -0.5) @ kh.float().transpose(-1, -2)
         sc = sc.masked_fill(~kvalid.bool()[:, None, None, :], float("-inf"))
         return torch.softmax(sc, dim=-1).mean(dim=1)
 
     aten_us = timed(aten, reps=10)
     err = float((aten() - a).abs().max())
-    print(f"B={b} H={h} Tq={t} Tk={tk}: probs_mean {us:8.1f} us  {nbytes / us / 1e3:7.1f} GB/s ({nbytes / 1e6:.1f} MB)   "
+    print(f"B={b} H={h} dh={dh} Tq={t} Tk={tk}: probs_mean {us:8.1f} us  {nbytes / us / 1e3:7.1f} GB/s ({nbytes / 1e6:.1f} MB)   "
           f"xattn_fwd {fwd_us:7.1f} us   ATen general path {aten_us:8.1f} us   max |HIP - ATen| {err:.1e}", flush=True)
 
 
@@ -81,7 +83,10 @@ def validate_case(b=12, text=256, mel=1024):
 
 
 if __name__ == "__main__":
-    kernel_case(12, 8, 1024, 256, 200)
-    kernel_case(12, 8, 4096, 256, 200)
-    kernel_case(12, 8, 4096, 512, 400)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dh", type=int, default=64, choices=(64, 128), help="head width of the kernel cases; the model width stays 512")
+    dh = ap.parse_args().dh
+    kernel_case(12, 512 // dh, 1024, 256, 200, dh)
+    kernel_case(12, 512 // dh, 4096, 256, 200, dh)
+    kernel_case(12, 512 // dh, 4096, 512, 400, dh)
     validate_case()

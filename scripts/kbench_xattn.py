@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Cross-attention kernels at the decoder shape of config/baseline.yml (GPU box only): us per launch, HIP events.
-RTTS_LIB=<alternative build> python scripts/kbench_xattn.py   # A/B against another build on the same box"""
+RTTS_LIB=<alternative build> python scripts/kbench_xattn.py   # A/B against another build on the same box
+--dh 128: 128-wide heads (num_heads 4 at width 512, the reference's config/legacy/attention-depth-3-heads-4.yml); same FLOPs."""
+import argparse
 import os
 import sys
 
@@ -10,8 +12,12 @@ import torch  # noqa: E402
 from reformer_tts_amd import _lib  # noqa: E402
 from reformer_tts_amd._seeds import seed_base  # noqa: E402
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--dh", type=int, default=64, choices=(64, 128), help="head width; the model width stays 512")
+args = ap.parse_args()
 dev = torch.device("cuda:0")
-b, h, t, tk, e = 12, 8, 1024, 256, 512
+b, t, tk, e = 12, 1024, 256, 512
+h = e // args.dh
 g = torch.Generator().manual_seed(0)
 q = torch.randn(b * t, e, generator=g).bfloat16().to(dev)
 kv = torch.randn(b * tk, 2 * e, generator=g).bfloat16().to(dev)
@@ -23,7 +29,7 @@ lse = torch.empty(b * h, t, dtype=torch.float32, device=dev)
 delta = torch.empty(b * h, t, dtype=torch.float32, device=dev)
 dq = torch.empty(b * t, e, dtype=torch.bfloat16, device=dev)
 part = torch.empty(t // 128, b * tk, 2 * e, dtype=torch.bfloat16, device=dev)
-nkc = _lib.load().rtts_xattn_key_chunks(tk)
+nkc = _lib.load().rtts_xattn_bwd_key_chunks(tk, e // h)
 dq_chunks = torch.empty(nkc, b * t, e, dtype=torch.bfloat16, device=dev) if nkc > 1 else None
 s = torch.cuda.current_stream().cuda_stream
 sb = seed_base(dev)
@@ -52,4 +58,4 @@ for name, fn in (("xattn_fwd", fwd), ("xattn_bwd", bwd)):
         fn()
     z.record()
     torch.cuda.synchronize()
-    print(f"{name}: {a.elapsed_time(z) / 50 * 1e3:7.1f} us   checksum {float(dq.float().abs().sum()) + float(o.float().abs().sum()):.6e}", flush=True)
+    print(f"dh {e // h} H {h} {name}: {a.elapsed_time(z) / 50 * 1e3:7.1f} us   checksum {float(dq.float().abs().sum()) + float(o.float().abs().sum()):.6e}", flush=True)
