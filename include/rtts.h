@@ -268,6 +268,29 @@ int rtts_sum_slabs(const void* part, int nslabs, int64_t n, void* out, void* str
 int rtts_xattn_probs_mean(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
                           const float* lse, int B, int H, int Tq, int Tk, int dh, float* a, int64_t ld_a, void* stream);
 
+/* ---- dense shared-QK attention (use_full_attn / T <= full_attn_thres of the LSH layer) -------------------
+ * What reformer_pytorch's LSHSelfAttention computes on its FullQKAttention branch; the layer is built at reference
+ * reformer_tts/model/reformer.py:198-217.  Per (batch, head), rows of dh = 64 bf16 in the [qk | v] layout (common stride ld):
+ *   s_ij = (qk_i . qk_j) / (sqrt(dh) max(|qk_j|, 1e-12)); then, each overwriting the last: s_ii = -5e4; s_ij = -FLT_MAX unless
+ *   mask_i and mask_j; causal: s_ij = -FLT_MAX for j > i.  P = softmax_j s, o_i = sum_j P_ij keep_ij v_j.
+ *   A query with mask_i = 0 therefore has P_ij = 1/T over ALL T keys: o_i = mean(v) and lse_i = -FLT_MAX exactly (the LSH
+ *   kernels give v_i there); the backward takes P = 1/T, dS = 0 for such rows and still adds their dout to dv of every key.
+ *   mask u8 (B,T) 1 = valid token, or NULL;  out bf16 (B,T,H*dh) stride ld_out;  lse f32 (B*H,T)
+ *   keep = 0 | 1/(1-p) by the counter hash of (drop_seed + *seed_dev, (head*T + i)*T + j), head = b*H + h, in wrapping uint32
+ *   T a multiple of 64, 64 <= T <= rtts_full_attn_max_t(dh) (4096 at dh = 64; -1 for any other dh): key tiles are streamed
+ *   backward: delta f32 (B*H,T) = rowsum(out*dout) (rtts_lsh_bwd_delta or the to_out dgrad epilogue); dqk, dv bf16 (B,T,H*dh)
+ *   stride ld_d; workspace of rtts_full_attn_bwd_workspace() bytes (fp32 key-role rows), 16-byte aligned.  Two passes (owner =
+ *   key: dv and the key-role rows; owner = query: query role + key role -> dqk), no atomics: every output row is written once
+ *   and two runs are bit-identical.  Bad arguments return an error (rtts_last_error) and launch nothing. */
+int rtts_full_attn_max_t(int dh);
+int rtts_full_attn_fwd(const void* qk, const void* v, int64_t ld, const uint8_t* mask, int B, int H, int T, int dh, int causal,
+                       void* out, int64_t ld_out, float* lse, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev,
+                       void* stream);
+int64_t rtts_full_attn_bwd_workspace(int B, int H, int T, int dh);
+int rtts_full_attn_bwd(const void* qk, const void* v, int64_t ld, const uint8_t* mask, const void* dout, int64_t ld_dout,
+                       const float* lse, const float* delta, int B, int H, int T, int dh, int causal, void* dqk, void* dv,
+                       int64_t ld_d, void* workspace, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream);
+
 /* ---- convolutional edges (prenet / postnet) and the loss ------------------------------------------
  * Reference reformer_tts/model/modules.py:8-61 (EncoderPreNet), :103-169 (PostConvNet); loss.py:28-53.
  * HALO ROWS.  The activations of a convolution stack are channels-last rows (B, L + 2*halo, C), halo = 2, with `halo` zero

@@ -764,13 +764,19 @@ class LSHExec:
         e = lyr.dim
         if self.hf:
             lyr.check_length(t)
-        elif t <= lyr.full_attn_thres:
-            raise NotImplementedError("full-attention shortcut (T <= full_attn_thres) is outside the HIP path")
+        # use_full_attn / T <= full_attn_thres: the dense shared-QK kernels, per call by t.  No rotations are drawn, no
+        # permutation is kept (st stays None in the slot), out and lse come from one launch
+        dense = not self.hf and lyr.dense(t)
+        if dense:
+            from .model.lsh_attention import dense_envelope
+            dense_envelope(t)
         xn, mean, rstd = pre if pre is not None else ln_fwd(inp, self.norm)
         wqkv = self._wqkv()
         if qkv is None:
             qkv = gemm(xn, wqkv).view(b, t, 2 * e)
-        if st is None and self.hf:
+        if dense:
+            pass
+        elif st is None and self.hf:
             st = lyr.hash_sort(qkv[..., :e], lyr._rotations(qkv, lyr.resolve_num_buckets(t)), mask)
         elif st is None:
             rot = lyr._rotations(qkv, t // lyr.bucket_size)
@@ -778,6 +784,8 @@ class LSHExec:
         lyr.last_st = st
         if stash is not None:
             out, lse_tot = stash
+        elif dense:
+            out, lse_tot = ops.full_attn_fwd(qkv[..., :e], qkv[..., e:], lyr.heads, lyr.causal, mask, adrop)
         else:
             o, lse = ops.lsh_attn_fwd(qkv[..., :e], qkv[..., e:], st, lyr.heads, lyr.bucket_size, lyr.causal, mask, adrop)
             out, lse_tot = ops.lsh_combine_fwd(o, lse, b, lyr.heads)
@@ -836,8 +844,12 @@ class LSHExec:
         else:
             dout = gemm(dyb, _bf16(lyr.to_out.weight), kn=True).view(b, t, e)
         dqkv = torch.empty_like(qkv)
-        ops.lsh_attn_bwd(qkv[..., :e], qkv[..., e:], st, out, dout, lse_tot, lyr.heads, lyr.bucket_size, lyr.causal, mask,
-                         dqkv=(dqkv[..., :e], dqkv[..., e:]), drop=adrop, delta=delta)
+        if lyr.dense(t):
+            ops.full_attn_bwd(qkv[..., :e], qkv[..., e:], out, dout, lse_tot, lyr.heads, lyr.causal, mask,
+                              dqkv=(dqkv[..., :e], dqkv[..., e:]), drop=adrop, delta=delta)
+        else:
+            ops.lsh_attn_bwd(qkv[..., :e], qkv[..., e:], st, out, dout, lse_tot, lyr.heads, lyr.bucket_size, lyr.causal, mask,
+                             dqkv=(dqkv[..., :e], dqkv[..., e:]), drop=adrop, delta=delta)
         return post, self._projection_backward(dqkv.view(b * t, 2 * e), xn, wqkv, inp, mean, rstd, d_inp, next_cast, d_src, join)
 
     def _projection_backward(self, dqkv2, xn, wqkv, inp, mean, rstd, d_inp, next_cast, d_src, join):

@@ -24,6 +24,10 @@ Recompute protocol at this seam (``forward(x, input_mask=...)`` is all the refer
     ``Deterministic``) is the same thing without the checks.
 The explicit executor (``engine.LSHExec``) keeps its permutations in per-call slots and does not come
 through ``forward``.
+
+``use_full_attn`` / ``T <= full_attn_thres`` take reformer_pytorch's dense branch (``FullQKAttention``) per call: the dense
+shared-QK kernels of ``csrc/full_attn.hip``, exact and deterministic, no rotations drawn and nothing kept for a replay but the
+seed of the probability dropout.
 """
 from __future__ import annotations
 
@@ -61,6 +65,37 @@ class _LSHAttnFn(torch.autograd.Function):
         ops.lsh_attn_bwd(qkv[..., :d], qkv[..., d:], st, out, dout, lse_tot, heads, bucket_size, causal, mask,
                          dqkv=(dqkv[..., :d], dqkv[..., d:]), drop=drop)
         return dqkv, None, None, None, None, None, None
+
+
+class _FullAttnFn(torch.autograd.Function):
+    """qkv (B,T,2d) bf16 [qk | v] -> out (B,T,d) bf16 (heads merged): dense shared-QK attention (``rtts_full_attn_fwd`` / ``_bwd``)."""
+
+    @staticmethod
+    def forward(ctx, qkv, mask, heads, causal, drop=None):
+        d = qkv.shape[-1] // 2
+        out, lse = ops.full_attn_fwd(qkv[..., :d], qkv[..., d:], heads, causal, mask, drop)
+        ctx.save_for_backward(qkv, out, lse, mask)
+        ctx.cfg = (heads, causal, drop)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, mask = ctx.saved_tensors
+        heads, causal, drop = ctx.cfg
+        d = qkv.shape[-1] // 2
+        dqkv = torch.empty_like(qkv)
+        if dout.dtype != torch.bfloat16 or dout.stride(2) != 1:
+            dout = dout.to(torch.bfloat16).contiguous()
+        ops.full_attn_bwd(qkv[..., :d], qkv[..., d:], out, dout, lse, heads, causal, mask, dqkv=(dqkv[..., :d], dqkv[..., d:]), drop=drop)
+        return dqkv, None, None, None, None
+
+
+def dense_envelope(t: int) -> None:
+    """Raise unless the dense shared-QK kernels take a sequence of ``t`` tokens."""
+    limit = ops.full_attn_max_t(64)
+    if t % 64 != 0 or not 64 <= t <= limit:
+        raise NotImplementedError(f"dense shared-QK attention (use_full_attn / T <= full_attn_thres) on the HIP path takes "
+                                  f"T a multiple of 64 from 64 to {limit}, got T={t}")
 
 
 def _gemm_tiles(m: int, n: int, k: int) -> bool:
@@ -127,7 +162,7 @@ class LSHSelfAttention(nn.Module):
             raise AssertionError("dimensions must be divisible by number of heads")
         unsupported = dict(add_local_attn_hash=add_local_attn_hash, attend_across_buckets=not attend_across_buckets,
                            allow_duplicate_attention=not allow_duplicate_attention, num_mem_kv=num_mem_kv,
-                           one_value_head=one_value_head, use_full_attn=use_full_attn, return_attn=return_attn)
+                           one_value_head=one_value_head, return_attn=return_attn)
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
         bad = [k for k, v in unsupported.items() if v]
@@ -137,6 +172,7 @@ class LSHSelfAttention(nn.Module):
             raise NotImplementedError(f"implementation='hip' is built for dim/heads == 64 (got {dim // heads})")
         self.dim, self.heads, self.bucket_size, self.n_hashes, self.causal = dim, heads, bucket_size, n_hashes, causal
         self.random_rotations_per_head = random_rotations_per_head
+        self.use_full_attn = bool(use_full_attn)
         self.full_attn_thres = bucket_size if full_attn_thres is None else full_attn_thres
         self.attn_chunks = attn_chunks  # memory-only knob in the reference; no numeric effect
         self.toqk = nn.Linear(dim, dim, bias=False)
@@ -145,6 +181,7 @@ class LSHSelfAttention(nn.Module):
         self.post_attn_dropout = nn.Dropout(post_attn_dropout)
         self.dropout = float(dropout)        # on the attention probabilities (config.py:27): a counter-hash mask inside the kernels
         self._attn_drop = None               # (p, seed) of the last no_grad training call: the recompute redraws the same mask
+        self._dense_drop = None              # the same for a dense call: (generator state, (p, seed))
         self.seed = seed
         self._gen: Optional[torch.Generator] = None
         self._saved: Optional[tuple] = None   # (generator state, st, input signature) of the last no_grad training call
@@ -201,10 +238,37 @@ class LSHSelfAttention(nn.Module):
         reconstructed stream differs by fp32 rounding), O(1) apart for any other input."""
         return x.detach().float().abs().sum(-1)
 
+    def dense(self, t: int) -> bool:
+        """Does a call of ``t`` tokens take the dense shared-QK branch (reformer_pytorch: ``use_full_attn or t <= full_attn_thres``)?"""
+        return self.use_full_attn or t <= self.full_attn_thres
+
+    def _forward_dense(self, x, input_mask, recompute):
+        """The FullQKAttention branch: exact and deterministic.  No rotations are drawn -- the default generator stays where it
+        was, as in the reference, so ``Deterministic`` has nothing to replay but ``post_attn_dropout`` -- and no permutation is
+        kept.  Only the counter-hash seed of the probability dropout is remembered across a no_grad training call, so that the
+        reversible recompute redraws the same mask."""
+        b, t, e = x.shape
+        dense_envelope(t)
+        qkv = _project(x.to(torch.bfloat16).reshape(b * t, e), None, self.toqk.weight, self.tov.weight).view(b, t, 2 * e)
+        drop = None
+        if self.training and self.dropout > 0.0:
+            state, grad_on, saved = self._generator_state(x.device), torch.is_grad_enabled(), self._dense_drop
+            replay = grad_on and saved is not None and (recompute or (state is not None and saved[0] == state))
+            drop = saved[1] if replay else (self.dropout, next_seed())
+            if replay:
+                self._dense_drop = None
+            elif not grad_on:
+                self._dense_drop = (state, drop)
+        self.last_st = None
+        mask = None if input_mask is None else input_mask.to(torch.uint8)
+        out = _FullAttnFn.apply(qkv, mask, self.heads, self.causal, drop)
+        y = _project(out.reshape(b * t, e), self.to_out.bias, self.to_out.weight).view(b, t, e)
+        return self.post_attn_dropout(y.float())
+
     def forward(self, x, input_mask=None, recompute: bool = False, **_):
         b, t, e = x.shape
-        if t <= self.full_attn_thres:
-            raise NotImplementedError("full-attention shortcut (T <= full_attn_thres) is outside the HIP path")
+        if self.dense(t):
+            return self._forward_dense(x, input_mask, recompute)
         if t % (self.bucket_size * 2) != 0:
             raise AssertionError(f"Sequence length ({t}) needs to be divisible by target bucket size  x 2 - {self.bucket_size * 2}")
         # (B,T,2d) = [qk | v]: ONE product over the stacked weights, on rtts_gemm_nt (forward, input gradient) / rtts_gemm_tn

@@ -213,6 +213,73 @@ def lsh_attn_bwd(qk, v, st, out, dout, lse_tot, heads: int, bucket_size: int, ca
     return dqk, dv
 
 
+def full_attn_max_t(dh: int = 64) -> int:
+    """Longest sequence the dense shared-QK kernels take at head width ``dh`` (-1: width not built)."""
+    return int(_lib.load().rtts_full_attn_max_t(int(dh)))
+
+
+def full_attn_fwd(qk, v, heads: int, causal: bool, mask=None, drop=None, out: Optional[torch.Tensor] = None):
+    """Dense shared-QK attention (the layer's ``use_full_attn`` / ``T <= full_attn_thres`` branch).  qk, v (B,T,H*dh) bf16 with a
+    common row stride -> out (B,T,H*dh) bf16 (merged heads), lse (B*H,T) f32.  ``drop`` = (p, seed) as ``lsh_attn_fwd``."""
+    ld = _check_rows(qk, "qk")
+    if _check_rows(v, "v") != ld or v.shape != qk.shape:
+        raise ValueError("qk and v must share shape and row stride")
+    b, t, d = qk.shape
+    dh = d // heads
+    mask = _check_mask(mask, b, t, qk.device)
+    if out is None:
+        out = torch.empty(b, t, d, dtype=torch.bfloat16, device=qk.device)
+    ld_out = _check_rows(out, "out")
+    lse = torch.empty(b * heads, t, dtype=torch.float32, device=qk.device)
+    ev = TIMING.start(f"rtts_full_attn_fwd/t{t}")
+    _lib.call("rtts_full_attn_fwd", qk.data_ptr(), v.data_ptr(), ld, _ptr(mask), b, heads, t, dh, int(causal), out.data_ptr(), ld_out,
+              lse.data_ptr(), *_drop_args(drop, qk.device), _stream())
+    # two MFMA products (Q K^T and P V) of 2*T*T*dh FLOP per head (a causal call works about half of them)
+    TIMING.stop(ev, 2.0 * 2.0 * t * t * dh * b * heads)
+    return out, lse
+
+
+def full_attn_bwd(qk, v, out, dout, lse, heads: int, causal: bool, mask=None,
+                  dqkv: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, drop=None, delta: Optional[torch.Tensor] = None):
+    """Backward of ``full_attn_fwd``.  -> dqk, dv (B,T,H*dh) bf16.  ``delta`` (B*H, T) fp32 = rowsum(out * dout) per head when the
+    caller already has it (the to_out input-gradient GEMM's epilogue), else computed here from ``out``."""
+    ld = _check_rows(qk, "qk")
+    if _check_rows(v, "v") != ld:
+        raise ValueError("qk and v must share a row stride")
+    ld_do = _check_rows(dout, "dout")
+    b, t, d = qk.shape
+    dh = d // heads
+    mask = _check_mask(mask, b, t, qk.device)
+    dev = qk.device
+    if delta is None:
+        ld_out = _check_rows(out, "out")
+        delta = torch.empty(b * heads, t, dtype=torch.float32, device=dev)
+        _lib.call("rtts_lsh_bwd_delta", out.data_ptr(), ld_out, dout.data_ptr(), ld_do, b, heads, t, dh, delta.data_ptr(), _stream())
+    elif delta.shape != (b * heads, t) or delta.dtype != torch.float32 or not delta.is_contiguous():
+        raise ValueError("delta: expected contiguous fp32 (B*H, T)")
+    if lse.shape != (b * heads, t) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("lse: expected contiguous fp32 (B*H, T)")
+    nbytes = int(_lib.load().rtts_full_attn_bwd_workspace(b, heads, t, dh))
+    if nbytes < 0:
+        raise _lib.RttsError(f"rtts_full_attn_bwd: T={t}, dh={dh} is outside the dense kernels' envelope "
+                             f"(T a multiple of 64 from 64 to {full_attn_max_t(64)}, dh 64)")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    if dqkv is None:
+        dqk = torch.empty(b, t, d, dtype=torch.bfloat16, device=dev)
+        dv = torch.empty(b, t, d, dtype=torch.bfloat16, device=dev)
+    else:
+        dqk, dv = dqkv
+    ld_d = _check_rows(dqk, "dqk")
+    if _check_rows(dv, "dv") != ld_d:
+        raise ValueError("dqk and dv must share a row stride")
+    ev = TIMING.start(f"rtts_full_attn_bwd/t{t}")
+    _lib.call("rtts_full_attn_bwd", qk.data_ptr(), v.data_ptr(), ld, _ptr(mask), dout.data_ptr(), ld_do, lse.data_ptr(), delta.data_ptr(),
+              b, heads, t, dh, int(causal), dqk.data_ptr(), dv.data_ptr(), ld_d, ws.data_ptr(), *_drop_args(drop, dev), _stream())
+    # seven MFMA products of 2*T*T*dh FLOP per head: S and dP in both passes, dV, G, dQ
+    TIMING.stop(ev, 7.0 * 2.0 * t * t * dh * b * heads)
+    return dqk, dv
+
+
 def mel_spectrogram(audio: torch.Tensor, sample_offsets_host, frame_offsets_host, offsets: torch.Tensor, nseg: int,
                     dft_basis: torch.Tensor, mel_basis: torch.Tensor, n_fft: int, hop: int, power: int, clip: float,
                     out: torch.Tensor) -> torch.Tensor:
