@@ -6,7 +6,8 @@ Criterion, per output element, with L1_t = sum_n |x_n w_n| of frame t and S_m = 
 (power 1: 2^-20 L1 S; power 2: 2^-19 L1^2 S).  A float32 k-ordered DFT chain errs by a few 1e-8 of L1 per bin (measured on the
 CPU against the same oracle: 1.4e-8 for an FFT, 3.6e-8 for a blocked DFT-GEMM), so 2^-20 ~ 9.5e-7 leaves about 25x, four orders
 of magnitude below the median signal (0.037 of L1 S): a wrong bin, window, reflection or offset cannot hide.  The relative term
-is the spacing of the stored f32 log (2^-20 near -11.5)."""
+is the spacing of the stored f32 log (2^-20 near -11.5).
+The banks used here weigh bin 0 and the bins above 8 kHz with zero: tests/test_mel_bins_hip.py reads every bin, tile path and mel width."""
 import math
 import os
 
