@@ -850,6 +850,48 @@ int rtts_denoise(const float* audio, const int64_t* sample_offsets_host, const i
                  const float* dft_basis, const float* idft_basis, const float* bias /* n_fft/2+1 */, float strength, int n_fft,
                  int hop, float* out, void* stream);
 
+/* ---- Griffin-Lim vocoding: log-mel spectrogram -> audio without a trained vocoder ---------------
+ * For a RAGGED batch of utterances, n_fft = 1024, hop = 256, w = periodic Hann of n_fft.  One utterance of L mel frames gives
+ * n = hop L samples (the vocoder's contract) and T = L + 1 STFT frames; STFT and iSTFT are those of rtts_denoise
+ * (torch.stft(center=True, pad_mode="reflect") / torch.istft(center=True, length=n)).
+ *   1. magnitudes   A[k][t] = max(0, sum_m P[k][m] exp(mel[m][t])),  t < L,  P = pinv(mel matrix) (n_fft/2 + 1, n_mels), float64 on the
+ *                   host, rounded once to f32;  M[k][t] = A[k][t]^(1/power), power = 1 (magnitude mels) or 2 (power mels);
+ *                   column L repeats column L - 1, so M is (n_fft/2 + 1, L + 1)
+ *   2. start        x_0 = iSTFT(M e^{i phi});  phase 1 ("hash"): phi[k][t] = 2 pi (rtts_drop_hash(seed, t (n_fft/2 + 1) + k) >> 8) / 2^24
+ *                   with t the utterance's OWN frame index (the counter hash of the dropout masks, csrc/rtts_common.h; the index in
+ *                   uint32 arithmetic);  phase 0 ("zero"): phi = 0.  The imaginary part of bins 0 and n_fft/2 is dropped, as irfft does
+ *   3. iteration    k = 0 .. n_iter - 1, beta = momentum / (1 + momentum):   R = STFT(x_k - beta x_{k-1})   (no beta term at k = 0)
+ *                   x_{k+1} = iSTFT(M R / |R|),  R / |R| = 1 where |R| = 0.  momentum 0 is the classic loop, 0.99 the fast one
+ *                   (by linearity the momentum term needs no spectrogram kept between the iterations)
+ *   4. an utterance of fewer than 3 frames (n <= n_fft / 2) cannot be reflect-padded: its samples are written as zeros
+ * All arithmetic is f32: M is one ascending-m fmaf chain per value; init and step are the launch of rtts_denoise with another gain
+ * (v_mfma_f32_32x32x2_f32, bit for bit a k-ordered fmaf chain, then one fixed-order sum per sample).  An utterance's output is
+ * bitwise the same alone and anywhere in a batch, and from call to call; no atomics.
+ *   mel             f32, read in place: frame t, channel m of utterance s is mel[s stride_b + m stride_c + (mel_start[s] + t) stride_t]
+ *                   (element strides).  A (B, n_mels, L) tensor: its strides and mel_start = 0; a packed (n_mels, sum L) one:
+ *                   stride_b = 0 and mel_start = the utterances' first columns.  mel_start: i64 (nseg), DEVICE
+ *   mag             f32 (n_fft/2 + 1, ld_mag) bin-major: utterance s owns columns [col_offsets[s], col_offsets[s+1]), L_s + 1 of them --
+ *                   the frame offsets of rtts_mel_spectrogram for lengths hop L_s.  col_offsets[nseg] <= ld_mag
+ *   sample_offsets  utterance s is samples [sample_offsets[s], sample_offsets[s+1]) of cur, prev and out: hop L_s of them
+ *   col_offsets, sample_offsets   i64 (nseg + 1): the DEVICE tables the kernels read, and the same values in the _host copies, which
+ *                   the entry points validate and size the grid by.  The two copies MUST hold the same values
+ *   pinv            f32 (n_fft/2 + 1, n_mels) row-major, device;  dft_basis, idft_basis: those of rtts_denoise
+ *   cur, prev, out  f32 over the same sample offsets.  prev may be null (and is not read when beta = 0).  out may overlap neither
+ *                   cur nor prev (a workgroup reads the input of its neighbours' samples); samples outside the offsets are neither
+ *                   read nor written
+ * Supported: n_fft = 1024, hop = 256, 1 <= nseg <= 65535, 1 <= n_mels <= 128, power 1 or 2, 0 <= beta < 1, phase 0 or 1.  Anything
+ * else, a null pointer (but prev), offsets that do not step as stated or an out that overlaps an input is rejected before any
+ * launch. */
+int rtts_gl_magnitudes(const float* mel, int64_t stride_b, int64_t stride_c, int64_t stride_t, const int64_t* mel_start,
+                       const int64_t* col_offsets_host, const int64_t* col_offsets, int nseg, const float* pinv, int n_mels, int power,
+                       int n_fft, float* mag, int64_t ld_mag, void* stream);
+int rtts_gl_init(const float* mag, int64_t ld_mag, const int64_t* col_offsets_host, const int64_t* col_offsets,
+                 const int64_t* sample_offsets_host, const int64_t* sample_offsets, int nseg, const float* dft_basis,
+                 const float* idft_basis, int phase, uint32_t seed, int n_fft, int hop, float* out, void* stream);
+int rtts_gl_step(const float* cur, const float* prev, float beta, const float* mag, int64_t ld_mag, const int64_t* col_offsets_host,
+                 const int64_t* col_offsets, const int64_t* sample_offsets_host, const int64_t* sample_offsets, int nseg,
+                 const float* dft_basis, const float* idft_basis, int n_fft, int hop, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,9 @@ SIGNATURES = {
     "rtts_resample_len": [_i64, _i32, _i32],
     "rtts_resample": [_vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "rtts_denoise": [_vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp],
+    "rtts_gl_magnitudes": [_vp, _i64, _i64, _i64, _vp, C.POINTER(_i64), _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
+    "rtts_gl_init": [_vp, _i64, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _i32, _u32, _i32, _i32, _vp, _vp],
+    "rtts_gl_step": [_vp, _vp, _f32, _vp, _i64, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
 }
 
 _lib = None

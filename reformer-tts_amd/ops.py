@@ -364,6 +364,105 @@ def denoise(audio: torch.Tensor, sample_offsets_host, offsets: torch.Tensor, nse
     return out
 
 
+def _gl_check(who: str, tensors, offsets: torch.Tensor, nseg: int, mag: torch.Tensor, col_offsets_host, n_fft: int) -> None:
+    """The checks the three Griffin-Lim ops share: device and dtype by name, the (2, nseg + 1) offset table, mag's rows."""
+    for name, t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise _lib.RttsError(f"{who} runs on the GPU only: {name} must be a CUDA float32 tensor "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.shape == (2, nseg + 1) and offsets.is_contiguous()):
+        raise ValueError(f"offsets: expected a contiguous CUDA int64 (2, {nseg + 1}) table [sample offsets; column offsets]")
+    if not (mag.dim() == 2 and mag.shape[0] == n_fft // 2 + 1 and mag.stride(1) == 1 and mag.stride(0) >= mag.shape[1]):
+        raise ValueError(f"{who}: mag must be (n_fft / 2 + 1 = {n_fft // 2 + 1}, columns) rows (got shape {tuple(mag.shape)})")
+    if col_offsets_host[0] < 0 or mag.shape[1] < col_offsets_host[nseg]:
+        raise ValueError(f"{who}: mag has {mag.shape[1]} columns for col_offsets from {col_offsets_host[0]} to {col_offsets_host[nseg]}")
+
+
+def gl_magnitudes(mel: torch.Tensor, mel_start_host, mel_start: torch.Tensor, col_offsets_host, offsets: torch.Tensor, nseg: int,
+                  pinv: torch.Tensor, power: int, n_fft: int, mag: torch.Tensor) -> torch.Tensor:
+    """Step 1 of Griffin-Lim (``rtts_gl_magnitudes``): mel = log-mel, f32, read in place -- (nseg, n_mels, L) of any strides, or packed
+    (n_mels, sum L); utterance s starts at frame ``mel_start[s]`` of it (i64 (nseg,) on the device, the same values as host ints) and
+    has ``col_offsets[s+1] - col_offsets[s] - 1`` frames; offsets: (2, nseg + 1) i64 device table [sample offsets; column offsets],
+    the column offsets also as a host ``ctypes.c_int64`` array; pinv (n_fft/2 + 1, n_mels) f32 -> mag (n_fft/2 + 1, >= columns) f32
+    = max(0, pinv @ exp(mel))^(1/power), column L of an utterance repeating column L - 1.  One launch on the current stream."""
+    _gl_check("gl_magnitudes", (("mel", mel), ("pinv", pinv), ("mag", mag)), offsets, nseg, mag, col_offsets_host, n_fft)
+    if not (pinv.dim() == 2 and pinv.is_contiguous() and pinv.shape[0] == n_fft // 2 + 1):
+        raise ValueError(f"gl_magnitudes: pinv must be contiguous (n_fft / 2 + 1, n_mels) (got shape {tuple(pinv.shape)})")
+    n_mels = pinv.shape[1]
+    if mel.dim() == 3 and mel.shape[0] == nseg and mel.shape[1] == n_mels:
+        sb, sc, st = mel.stride()
+    elif mel.dim() == 2 and mel.shape[0] == n_mels:
+        sb, (sc, st) = 0, mel.stride()
+    else:
+        raise ValueError(f"gl_magnitudes: mel must be ({nseg}, {n_mels}, L) or packed ({n_mels}, frames) (got shape {tuple(mel.shape)})")
+    if min(sb, sc, st) < 0:
+        raise ValueError("gl_magnitudes: mel must not have negative strides")
+    if not (mel_start.is_cuda and mel_start.dtype == torch.int64 and mel_start.dim() == 1 and mel_start.numel() >= nseg
+            and mel_start.is_contiguous() and len(mel_start_host) >= nseg):
+        raise ValueError(f"mel_start: expected a contiguous CUDA int64 table of {nseg} first frames and the same values on the host")
+    for s in range(nseg):
+        frames = col_offsets_host[s + 1] - col_offsets_host[s] - 1
+        if frames < 0 or mel_start_host[s] < 0 or mel_start_host[s] + frames > mel.shape[-1]:
+            raise ValueError(f"gl_magnitudes: utterance {s} of {frames} frames from frame {mel_start_host[s]} does not lie in mel of "
+                             f"{mel.shape[-1]} frames (mel_start / col_offsets)")
+    ev = TIMING.start(f"rtts_gl_magnitudes/n{n_fft}")
+    _lib.call("rtts_gl_magnitudes", mel.data_ptr(), sb, sc, st, mel_start.data_ptr(), col_offsets_host, offsets[1].data_ptr(), nseg,
+              pinv.data_ptr(), n_mels, int(power), n_fft, mag.data_ptr(), mag.stride(0), _stream())
+    TIMING.stop(ev, 2.0 * col_offsets_host[nseg] * n_mels * (n_fft // 2 + 1))
+    return mag
+
+
+def _gl_audio(who: str, buffers, sample_offsets_host, nseg: int, dft_basis: torch.Tensor, idft_basis: torch.Tensor, n_fft: int) -> None:
+    for name, t in buffers:
+        if not (t.dim() == 1 and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be flat and contiguous (got shape {tuple(t.shape)})")
+        if sample_offsets_host[0] < 0 or t.numel() < sample_offsets_host[nseg]:
+            raise ValueError(f"{who}: {name} has {t.numel()} samples for sample_offsets ending at {sample_offsets_host[nseg]}")
+    if not (dft_basis.is_contiguous() and idft_basis.is_contiguous() and tuple(dft_basis.shape) == (n_fft, n_fft)
+            and tuple(idft_basis.shape) == (n_fft, n_fft)):
+        raise ValueError(f"{who}: dft_basis and idft_basis must be contiguous (n_fft, n_fft)")
+
+
+def gl_init(mag: torch.Tensor, col_offsets_host, sample_offsets_host, offsets: torch.Tensor, nseg: int, dft_basis: torch.Tensor,
+            idft_basis: torch.Tensor, phase: str, seed: int, n_fft: int, hop: int, out: torch.Tensor) -> torch.Tensor:
+    """Step 2 of Griffin-Lim (``rtts_gl_init``): mag from ``gl_magnitudes``; offsets: (2, nseg + 1) i64 device table [sample offsets;
+    column offsets] and the same values as two host ``ctypes.c_int64`` arrays; phase "hash" (phases from ``rtts_drop_hash(seed, .)``)
+    or "zero" -> out, flat f32: utterance s = iSTFT(mag e^{i phi}) over its sample offsets, zeros where it has fewer than three
+    frames.  One launch on the current stream."""
+    if phase not in ("hash", "zero"):
+        raise ValueError(f"gl_init: phase must be 'hash' or 'zero' (got {phase!r})")
+    _gl_check("gl_init", (("mag", mag), ("dft_basis", dft_basis), ("idft_basis", idft_basis), ("out", out)), offsets, nseg, mag,
+              col_offsets_host, n_fft)
+    _gl_audio("gl_init", (("out", out),), sample_offsets_host, nseg, dft_basis, idft_basis, n_fft)
+    ev = TIMING.start(f"rtts_gl_init/n{n_fft}")
+    _lib.call("rtts_gl_init", mag.data_ptr(), mag.stride(0), col_offsets_host, offsets[1].data_ptr(), sample_offsets_host,
+              offsets[0].data_ptr(), nseg, dft_basis.data_ptr(), idft_basis.data_ptr(), 1 if phase == "hash" else 0,
+              int(seed) & 0xFFFFFFFF, n_fft, hop, out.data_ptr(), _stream())
+    TIMING.stop(ev, 2.0 * col_offsets_host[nseg] * n_fft * n_fft)
+    return out
+
+
+def gl_step(cur: torch.Tensor, prev: Optional[torch.Tensor], beta: float, mag: torch.Tensor, col_offsets_host, sample_offsets_host,
+            offsets: torch.Tensor, nseg: int, dft_basis: torch.Tensor, idft_basis: torch.Tensor, n_fft: int, hop: int,
+            out: torch.Tensor) -> torch.Tensor:
+    """One Griffin-Lim iteration (``rtts_gl_step``): out = iSTFT(mag R / |R|), R = STFT(cur - beta prev), per utterance over the
+    sample offsets; ``prev`` may be None (the first iteration, or beta = 0).  ``out`` may overlap neither ``cur`` nor ``prev``.
+    Tables as for ``gl_init``.  One launch on the current stream."""
+    tensors = [("cur", cur), ("mag", mag), ("dft_basis", dft_basis), ("idft_basis", idft_basis), ("out", out)]
+    buffers = [("cur", cur), ("out", out)]
+    if prev is not None:
+        tensors.append(("prev", prev))
+        buffers.append(("prev", prev))
+    _gl_check("gl_step", tensors, offsets, nseg, mag, col_offsets_host, n_fft)
+    _gl_audio("gl_step", buffers, sample_offsets_host, nseg, dft_basis, idft_basis, n_fft)
+    ev = TIMING.start(f"rtts_gl_step/n{n_fft}")
+    _lib.call("rtts_gl_step", cur.data_ptr(), _ptr(prev), float(beta), mag.data_ptr(), mag.stride(0), col_offsets_host,
+              offsets[1].data_ptr(), sample_offsets_host, offsets[0].data_ptr(), nseg, dft_basis.data_ptr(), idft_basis.data_ptr(), n_fft,
+              hop, out.data_ptr(), _stream())
+    TIMING.stop(ev, 4.0 * col_offsets_host[nseg] * n_fft * n_fft)
+    return out
+
+
 def sw_inv1x1_factor(weights) -> Tuple[list, torch.Tensor]:
     """The invertible 1x1 convolutions of a SqueezeWave factored on the device: ``weights`` = CUDA float32 (n, n) contiguous
     matrices, 1 <= n <= 128 -> (their inverses, fp32 rounded once from the float64 elimination; slogdet (len, 2) float64 on the

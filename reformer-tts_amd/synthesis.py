@@ -15,6 +15,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from .griffin_lim import GriffinLim, GriffinLimTables  # noqa: F401  (the vocoder that needs no training)
 from .squeeze_wave.modules import host_lengths, segment_offsets  # noqa: F401  (re-exported for callers that pack by hand)
 
 
@@ -65,7 +66,8 @@ def vocode_trimmed(vocoder, spectrogram: torch.Tensor, stop, *, sigma: float = 0
     before it is split, so every waveform is what ``denoiser.forward`` makes of the waveform without it (utterances of one or
     two frames are too short to denoise and come back as vocoded)."""
     frames = frame_counts(stop.cpu() if torch.is_tensor(stop) else stop, spectrogram.shape[2], max_len)
-    if not use_graph or noise is not None or sum(frames) == 0:
+    # a vocoder without capture_ragged (griffin_lim.GriffinLim) runs its stage eagerly whatever use_graph says
+    if not use_graph or noise is not None or sum(frames) == 0 or not hasattr(vocoder, "capture_ragged"):
         packed, waves = vocoder.infer_ragged(spectrogram, frames, sigma=sigma, noise=noise)
         if denoiser is None or sum(frames) == 0:
             return waves
