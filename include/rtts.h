@@ -755,6 +755,50 @@ int rtts_infer_metrics(const float* gen, int64_t gs_b, int64_t gs_mel, int64_t g
                        int64_t ts_mel, int64_t ts_t, int64_t truth_frames, const int64_t* frame_offsets, int n_utt, const int32_t* ids,
                        const int64_t* starts, const int32_t* lengths, int B, int n_mel, int lm, int longest, double* partials, double* sse,
                        double* stop_err, double* totals, void* stream);
+/* B generated spectrograms aligned to their truths by dynamic time warping (csrc/dtw.hip): the path cost and path length behind
+ * MCD-DTW, the number that survives a generation running a few frames early, late or at another rate, which the frame-by-frame
+ * rtts_infer_metrics above does not.  Not in the reference.  Four kernels on `stream`, nothing read back, no atomics; the call can
+ * be captured in a hipGraph.
+ *   gen, gen_stop, truth and the two truth descriptions: exactly the arguments of rtts_infer_metrics, with L <= rtts_dtw_max_frames()
+ *   slot b          compares its first N_b = min(gen_stop[b], L) generated frames (L when gen_stop is null) with its M_b = len_b truth
+ *                   frames; both lengths are read on the device
+ *   lm              a host upper bound of every M_b, 1..rtts_dtw_max_frames() (a slot with M_b > lm is not scored)
+ *   basis           f32 (n_proj, n_mel) row-major, nullable: every compared frame x becomes p[k] = f32(sum_m f64(basis[k, m]) f64(x[m])),
+ *                   m ascending.  Null: the frames are compared as they are, and n_proj must be n_mel.  Which basis makes the result
+ *                   a mel-cepstral distortion is the caller's business (evaluation.cepstral_basis)
+ *   workspace       rtts_dtw_workspace_bytes(B, L, lm, n_proj) bytes (-1 for sizes the call would reject), overwritten.  It begins
+ *                   with the projected generated frames, f32 (B, max(L, 1), n_proj) (tests read them)
+ *   phases          RTTS_DTW_ALL.  A subset runs only those kernels on what an earlier call left in the workspace and the
+ *                   outputs: for timing the phases one by one, nothing else
+ * With d(i, j) = sqrtf(sum_k (p_i[k] - q_j[k])^2) in f32, computed FROM THE DIFFERENCES with k ascending (never as
+ * |p|^2 + |q|^2 - 2 p.q, which cancels exactly where a good generation sits; a distance past the f32 range counts as FLT_MAX),
+ * and widened to f64:
+ *   D(0, 0) = d(0, 0);  D(i, j) = d(i, j) + the first minimal of D(i-1, j-1), D(i-1, j), D(i, j-1) in this order (a later one replaces
+ *   an earlier one only when strictly smaller; predecessors outside the table do not exist);  S(i, j) = S of the chosen one + 1,
+ *   S(0, 0) = 1
+ * Outputs:
+ *   cost[b]    f64 = D(N_b - 1, M_b - 1)            steps[b]  i32 = S(N_b - 1, M_b - 1), in [max(N_b, M_b), N_b + M_b - 1]
+ *   totals[0]  f64 = mean_b cost[b] / steps[b]      totals[1] f64 = sum_b cost[b] / sum_b steps[b]
+ * Every cell has one evaluation and every sum one fixed order: the outputs depend on the arguments alone -- not on the strides,
+ * not on which truth description named the frames -- and a second call gives the same bits.
+ * A slot with N_b = 0 or M_b > lm, one whose description leaves [0, truth_frames] or is empty, or whose id is outside [0, n_utt),
+ * is never read: cost NaN, steps 0.  A non-finite value in a COMPARED frame (or in its projection) is detected while
+ * projecting and gives the slot cost NaN, steps 0 as well: the recurrence never orders NaNs; frames at or past N_b / M_b are
+ * not read, so a NaN there reaches nothing.  Either case makes both totals NaN.
+ * Supported: B in 1..65535, 1 <= n_mel <= 128, 1 <= n_proj <= 128, 0 <= L <= rtts_dtw_max_frames() (2048), 1 <= lm <=
+ * rtts_dtw_max_frames(); anything else, a null pointer, neither or both truth descriptions, or a workspace smaller than
+ * rtts_dtw_workspace_bytes is rejected before any launch by the argument's name. */
+#define RTTS_DTW_PROJECT 1
+#define RTTS_DTW_DISTANCES 2
+#define RTTS_DTW_RECURRENCE 4
+#define RTTS_DTW_FOLD 8
+#define RTTS_DTW_ALL 15
+int rtts_dtw_max_frames(void);
+int64_t rtts_dtw_workspace_bytes(int B, int L, int lm, int n_proj);
+int rtts_dtw_align(const float* gen, int64_t gs_b, int64_t gs_mel, int64_t gs_t, int L, const int64_t* gen_stop, const float* truth,
+                   int64_t ts_mel, int64_t ts_t, int64_t truth_frames, const int64_t* frame_offsets, int n_utt, const int32_t* ids,
+                   const int64_t* starts, const int32_t* lengths, int B, int n_mel, int lm, const float* basis, int n_proj,
+                   void* workspace, int64_t workspace_bytes, int phases, double* cost, int32_t* steps, double* totals, void* stream);
 
 /* ---- Audio -> log-mel spectrogram (dataset preprocessing) ---------
  * Replaces the spectrogram creators of reference reformer_tts/dataset/convert.py:86-123 (Tacotron2SpectrogramCreator; :34-84

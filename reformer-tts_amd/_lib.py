@@ -159,6 +159,10 @@ SIGNATURES = {
     "rtts_infer_metrics_tiles": [_i32],
     "rtts_infer_metrics": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                            _vp, _vp],
+    "rtts_dtw_max_frames": [],
+    "rtts_dtw_workspace_bytes": [_i32, _i32, _i32, _i32],
+    "rtts_dtw_align": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i64,
+                       _i32, _vp, _vp, _vp, _vp],
     "rtts_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
     "rtts_mel_frames": [_i64, _i32],
     "rtts_mel_spectrogram": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
@@ -225,6 +229,7 @@ def load() -> C.CDLL:
         lib.rtts_mel_frames.restype = C.c_int64
         lib.rtts_resample_len.restype = C.c_int64
         lib.rtts_full_attn_bwd_workspace.restype = C.c_int64
+        lib.rtts_dtw_workspace_bytes.restype = C.c_int64
         _lib = lib
         # A/B scripts may name a run length in the environment: read ONCE, here -- the library's launch path reads none
         fw, bw = os.environ.get("RTTS_LSH_FWD_WALK"), os.environ.get("RTTS_LSH_BWD_WALK")

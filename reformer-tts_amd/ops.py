@@ -640,3 +640,84 @@ def infer_metrics(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: to
               partials.data_ptr(), sse.data_ptr(), stop_err.data_ptr(), totals.data_ptr(), _stream())
     TIMING.stop(ev, 0.0)
     return sse, stop_err, totals
+
+
+DTW_ALL = 15           # RTTS_DTW_ALL of include/rtts.h: project | distances | recurrence | fold
+
+
+def dtw_max_frames() -> int:
+    """The largest ``L`` and ``lm`` ``dtw_align`` takes (``rtts_dtw_max_frames``)."""
+    return int(_lib.load().rtts_dtw_max_frames())
+
+
+def dtw_align(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: torch.Tensor, lm: int, *, basis: Optional[torch.Tensor] = None,
+              gen_frames_last: bool = True, truth_frames_last: bool = True, frame_offsets: Optional[torch.Tensor] = None,
+              ids: Optional[torch.Tensor] = None, starts: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
+              _phases: int = DTW_ALL, _state=None):
+    """B generated spectrograms aligned to their truths by dynamic time warping (``rtts_dtw_align``), with the operands of
+    ``infer_metrics``: ``gen`` f32 3-D with any strides, (B, n_mel, L) or, with ``gen_frames_last=False``, (B, T, n_mel);
+    ``gen_stop`` int64 (B,) or None; ``truth`` f32 2-D, (n_mel, frames) or, with ``truth_frames_last=False``, (frames, n_mel) rows,
+    slot b's frames named by exactly one of ``frame_offsets`` (+ ``ids``) or ``starts`` + ``lengths``, all ON THE DEVICE.  Slot b
+    compares its first min(gen_stop[b], L) generated frames (L without ``gen_stop``) with its own truth frames; ``lm`` is a host
+    upper bound of the truth lengths.  ``basis`` f32 (n_proj, n_mel) contiguous or None: the linear projection every compared
+    frame goes through before the Euclidean frame distance (``evaluation.cepstral_basis`` makes the result an MCD in dB).
+    -> (cost f64 (B,) = the summed distance along the optimal path, steps int32 (B,) = the path's length, totals f64 (2,) =
+    [mean_b cost/steps, Σ cost / Σ steps]).  A slot that cannot be scored (no generated frame, a bad description, a non-finite
+    compared value) has cost NaN and steps 0, and makes the totals NaN.  One call on the current stream, nothing read back:
+    capturable.  ``_phases`` / ``_state``: scripts/dtw_bench.py times the four kernels one by one on a previous call's buffers."""
+    corpus, padded = frame_offsets is not None, (starts is not None or lengths is not None)
+    if corpus == padded or (padded and (starts is None or lengths is None)) or (ids is not None and not corpus):
+        raise ValueError("dtw_align: describe the truth by frame_offsets (+ ids) or by starts + lengths: exactly one of the two")
+    named = (("gen", gen, torch.float32, False), ("gen_stop", gen_stop, torch.int64, True), ("truth", truth, torch.float32, False),
+             ("basis", basis, torch.float32, True), ("frame_offsets", frame_offsets, torch.int64, True), ("ids", ids, torch.int32, True),
+             ("starts", starts, torch.int64, True), ("lengths", lengths, torch.int32, True))
+    for name, t, dt, optional in named:
+        if t is None and optional:
+            continue
+        if not (torch.is_tensor(t) and t.dtype == dt):
+            raise ValueError(f"dtw_align: {name} must be a {dt} tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+    dev = gen.device
+    for name, t, dt, optional in named:
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise _lib.RttsError(f"dtw_align runs on the GPU only: {name} must be a CUDA {dt} tensor on {dev} (got one on {t.device})")
+    if gen.dim() != 3 or truth.dim() != 2:
+        raise ValueError(f"dtw_align: gen must be 3-D and truth 2-D (got {tuple(gen.shape)} and {tuple(truth.shape)})")
+    b = gen.shape[0]
+    n_mel, frames, gs_mel, gs_t = (gen.shape[1], gen.shape[2], gen.stride(1), gen.stride(2)) if gen_frames_last else \
+        (gen.shape[2], gen.shape[1], gen.stride(2), gen.stride(1))
+    t_mel, t_frames, ts_mel, ts_t = (truth.shape[0], truth.shape[1], truth.stride(0), truth.stride(1)) if truth_frames_last else \
+        (truth.shape[1], truth.shape[0], truth.stride(1), truth.stride(0))
+    if t_mel != n_mel:
+        raise ValueError(f"dtw_align: gen has {n_mel} mel channels, truth {t_mel}")
+    n_proj = n_mel
+    if basis is not None:
+        if not (basis.dim() == 2 and basis.shape[1] == n_mel and basis.shape[0] >= 1 and basis.is_contiguous()):
+            raise ValueError(f"dtw_align: basis must be contiguous of shape (n_proj, {n_mel}), got {tuple(basis.shape)}")
+        n_proj = basis.shape[0]
+    for name, t in (("gen_stop", gen_stop), ("ids", ids), ("starts", starts), ("lengths", lengths)):
+        if t is not None and not (tuple(t.shape) == (b,) and t.is_contiguous()):
+            raise ValueError(f"dtw_align: {name} must be contiguous of shape ({b},), got {tuple(t.shape)}")
+    n_utt = 0
+    if corpus:
+        n_utt = frame_offsets.numel() - 1
+        if not (frame_offsets.dim() == 1 and frame_offsets.is_contiguous() and n_utt >= 1):
+            raise ValueError("dtw_align: frame_offsets must be contiguous of shape (n + 1,), n >= 1")
+    lm = int(lm)
+    lib = _lib.load()
+    most = int(lib.rtts_dtw_max_frames())
+    for name, v in (("L", frames), ("lm", lm)):
+        if v > most:
+            raise ValueError(f"dtw_align: {name} = {v} frames exceeds rtts_dtw_max_frames() = {most}")
+    if _state is None:
+        need = int(lib.rtts_dtw_workspace_bytes(b, frames, lm, n_proj))
+        if need < 0:
+            raise ValueError(f"dtw_align: unsupported sizes B = {b}, L = {frames}, lm = {lm}, n_proj = {n_proj} (include/rtts.h, rtts_dtw_align)")
+        out = torch.empty(b + 2, dtype=torch.float64, device=dev)
+        _state = (torch.empty(need, dtype=torch.uint8, device=dev), out[:b], torch.empty(b, dtype=torch.int32, device=dev), out[b:])
+    work, cost, steps, totals = _state
+    ev = TIMING.start("rtts_dtw_align")
+    _lib.call("rtts_dtw_align", gen.data_ptr() if frames else None, gen.stride(0), gs_mel, gs_t, frames, _ptr(gen_stop), truth.data_ptr(),
+              ts_mel, ts_t, t_frames, _ptr(frame_offsets), n_utt, _ptr(ids), _ptr(starts), _ptr(lengths), b, n_mel, lm, _ptr(basis), n_proj,
+              work.data_ptr(), work.numel(), int(_phases), cost.data_ptr(), steps.data_ptr(), totals.data_ptr(), _stream())
+    TIMING.stop(ev, 0.0)
+    return cost, steps, totals

@@ -786,7 +786,8 @@ class Trainer:
         self.model.dec.reformer.collect_attention = was_collect
         self.model.train(was_training)
 
-    def _validate_inference(self, phonemes, truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder, return_outputs):
+    def _validate_inference(self, phonemes, truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder, return_outputs,
+                            dtw=False):
         from .. import ops
         if combine_strategy not in ("concat", "replace"):
             raise ValueError(f"validate_inference: combine_strategy must be 'concat' or 'replace' (got {combine_strategy!r})")
@@ -805,13 +806,19 @@ class Trainer:
         sse, stop_err, totals = ops.infer_metrics(spec, stop, lm=lm, **truth_kw)
         out = {f"{combine_strategy}_inference_pred_mse": totals[0], f"{combine_strategy}_inference_stop_mae": totals[1],
                f"{combine_strategy}_inference_time": inference_time, "sse": sse, "stop_err": stop_err}
+        if dtw:                                                # one more call on the tensors the metrics above read
+            from .. import evaluation
+            where = {k: v for k, v in truth_kw.items() if k != "longest"}
+            out["mcd"], out["dtw_steps"], dtw_totals = evaluation.mel_cepstral_distortion(spec, stop, lm=lm, **where)
+            out[f"{combine_strategy}_inference_mcd"] = dtw_totals[0]
         if return_outputs:
             out["spectrogram"], out["stop"] = spec, stop
         return out
 
     @torch.no_grad()
     def validate_inference(self, batch, combine_strategy: str = "concat", *, max_len: int = 1024, stop_threshold: float = 0.25,
-                           use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False) -> dict:
+                           use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False,
+                           dtw: bool = False) -> dict:
         """``LitReformerTTS.validate_inference`` (``wrappers.py:165-211``) without the plots, on a device batch in the reference's
         collate layout: ``model.infer`` on the batch's phonemes with ``stop_at_stop_token = (cfg.stop_loss_weight != 0)``
         (``:180``), then ONE ``rtts_infer_metrics`` call that scores the generated spectrogram against
@@ -828,7 +835,13 @@ class Trainer:
 
         ``use_graph`` (default: on for "concat" on the GPU) generates with one hipGraph replay per frame; "replace" runs the eager
         loop.  Parameters, Adam moments, ``global_step``, the train/eval mode, ``collect_attention``, the stacks' executor flags
-        and the per-shape training graph cache are left as they were."""
+        and the per-shape training graph cache are left as they were.
+
+        ``dtw=True`` adds what the frame-by-frame numbers above cannot say about a generation that is right but early, late or
+        at another rate (not in the reference): ``f"{strategy}_inference_mcd"``, the batch's mean MCD-DTW in dB as an f64 DEVICE
+        scalar, and the per-utterance ``mcd`` (f64) and ``dtw_steps`` (int32), from ONE ``rtts_dtw_align`` call
+        (``evaluation.mel_cepstral_distortion``) on the same tensors: the first min(stop_b, L) generated frames aligned to the
+        utterance's truth.  The other entries are the same bits with and without it."""
         spec = batch["spectrogram"]
         b, rows, n_mel = spec.shape
         spec = spec if spec.is_contiguous() else spec.contiguous()
@@ -836,11 +849,12 @@ class Trainer:
                         starts=torch.arange(b, dtype=torch.int64, device=spec.device) * rows + 1,
                         lengths=(batch["stop_tokens"].argmax(dim=1) + 1).to(torch.int32))
         return self._validate_inference(batch["phonemes"], truth_kw, rows - 1, combine_strategy, max_len, stop_threshold, use_graph,
-                                        cache_encoder, return_outputs)
+                                        cache_encoder, return_outputs, dtw)
 
     @torch.no_grad()
     def validate_inference_corpus(self, corpus, ids, combine_strategy: str = "concat", *, max_len: int = 1024, stop_threshold: float = 0.25,
-                                  use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False) -> dict:
+                                  use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False,
+                                  dtw: bool = False) -> dict:
         """``validate_inference`` on the utterances ``ids`` (host ints) of a ``dataset.TTSCorpus``: ``rtts_tts_collate`` writes the
         padded phonemes alone, and the generated spectrogram is scored against ``corpus.mel`` in place through the corpus's
         frame offsets and the ids -- no padded truth batch is built.  Same dictionary, same bits as the batch form."""
@@ -851,17 +865,19 @@ class Trainer:
         corpus._launch(dev_ids, lm, None, 0, phonemes=phonemes)
         truth_kw = dict(truth=corpus.mel, frame_offsets=corpus.tables[0], ids=dev_ids, longest=lm)
         return self._validate_inference(phonemes[:, :lp], truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder,
-                                        return_outputs)
+                                        return_outputs, dtw)
 
     @torch.no_grad()
-    def validation_epoch(self, corpus, ids, batch_size: Optional[int] = None, inference: bool = True, **inference_kwargs) -> Dict[str, float]:
+    def validation_epoch(self, corpus, ids, batch_size: Optional[int] = None, inference: bool = True, dtw: bool = False,
+                         **inference_kwargs) -> Dict[str, float]:
         """The reference's validation epoch without the plotting: ``val_dataloader`` (``wrappers.py:224-232``: batches of
         ``batch_size``, default ``cfg.batch_size``, in order, the incomplete last batch dropped), ``validation_step`` on each
         (``validate_corpus``), ``validation_epoch_end``'s mean over batches of the five values (``:131-158``) and, with
         ``inference``, ``validate_inference_corpus`` on the first ``batch_size`` ids (``:166-168``; ``inference_kwargs``, e.g.
         ``max_len``, pass through to it).  -> the reference's log dictionary as host floats: ``val_loss``, ``val_stop_loss``,
         ``val_raw_pred_loss``, ``val_post_pred_loss``, ``val_stop_mae`` and the three ``concat_inference_*`` entries.  Everything
-        is accumulated on the device and read once."""
+        is accumulated on the device and read once.  ``dtw=True`` (with ``inference``) adds ``concat_inference_mcd``, the MCD-DTW
+        of ``validate_inference_corpus(dtw=True)``, to the same single read."""
         ids = [int(i) for i in ids]
         bs = int(self.cfg.batch_size if batch_size is None else batch_size)
         if bs < 1 or len(ids) < bs:
@@ -874,9 +890,10 @@ class Trainer:
         names = ["val_loss", "val_raw_pred_loss", "val_post_pred_loss", "val_stop_loss", "val_stop_mae"]
         inference_time = None
         if inference:
-            inf = self.validate_inference_corpus(corpus, ids[:bs], "concat", **inference_kwargs)
-            values = torch.cat([values, torch.stack([inf["concat_inference_pred_mse"], inf["concat_inference_stop_mae"]])])
-            names += ["concat_inference_pred_mse", "concat_inference_stop_mae"]
+            inf = self.validate_inference_corpus(corpus, ids[:bs], "concat", dtw=dtw, **inference_kwargs)
+            extra = ["concat_inference_pred_mse", "concat_inference_stop_mae"] + (["concat_inference_mcd"] if dtw else [])
+            values = torch.cat([values, torch.stack([inf[k] for k in extra])])
+            names += extra
             inference_time = inf["concat_inference_time"]
         logs = dict(zip(names, values.cpu().tolist()))
         if inference:
