@@ -291,6 +291,43 @@ int rtts_full_attn_bwd(const void* qk, const void* v, int64_t ld, const uint8_t*
                        const float* lse, const float* delta, int B, int H, int T, int dh, int causal, void* dqk, void* dv,
                        int64_t ld_d, void* workspace, float drop_p, uint32_t drop_seed, const uint32_t* seed_dev, void* stream);
 
+/* ---- single-query attention over a frame cache (incremental generation, csrc/decode.hip) -----------------
+ * One new decoder position per utterance.  VALU kernels (M = 1), bounded by the read of the keys and values.
+ *   rtts_decode_self_attn   row bf16 (B, 2*H*64) = [qk | v] of the new position (stride ld_row); cache bf16 (B, cap, 2*H*64), row
+ *                           stride ld_cache, cache_batch_stride elements between two utterances; pos: a DEVICE int32 p = rows
+ *                           already cached, shared by the batch and read when the kernel runs (one captured launch serves every
+ *                           frame).  The call writes `row` into cache[b, p] exactly once, touches no other cache row, and takes key
+ *                           and value of position p from `row`.  Per (b, h): s_j = (q . k_j) / (8 max(|k_j|, 1e-12)) for j < p,
+ *                           s_p = -5e4, P = softmax over j <= p, o = sum_j P_j v_j as bf16 (B, H*64) stride ld_o: row p of
+ *                           rtts_full_attn_fwd (causal, every position valid) with P and the P V sum kept in fp32.  p = 0: o = v_0.
+ *                           cap a multiple of 64, 64 <= cap <= rtts_full_attn_max_t(64).  p outside [0, cap): nothing is written to
+ *                           the cache and every o is NaN -- never an out-of-range access.  Cache rows >= p are not read.
+ *   rtts_decode_cross_attn  q bf16 (B, H*dh) stride ld_q; kv, kvalid as rtts_xattn_fwd (dh 64 or 128, T_k a multiple of 128 up to
+ *                           2048); s_j = q . k_j / sqrt(dh); keys with kvalid = 0 have P exactly 0; a sample without any valid key
+ *                           gets o = NaN and leaves the other samples' bits alone.  o bf16 (B, H*dh) stride ld_o.
+ *   splits                  a (b, h) is worked by `splits` workgroups (1 ... 64); key tiles of 64 are dealt round-robin (split s takes
+ *                           tiles s, s + S, ...), each split leaves an fp32 partial (running maximum, normaliser, dh accumulators)
+ *                           in `workspace` (rtts_decode_attn_workspace bytes, 16-byte aligned) and a second launch folds them in
+ *                           split order; a split without keys contributes exactly nothing.  splits = 1: no second launch,
+ *                           workspace may be NULL.  splits = 0: rtts_decode_attn_splits(B*H, cap or T_k), a host function of its
+ *                           arguments only (-1 for sizes the calls reject; the workspace function likewise).  No atomics: two calls
+ *                           give the same bits; two split counts differ by fp32 summation order only.
+ *   rtts_decode_tail_im2col the postnet tail: im2col rows [tap][channel] (bf16, 5*CP wide) of window rows r0 ... R - 1 of the
+ *                           R = 2 n + 1 positions that end at p = *pos (window row w <-> position p - (R - 1) + w).  src_abs = 1: src
+ *                           fp32 (B, cap, C) indexed by position; 0: bf16 plain rows of window rows src_r0 ... R - 1 per utterance
+ *                           (src_batch_stride elements apart).  Rows in front of position 0 or behind p, channels >= C and a p
+ *                           outside [0, cap) give zeros.  dst row b * (R - r0) + (r - r0).
+ * Bad arguments return an error naming the argument (rtts_last_error) and launch nothing. */
+int rtts_decode_attn_splits(int BH, int T);
+int64_t rtts_decode_attn_workspace(int BH, int splits, int dh);
+int rtts_decode_self_attn(const void* row, int64_t ld_row, void* cache, int64_t ld_cache, int64_t cache_batch_stride,
+                          const int32_t* pos, int B, int H, int cap, int dh, void* o, int64_t ld_o,
+                          int splits, void* workspace, void* stream);
+int rtts_decode_cross_attn(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
+                           int B, int H, int Tk, int dh, void* o, int64_t ld_o, int splits, void* workspace, void* stream);
+int rtts_decode_tail_im2col(const void* src, int src_abs, int64_t ld_src, int64_t src_batch_stride, int src_r0, int C,
+                            const int32_t* pos, int cap, int B, int R, int r0, int nr, int CP, void* dst, void* stream);
+
 /* ---- convolutional edges (prenet / postnet) and the loss ------------------------------------------
  * Reference reformer_tts/model/modules.py:8-61 (EncoderPreNet), :103-169 (PostConvNet); loss.py:28-53.
  * HALO ROWS.  The activations of a convolution stack are channels-last rows (B, L + 2*halo, C), halo = 2, with `halo` zero

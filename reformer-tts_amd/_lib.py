@@ -97,6 +97,11 @@ SIGNATURES = {
     "rtts_full_attn_bwd_workspace": [_i32, _i32, _i32, _i32],
     "rtts_full_attn_bwd": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _f32, _u32, _vp,
                            _vp],
+    "rtts_decode_attn_splits": [_i32, _i32],
+    "rtts_decode_attn_workspace": [_i32, _i32, _i32],
+    "rtts_decode_self_attn": [_vp, _i64, _vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp],
+    "rtts_decode_cross_attn": [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp],
+    "rtts_decode_tail_im2col": [_vp, _i32, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "rtts_conv1d_k5": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp],
     "rtts_to_halo": [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i64, _vp],
     "rtts_heads_grad": [_vp, _vp, _i32, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
@@ -230,6 +235,7 @@ def load() -> C.CDLL:
         lib.rtts_resample_len.restype = C.c_int64
         lib.rtts_full_attn_bwd_workspace.restype = C.c_int64
         lib.rtts_dtw_workspace_bytes.restype = C.c_int64
+        lib.rtts_decode_attn_workspace.restype = C.c_int64
         _lib = lib
         # A/B scripts may name a run length in the environment: read ONCE, here -- the library's launch path reads none
         fw, bw = os.environ.get("RTTS_LSH_FWD_WALK"), os.environ.get("RTTS_LSH_BWD_WALK")

@@ -190,7 +190,8 @@ class ReformerTTS(nn.Module):
     @torch.no_grad()
     def infer(self, phonemes: torch.LongTensor, combine_strategy: str = "concat", max_len: int = 1024,
               stop_threshold: float = 0.25, verbose: bool = False, stop_at_stop_token: bool = True,
-              cache_encoder: bool = False, check_every: int = 8, use_graph: bool = False) -> Tuple[torch.Tensor, torch.LongTensor]:
+              cache_encoder: bool = False, check_every: int = 8, use_graph: bool = False,
+              incremental: bool = False) -> Tuple[torch.Tensor, torch.LongTensor]:
         """``reformer_tts.py:145-221``: autoregressive generation by repeated full forwards over the spectrogram
         generated so far.  Same arguments, same results -- (spectrogram (B, n_mels, L), stop_idx (B,)) -- including the
         loop guard ``max(spectrogram.shape) > max_len`` (the shape includes the mel axis: ``max_len < n_mels`` ends
@@ -203,12 +204,21 @@ class ReformerTTS(nn.Module):
           back to where the reference's loop would have ended; "replace" rewrites every frame and checks every time);
         * ``cache_encoder=True`` runs the encoder once instead of once per frame.  That IS visible -- the reference
           re-draws the LSH rotations of the encoder in every forward -- hence off by default;
-        * ``use_graph=True`` ("concat" only): one frame = one hipGraph replay (see ``_infer_graphed``)."""
+        * ``use_graph=True`` ("concat" only): one frame = one hipGraph replay (see ``_infer_graphed``);
+        * ``incremental=True`` ("concat" only, an all-dense decoder -- ``use_full_attn`` -- only): one frame = ONE decoder row
+          per utterance against a per-layer cache instead of a forward over the whole window (``model/incremental.py``).  It
+          implies the cached encoder, and it IS visible: the postnet sees the sequence end at the newest frame, where the
+          windowed paths run it over the padded window, so the frames differ from theirs.  ``use_graph=True`` replays one
+          captured step for every frame of every length; ``use_graph=False`` runs the same step eagerly."""
         assert combine_strategy in {"concat", "replace"}
         assert -1. < stop_threshold < 1.
+        if incremental and combine_strategy != "concat":
+            raise ValueError("infer(incremental=True) generates frame by frame: combine_strategy must be 'concat'")
         if self.dec.mel_linear.weight.is_cuda:
             from ..edges import refresh_eval_operands
             refresh_eval_operands(self)               # cached padded / re-laid-out weights follow the parameters (graphs hold addresses)
+        if incremental:
+            return self._infer_incremental(phonemes, max_len, stop_threshold, stop_at_stop_token, check_every, use_graph)
         if use_graph and combine_strategy == "concat":
             return self._infer_graphed(phonemes, max_len, stop_threshold, stop_at_stop_token, cache_encoder, check_every)
         was_training = self.training
@@ -277,6 +287,33 @@ class ReformerTTS(nn.Module):
             for st_, f in zip(stacks, was_fused):
                 st_.fused_in_eval = f
             self.dec.reformer.collect_attention = was_collect
+            self.train(was_training)
+
+    @torch.no_grad()
+    def _infer_incremental(self, phonemes, max_len, stop_threshold, stop_at_stop_token, check_every, use_graph):
+        """"concat" generation one decoder row at a time (``model/incremental.py``).  State and graph are kept per (batch, padded
+        text length, capacity, options) and reused by later calls, as ``_infer_graphed`` keeps its windows' graphs."""
+        from .incremental import IncrementalDecoder, check_supported, generation_plan
+        b = phonemes.shape[0]
+        _, capacity = generation_plan(b, self.num_mel_coeffs, max_len)
+        tk = _pad_len(phonemes.shape[1], self.pad_base)
+        check_supported(self, b, capacity, tk)
+        self._require_gpu()
+        dev = self.dec.mel_linear.weight.device
+        was_training = self.training
+        self.eval()
+        try:
+            params = tuple(p_.data_ptr() for p_ in self.parameters())
+            key = (b, tk, capacity, bool(stop_at_stop_token), float(stop_threshold), str(dev))
+            cache = self.__dict__.setdefault("_inc_cache", {})
+            gen = cache.get(key)
+            if gen is None or gen.params != params:              # new shape, or the weights moved (other device / storage)
+                cache.clear()                                    # one generator state at a time (each pins HBM for its caches)
+                gen = cache[key] = IncrementalDecoder(self, phonemes, capacity, stop_threshold, stop_at_stop_token)
+            else:
+                gen.begin(phonemes)
+            return gen.generate(max_len, stop_at_stop_token, check_every, use_graph)
+        finally:
             self.train(was_training)
 
     @torch.no_grad()

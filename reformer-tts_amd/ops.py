@@ -280,6 +280,85 @@ def full_attn_bwd(qk, v, out, dout, lse, heads: int, causal: bool, mask=None,
     return dqk, dv
 
 
+def decode_attn_splits(bh: int, t: int) -> int:
+    """The library's pick of workgroups per (batch, head) for the single-query kernels over ``t`` cache rows / keys (-1: a size
+    the calls reject).  A host function of its arguments only."""
+    return int(_lib.load().rtts_decode_attn_splits(int(bh), int(t)))
+
+
+def _decode_rows(x: torch.Tensor, name: str, width: int) -> int:
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == width and x.stride(1) == 1):
+        raise ValueError(f"{name}: expected CUDA bfloat16 rows (B, {width}) with unit column stride, got {x.dtype} {tuple(x.shape)}")
+    return x.stride(0)
+
+
+def _decode_ws(who: str, bh: int, t: int, dh: int, splits: int, workspace, device):
+    if splits == 0:
+        splits = decode_attn_splits(bh, t)
+    nbytes = int(_lib.load().rtts_decode_attn_workspace(bh, max(splits, 1), dh)) if splits >= 0 else -1
+    if nbytes < 0:
+        raise _lib.RttsError(f"{who}: B*H={bh}, T={t}, dh={dh}, splits={splits} is outside the single-query kernels' envelope")
+    if splits == 1:
+        return splits, None
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.numel() * 4 < nbytes or workspace.device != device:
+        raise ValueError(f"{who}: workspace must be contiguous fp32 of at least {nbytes} bytes")
+    return splits, workspace
+
+
+def decode_self_attn(row: torch.Tensor, cache: torch.Tensor, pos: torch.Tensor, heads: int, cap: Optional[int] = None, splits: int = 0,
+                     out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, batch: Optional[int] = None):
+    """One new position of dense shared-QK attention against a frame cache.  row (>= B, 2*H*64) bf16 = [qk | v]; cache (B, rows,
+    2*H*64) bf16; ``pos`` a device int32 scalar p = rows already cached (read on the device).  Appends ``row`` at cache[:, p] and
+    returns o (rows of ``row``, H*64) bf16 = row p of ``full_attn_fwd`` (causal, no mask).  ``cap`` (default: the cache's rows)
+    bounds the positions; p outside [0, cap) writes nothing to the cache and gives NaN.  ``batch``: utterances when ``row`` /
+    ``out`` carry filler rows behind them."""
+    b = cache.shape[0] if batch is None else int(batch)
+    d2 = cache.shape[2]
+    ld_cache = _check_rows(cache, "cache")
+    ld_row = _decode_rows(row, "row", d2)
+    e = d2 // 2
+    dh = e // heads
+    cap = cache.shape[1] if cap is None else int(cap)
+    if cap > cache.shape[1] or row.shape[0] < b or b > cache.shape[0]:
+        raise ValueError(f"decode_self_attn: cap={cap} / batch={b} exceed the cache {tuple(cache.shape)} or the rows {tuple(row.shape)}")
+    if not (pos.is_cuda and pos.dtype == torch.int32 and pos.numel() == 1):
+        raise ValueError("pos: expected a CUDA int32 scalar")
+    if out is None:
+        out = torch.empty(row.shape[0], e, dtype=torch.bfloat16, device=row.device)
+    ld_o = _decode_rows(out, "out", e)
+    splits, workspace = _decode_ws("rtts_decode_self_attn", b * heads, cap, dh, int(splits), workspace, row.device)
+    ev = TIMING.start(f"rtts_decode_self_attn/cap{cap}")
+    _lib.call("rtts_decode_self_attn", row.data_ptr(), ld_row, cache.data_ptr(), ld_cache, cache.stride(0), pos.data_ptr(), b, heads, cap, dh,
+              out.data_ptr(), ld_o, splits, _ptr(workspace), _stream())
+    TIMING.stop(ev, 0.0)
+    return out
+
+
+def decode_cross_attn(q: torch.Tensor, kv: torch.Tensor, heads: int, kvalid: Optional[torch.Tensor] = None, splits: int = 0,
+                      out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, batch: Optional[int] = None):
+    """One query per utterance against projected encoder keys.  q (>= B, H*dh) bf16; kv (B, T_k, 2*H*dh) bf16 = [k | v]; kvalid
+    (B, T_k) 1 = attend, or None -> o (rows of ``q``, H*dh) bf16 with the arithmetic of ``rtts_xattn_fwd``."""
+    b = kv.shape[0] if batch is None else int(batch)
+    tk, e = kv.shape[1], kv.shape[2] // 2
+    ld_kv = _check_rows(kv, "kv")
+    ld_q = _decode_rows(q, "q", e)
+    dh = e // heads
+    if q.shape[0] < b or b > kv.shape[0]:
+        raise ValueError(f"decode_cross_attn: batch={b} exceeds q {tuple(q.shape)} or kv {tuple(kv.shape)}")
+    kvalid = _check_mask(kvalid, b, tk, q.device)
+    if out is None:
+        out = torch.empty(q.shape[0], e, dtype=torch.bfloat16, device=q.device)
+    ld_o = _decode_rows(out, "out", e)
+    splits, workspace = _decode_ws("rtts_decode_cross_attn", b * heads, tk, dh, int(splits), workspace, q.device)
+    ev = TIMING.start(f"rtts_decode_cross_attn/tk{tk}")
+    _lib.call("rtts_decode_cross_attn", q.data_ptr(), ld_q, kv.data_ptr(), ld_kv, _ptr(kvalid), b, heads, tk, dh, out.data_ptr(), ld_o, splits,
+              _ptr(workspace), _stream())
+    TIMING.stop(ev, 0.0)
+    return out
+
+
 def mel_spectrogram(audio: torch.Tensor, sample_offsets_host, frame_offsets_host, offsets: torch.Tensor, nseg: int,
                     dft_basis: torch.Tensor, mel_basis: torch.Tensor, n_fft: int, hop: int, power: int, clip: float,
                     out: torch.Tensor) -> torch.Tensor:

@@ -787,7 +787,7 @@ class Trainer:
         self.model.train(was_training)
 
     def _validate_inference(self, phonemes, truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder, return_outputs,
-                            dtw=False):
+                            dtw=False, incremental=False):
         from .. import ops
         if combine_strategy not in ("concat", "replace"):
             raise ValueError(f"validate_inference: combine_strategy must be 'concat' or 'replace' (got {combine_strategy!r})")
@@ -798,7 +798,7 @@ class Trainer:
             start = time.perf_counter()
             spec, stop = self.model.infer(phonemes, combine_strategy=combine_strategy, max_len=max_len, stop_threshold=stop_threshold,
                                           stop_at_stop_token=self.cfg.stop_loss_weight != 0., cache_encoder=cache_encoder,
-                                          use_graph=bool(use_graph) and combine_strategy == "concat")
+                                          use_graph=bool(use_graph) and combine_strategy == "concat", incremental=bool(incremental))
             torch.cuda.synchronize(spec.device)
             inference_time = time.perf_counter() - start
         finally:
@@ -818,7 +818,7 @@ class Trainer:
     @torch.no_grad()
     def validate_inference(self, batch, combine_strategy: str = "concat", *, max_len: int = 1024, stop_threshold: float = 0.25,
                            use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False,
-                           dtw: bool = False) -> dict:
+                           dtw: bool = False, incremental: bool = False) -> dict:
         """``LitReformerTTS.validate_inference`` (``wrappers.py:165-211``) without the plots, on a device batch in the reference's
         collate layout: ``model.infer`` on the batch's phonemes with ``stop_at_stop_token = (cfg.stop_loss_weight != 0)``
         (``:180``), then ONE ``rtts_infer_metrics`` call that scores the generated spectrogram against
@@ -841,7 +841,10 @@ class Trainer:
         at another rate (not in the reference): ``f"{strategy}_inference_mcd"``, the batch's mean MCD-DTW in dB as an f64 DEVICE
         scalar, and the per-utterance ``mcd`` (f64) and ``dtw_steps`` (int32), from ONE ``rtts_dtw_align`` call
         (``evaluation.mel_cepstral_distortion``) on the same tensors: the first min(stop_b, L) generated frames aligned to the
-        utterance's truth.  The other entries are the same bits with and without it."""
+        utterance's truth.  The other entries are the same bits with and without it.
+
+        ``incremental=True`` ("concat", an all-dense decoder) generates one decoder row per frame against a cache
+        (``ReformerTTS.infer(incremental=True)``): same dictionary; the frames differ from the windowed paths' as documented there."""
         spec = batch["spectrogram"]
         b, rows, n_mel = spec.shape
         spec = spec if spec.is_contiguous() else spec.contiguous()
@@ -849,12 +852,12 @@ class Trainer:
                         starts=torch.arange(b, dtype=torch.int64, device=spec.device) * rows + 1,
                         lengths=(batch["stop_tokens"].argmax(dim=1) + 1).to(torch.int32))
         return self._validate_inference(batch["phonemes"], truth_kw, rows - 1, combine_strategy, max_len, stop_threshold, use_graph,
-                                        cache_encoder, return_outputs, dtw)
+                                        cache_encoder, return_outputs, dtw, incremental)
 
     @torch.no_grad()
     def validate_inference_corpus(self, corpus, ids, combine_strategy: str = "concat", *, max_len: int = 1024, stop_threshold: float = 0.25,
                                   use_graph: Optional[bool] = None, cache_encoder: bool = False, return_outputs: bool = False,
-                                  dtw: bool = False) -> dict:
+                                  dtw: bool = False, incremental: bool = False) -> dict:
         """``validate_inference`` on the utterances ``ids`` (host ints) of a ``dataset.TTSCorpus``: ``rtts_tts_collate`` writes the
         padded phonemes alone, and the generated spectrogram is scored against ``corpus.mel`` in place through the corpus's
         frame offsets and the ids -- no padded truth batch is built.  Same dictionary, same bits as the batch form."""
@@ -865,7 +868,7 @@ class Trainer:
         corpus._launch(dev_ids, lm, None, 0, phonemes=phonemes)
         truth_kw = dict(truth=corpus.mel, frame_offsets=corpus.tables[0], ids=dev_ids, longest=lm)
         return self._validate_inference(phonemes[:, :lp], truth_kw, lm, combine_strategy, max_len, stop_threshold, use_graph, cache_encoder,
-                                        return_outputs, dtw)
+                                        return_outputs, dtw, incremental)
 
     @torch.no_grad()
     def validation_epoch(self, corpus, ids, batch_size: Optional[int] = None, inference: bool = True, dtw: bool = False,
