@@ -1,7 +1,8 @@
 // Audio -> log-mel spectrogram for a ragged batch of utterances, one launch (rtts_mel_spectrogram of include/rtts.h).
 //
 // A workgroup (8 waves) takes MEL_FT consecutive frames of ONE utterance:
-//   1. stages the audio span the frames share, reflect-padded per utterance, in LDS once (frame t is span[t * hop, + n_fft));
+//   1. stages the audio span the frames share, reflect-padded per utterance (stft_reflect of stft_tile.h), in LDS once (frame t
+//      is span[t * hop, + n_fft));
 //   2. short-time DFT as a GEMM on v_mfma_f32_32x32x2_f32: D[bin][frame] = sum_n basis[n][col] * span[frame * hop + n], the
 //      basis (window folded in) streamed from L2 straight into the A operand, the frames read from LDS as the B operand.  The
 //      real DFT of n_fft samples has exactly n_fft independent real outputs, so the basis is square: columns [0, n_fft/2) are the
@@ -14,7 +15,7 @@
 //   5. log(max(., clip)) and the store, 32 consecutive frames of a mel row per half wave.
 // Everything is f32, and every output element is ONE k-ordered fmaf chain over n (then over bins): the instruction is bit for bit
 // that chain, so a frame's values do not depend on its place in the tile, the utterance or the batch.
-#include "rtts_common.h"
+#include "stft_tile.h"                                            // stft_reflect
 
 #define MEL_THREADS 512
 #define MEL_WAVES 8
@@ -56,9 +57,7 @@ __global__ __launch_bounds__(MEL_THREADS) void mel_kernel(const float* __restric
     const float* x = audio + s0;
     for (int p = tid; p < S::SPAN; p += MEL_THREADS) {
         int64_t s = t0 * HOP - NFFT / 2 + p;
-        if (s < 0) s = -s;
-        if (s >= n) s = 2 * (n - 1) - s;                          // n > NFFT / 2: one reflection reaches every sample of a real frame
-        xs[p + (p >> S::LOG_HOP)] = (s >= 0 && s < n) ? x[s] : 0.f;   // samples of frames past the last one
+        xs[p + (p >> S::LOG_HOP)] = stft_reflect(n, s) ? x[s] : 0.f;
     }
     __syncthreads();
 

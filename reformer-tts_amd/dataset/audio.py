@@ -187,7 +187,39 @@ def _utterances(audio, lengths, who: str) -> Tuple[List[torch.Tensor], List[int]
     return parts, lens
 
 
-class MelTables:
+class _GpuOnly:
+    """``_device(what)`` of the modules below: the device of the buffer named by ``_anchor``, which has to be a GPU."""
+
+    _anchor: str
+
+    def _device(self, what: str) -> torch.device:
+        dev = getattr(self, self._anchor).device
+        if dev.type != "cuda":
+            raise _lib.RttsError(f"{type(self).__name__}.{what} runs on the GPU only (no CPU fallback for the HIP path)")
+        return dev
+
+
+def _host_array(offsets: Sequence[int]):
+    return (ctypes.c_int64 * len(offsets))(*offsets)
+
+
+class _OffsetTables:
+    """What the tables of a ragged call share: offset lists as host arrays (validated by the entry point) and as one device
+    tensor (read by the kernel)."""
+
+    def _upload(self, device, rows=None, **host_arrays) -> None:
+        """Attribute ``name`` = the ``c_int64`` array of each ``name=offsets``; ``device_table`` = int64 ``rows`` (default: those
+        offset lists in order), copied from pinned memory when ``device`` is a GPU, without waiting."""
+        for name, offsets in host_arrays.items():
+            setattr(self, name, _host_array(offsets))
+        host = torch.tensor(list(host_arrays.values()) if rows is None else rows, dtype=torch.int64)
+        if torch.device(device).type == "cuda":
+            host = host.pin_memory()
+        self.device_table = host.to(device, non_blocking=True)    # enqueued, not waited for
+        self._pinned = host                                       # alive until the copy has run
+
+
+class MelTables(_OffsetTables):
     """Offset tables of one ragged call: utterance lengths -> sample / frame offsets, as host arrays (validated by the entry
     point) and as one device tensor (read by the kernel).  Build it once to replay a captured call on new audio of the same
     lengths."""
@@ -198,16 +230,13 @@ class MelTables:
             raise ValueError(f"a mel call takes 1..{MEL_MAX_SEGMENTS} utterances (got {len(self.lengths)})")
         self.frames = [n // hop_length + 1 for n in self.lengths]
         self.sample_offsets, self.frame_offsets = _offsets(self.lengths), _offsets(self.frames)
-        n1 = len(self.lengths) + 1
-        self.soff_host = (ctypes.c_int64 * n1)(*self.sample_offsets)
-        self.foff_host = (ctypes.c_int64 * n1)(*self.frame_offsets)
-        host = torch.tensor([self.sample_offsets, self.frame_offsets], dtype=torch.int64).pin_memory()
-        self.device_table = host.to(device, non_blocking=True)    # enqueued, not waited for
-        self._pinned = host                                       # alive until the copy has run
+        self._upload(device, soff_host=self.sample_offsets, foff_host=self.frame_offsets)
 
 
-class _LogMel(nn.Module):
+class _LogMel(_GpuOnly, nn.Module):
     """Shared body of the two creators: bases as non-persistent device buffers, ragged launches, padding, file I/O."""
+
+    _anchor = "dft_basis"
 
     def __init__(self, sample_rate: int, n_fft: int, win_length: int, hop_length: int, n_mels: int, *, power: int, mel_scale: str,
                  norm: Optional[str], f_min: float = 0.0, f_max: float = 8000.0, clip: float = 1e-5):
@@ -225,12 +254,6 @@ class _LogMel(nn.Module):
     def log_clip(self) -> float:
         """log(clip) rounded to f32: the value of padding frames (and, to the last bit or so, of silence)."""
         return float(np.float32(math.log(float(np.float32(self.clip)))))
-
-    def _device(self, what: str) -> torch.device:
-        dev = self.dft_basis.device
-        if dev.type != "cuda":
-            raise _lib.RttsError(f"{type(self).__name__}.{what} runs on the GPU only (no CPU fallback for the HIP path)")
-        return dev
 
     def tables(self, lengths: Sequence[int]) -> MelTables:
         return MelTables(lengths, self.hop_length, self._device("tables"))
@@ -349,7 +372,7 @@ def resample_len(n_samples: int, orig: int, new: int) -> int:
     return int(m)
 
 
-class ResampleTables:
+class ResampleTables(_OffsetTables):
     """Offset tables of one ragged ``rtts_resample`` call: utterance lengths in frames -> input / output offsets, as host arrays
     and as one device tensor, like ``MelTables``.  ``out_lengths`` / ``out_offsets`` are the lengths / sample offsets of the mel
     call that takes the output."""
@@ -362,17 +385,14 @@ class ResampleTables:
             raise ValueError(f"utterances need at least one sample (got lengths {self.lengths})")
         self.out_lengths = [-((-n * new) // orig) for n in self.lengths]
         self.in_offsets, self.out_offsets = _offsets(self.lengths), _offsets(self.out_lengths)
-        n1 = len(self.lengths) + 1
-        self.ioff_host = (ctypes.c_int64 * n1)(*self.in_offsets)
-        self.ooff_host = (ctypes.c_int64 * n1)(*self.out_offsets)
-        host = torch.tensor([self.in_offsets, self.out_offsets], dtype=torch.int64).pin_memory()
-        self.device_table = host.to(device, non_blocking=True)    # enqueued, not waited for
-        self._pinned = host                                       # alive until the copy has run
+        self._upload(device, ioff_host=self.in_offsets, ooff_host=self.out_offsets)
 
 
-class Resample(nn.Module):
+class Resample(_GpuOnly, nn.Module):
     """``torchaudio.transforms.Resample(orig_freq, new_freq)`` as the reference uses it (``convert.py:137``), for ragged batches on
     the GPU: one ``rtts_resample`` launch per call.  ``orig_freq == new_freq`` returns its input unchanged, as torchaudio's does."""
+
+    _anchor = "first"
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000):
         super().__init__()
@@ -385,12 +405,6 @@ class Resample(nn.Module):
             first, coef, self.orig_red, self.new_red, self.taps = resample_tables(self.orig_freq, self.new_freq)
         self.register_buffer("first", first, persistent=False)
         self.register_buffer("coefficients", coef.contiguous(), persistent=False)
-
-    def _device(self, what: str) -> torch.device:
-        dev = self.first.device
-        if dev.type != "cuda":
-            raise _lib.RttsError(f"{type(self).__name__}.{what} runs on the GPU only (no CPU fallback for the HIP path)")
-        return dev
 
     def tables(self, lengths: Sequence[int]) -> ResampleTables:
         return ResampleTables(lengths, self.orig_red, self.new_red, self._device("tables"))

@@ -16,14 +16,13 @@ synchronisation and no allocation between them: it can be captured into a hipGra
 Utterances of fewer than three frames cannot be reflect-padded: their samples are zeros."""
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
 
 from . import _lib, ops
-from .dataset.audio import MEL_MAX_SEGMENTS, _offsets, dft_basis, idft_basis
+from .dataset.audio import MEL_MAX_SEGMENTS, _GpuOnly, _OffsetTables, _offsets, dft_basis, idft_basis
 from .squeeze_wave.modules import host_lengths, segment_offsets
 
 GL_N_FFT, GL_HOP = 1024, 256          # the one shape of rtts_gl_init / rtts_gl_step
@@ -34,7 +33,7 @@ def mel_pseudo_inverse(mel_basis: torch.Tensor) -> torch.Tensor:
     return torch.linalg.pinv(mel_basis.detach().to("cpu", torch.float64)).to(torch.float32).contiguous()
 
 
-class GriffinLimTables:
+class GriffinLimTables(_OffsetTables):
     """Offset tables of one ragged call: mel frame counts L_i -> sample offsets (256 L_i samples each), the column offsets of the
     magnitudes (L_i + 1 columns each: the frame offsets ``MelTables`` gives for lengths 256 L_i) and the first frames of a packed
     (n_mels, sum L) mel, as host arrays and as one device tensor.  Build it once to replay a captured call on a new mel of the same
@@ -48,23 +47,19 @@ class GriffinLimTables:
         self.sample_offsets = _offsets(self.lengths)
         self.col_offsets = _offsets([n + 1 for n in self.frames])
         self.mel_offsets = _offsets(self.frames)
-        n1 = len(self.frames) + 1
-        self.soff_host = (ctypes.c_int64 * n1)(*self.sample_offsets)
-        self.coff_host = (ctypes.c_int64 * n1)(*self.col_offsets)
-        host = torch.tensor([self.sample_offsets, self.col_offsets, self.mel_offsets, [0] * n1], dtype=torch.int64)
-        if torch.device(device).type == "cuda":
-            host = host.pin_memory()
-        self.device_table = host.to(device, non_blocking=True)    # enqueued, not waited for
-        self._pinned = host                                       # alive until the copy has run
+        self._upload(device, [self.sample_offsets, self.col_offsets, self.mel_offsets, [0] * len(self.col_offsets)],
+                     soff_host=self.sample_offsets, coff_host=self.col_offsets)
 
 
-class GriffinLim(nn.Module):
+class GriffinLim(_GpuOnly, nn.Module):
     """``GriffinLim(creator)``: ``creator`` is the ``dataset.audio`` spectrogram module whose log-mels are to be inverted
     (``Tacotron2Spectrogram``: magnitude mels, power 1; ``MelSpectrogram``: power mels, power 2); it gives the mel matrix, the power,
     n_fft and the hop.  The object goes where a vocoder goes: ``synthesis.vocode_trimmed(gl, spectrogram, stop)``,
     ``synthesis.synthesize(tts, gl, phonemes)``.
 
     Supported: n_fft = win_length = 1024, hop_length = 256 (the one shape of the kernels)."""
+
+    _anchor = "pinv"
 
     def __init__(self, creator, n_iter: int = 32, momentum: float = 0.99, phase: str = "hash", seed: int = 0):
         super().__init__()
@@ -86,12 +81,6 @@ class GriffinLim(nn.Module):
         self.register_buffer("pinv", mel_pseudo_inverse(creator.mel_basis).to(device), persistent=False)
         self.register_buffer("dft_basis", dft_basis(GL_N_FFT, GL_N_FFT).to(device), persistent=False)
         self.register_buffer("idft_basis", idft_basis(GL_N_FFT, GL_N_FFT).to(device), persistent=False)
-
-    def _device(self, what: str) -> torch.device:
-        dev = self.pinv.device
-        if dev.type != "cuda":
-            raise _lib.RttsError(f"{type(self).__name__}.{what} runs on the GPU only (no CPU fallback for the HIP path)")
-        return dev
 
     def tables(self, frames: Sequence[int]) -> GriffinLimTables:
         return GriffinLimTables(frames, self._device("tables"), self.hop_length)

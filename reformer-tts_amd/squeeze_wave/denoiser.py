@@ -12,7 +12,6 @@ A ragged batch is one launch of ``rtts_denoise`` (csrc/denoise.hip) on packed au
 ``capture_ragged`` return and ``dataset.audio`` reads."""
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -20,7 +19,7 @@ import torch
 from torch import nn
 
 from .. import _lib, ops
-from ..dataset.audio import MEL_MAX_SEGMENTS, _offsets, _utterances, dft_basis, idft_basis
+from ..dataset.audio import MEL_MAX_SEGMENTS, _GpuOnly, _OffsetTables, _host_array, _offsets, _utterances, dft_basis, idft_basis
 
 DENOISE_N_FFT, DENOISE_HOP = 1024, 256        # the one shape of rtts_denoise
 
@@ -40,7 +39,7 @@ def first_frame_magnitudes(audio: torch.Tensor, n_fft: int = DENOISE_N_FFT, win_
     return mag
 
 
-class DenoiseTables:
+class DenoiseTables(_OffsetTables):
     """Offset tables of one ragged call: utterance lengths -> sample offsets, as a host array and a device tensor, and the plan
     of the call: maximal runs of consecutive utterances longer than n_fft / 2 (one launch each: ``runs`` of (first, count)) and
     the sample ranges of the shorter ones between them (``copies``), which pass through.  Build it once to replay a captured
@@ -65,15 +64,11 @@ class DenoiseTables:
                 self.copies.append((self.sample_offsets[i], self.sample_offsets[j]))
             i = j
         # a run's host table is its own array: the entry point reads count + 1 values from its start
-        self.soff_host = [(ctypes.c_int64 * (cnt + 1))(*self.sample_offsets[first:first + cnt + 1]) for first, cnt in self.runs]
-        host = torch.tensor(self.sample_offsets, dtype=torch.int64)
-        if torch.device(device).type == "cuda":
-            host = host.pin_memory()
-        self.device_table = host.to(device, non_blocking=True)    # enqueued, not waited for
-        self._pinned = host                                       # alive until the copy has run
+        self.soff_host = [_host_array(self.sample_offsets[first:first + cnt + 1]) for first, cnt in self.runs]
+        self._upload(device, self.sample_offsets)
 
 
-class Denoiser(nn.Module):
+class Denoiser(_GpuOnly, nn.Module):
     """``Denoiser(vocoder)``: the bias spectrum of ``vocoder`` -- frame 0 of the STFT magnitudes of what it emits for a zero mel of
     ``n_bias_frames`` frames at ``sigma = 0`` -- as the f32 buffer ``bias_spec`` (n_fft/2 + 1,), computed once in float64.  The
     reference's ``infer`` scales every latent draw by sigma except the first (``modules.py:340-368``), so the zero latent that
@@ -81,6 +76,8 @@ class Denoiser(nn.Module):
     (``Denoiser.bias_audio``).  ``Denoiser(bias_spec=...)`` takes a spectrum as given (tests, saved denoisers).
 
     Supported: n_fft = win_length = 1024, hop_length = 256 (the one shape of ``rtts_denoise``)."""
+
+    _anchor = "bias_spec"
 
     def __init__(self, vocoder=None, *, bias_spec: Optional[torch.Tensor] = None, n_fft: int = 1024, hop_length: int = 256,
                  win_length: int = 1024, n_bias_frames: int = 88):
@@ -109,12 +106,6 @@ class Denoiser(nn.Module):
         mel = torch.zeros(1, vocoder._n_mel(), int(n_bias_frames), device=dev)
         noise = [torch.zeros(s, device=dev) for s in vocoder.noise_shapes(1, int(n_bias_frames))]
         return vocoder.infer(mel, sigma=0.0, noise=noise).reshape(-1)
-
-    def _device(self, what: str) -> torch.device:
-        dev = self.bias_spec.device
-        if dev.type != "cuda":
-            raise _lib.RttsError(f"{type(self).__name__}.{what} runs on the GPU only (no CPU fallback for the HIP path)")
-        return dev
 
     def tables(self, lengths: Sequence[int]) -> DenoiseTables:
         return DenoiseTables(lengths, self.n_fft, self._device("tables"))
