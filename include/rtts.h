@@ -973,6 +973,55 @@ int rtts_gl_step(const float* cur, const float* prev, float beta, const float* m
                  const int64_t* col_offsets, const int64_t* sample_offsets_host, const int64_t* sample_offsets, int nseg,
                  const float* dft_basis, const float* idft_basis, int n_fft, int hop, float* out, void* stream);
 
+/* ---- F0 tracking and pitch-error counts (evaluation; not in the reference) ---------------------
+ * rtts_pitch_yin: the F0 contour of a RAGGED batch of utterances on the frame grid of rtts_mel_spectrogram, one launch: YIN
+ * (de Cheveigne and Kawahara 2002, steps 2 to 5) with the integration window W = 1024 and lags 0 .. RTTS_PITCH_MAX_LAG = 512.
+ * One utterance x[0..N), zero outside, frame t, s_t = t hop - (W + 512) / 2:
+ *     d_t(tau)  = sum_{j=0..W-1} (x[s_t + j] - x[s_t + j + tau])^2                           tau = 0 .. 512
+ *     d'_t(0)   = 1,   d'_t(tau) = d_t(tau) tau / sum_{j=1..tau} d_t(j),  1 where that sum is 0
+ *     pick      the smallest tau in [tau_min, tau_max] with d'(tau) < threshold; then, while tau + 1 <= tau_max and
+ *               d'(tau + 1) < d'(tau), tau + 1.  None: the frame is unvoiced, f0 = 0, aperiodicity = min d' over [tau_min, tau_max]
+ *     voiced    a, b, c = d'(tau - 1), d'(tau), d'(tau + 1);  off = 0.5 (a - c) / (a - 2 b + c) if a > b and c >= b, else 0;
+ *               f0 = sample_rate / (tau + off),  aperiodicity = b
+ * All arithmetic is f32, and d is summed in the direct squared-difference form (never as energies minus twice a correlation,
+ * which cancels exactly at the period): with block k = samples [k hop - 768, + hop), P_k(tau) is one fmaf chain over the block's
+ * j in ascending order, P = fmaf(e, e, P) with e the rounded difference; d_t = P_t + P_{t+1} + ... + P_{t + W / hop - 1}, left to
+ * right; the running sum of lag tau = 8 l + i (i = 1..8) is (the totals of the groups of eight lags before l, combined by a
+ * 64-wide Hillis-Steele scan, distances 1, 2, .. 32) + (d(8 l + 1) + ... + d(tau), left to right).  The order depends on hop alone:
+ * an utterance's outputs are bitwise the same alone and anywhere in a batch, and from call to call.  No atomics; the call can be
+ * captured in a hipGraph.
+ *   audio           f32, the utterances end to end: utterance s is samples [sample_offsets[s], sample_offsets[s+1]), N_s >= 1 of
+ *                   them (shorter than the window is fine)
+ *   sample_offsets  i64 (nseg + 1), frame_offsets i64 (nseg + 1): DEVICE tables the kernel reads, and the same values in
+ *                   sample_offsets_host / frame_offsets_host, which the entry point validates and sizes the grid by (1 <= nseg <= 65535).
+ *                   The two copies MUST hold the same values, as for rtts_mel_spectrogram
+ *   f0, aperiodicity   f32, one value per frame: utterance s owns [frame_offsets[s], + T_s), T_s = rtts_mel_frames(N_s, hop);
+ *                   frame_offsets[s+1] - frame_offsets[s] >= T_s, slots past T_s are not touched
+ *   cmnd            nullable; f32 (frame_offsets[nseg], RTTS_PITCH_MAX_LAG + 1) row-major: row frame_offsets[s] + t = d'_t(0 .. 512)
+ *   a frame that touches a non-finite sample (one in [s_t, s_t + W + 512)) gives NaN in f0 and aperiodicity; its cmnd row holds
+ *   what the arithmetic gave
+ * A workgroup computes RTTS_PITCH_TILE_FRAMES consecutive frames of one utterance from one LDS image of the samples they share,
+ * and every hop block's partial sums once for the frames that overlap it.
+ * Supported: hop in {128, 256, 512}, 2 <= tau_min <= tau_max <= 511, 0 < threshold < 1, sample_rate > 0.  Anything else, a null
+ * pointer (but cmnd), an offset that decreases, an empty utterance or a frame slot smaller than T_s is rejected before any launch.
+ *
+ * rtts_f0_compare: contour a against the reference contour b, one launch, nothing read on the host.  Each contour is packed f32
+ * with its own DEVICE i64 (nseg + 1) frame-offset table; utterance s is compared over its first n_s = min(T_a, T_b) frames, T =
+ * the difference of its offsets.  A frame is voiced where its value is > 0.  table is f64 (nseg + 1, 5) row-major, row s:
+ *     [0] n_s      [1] frames voiced in both      [2] sum over those of (1200 log2(fa / fb))^2, in f64
+ *     [3] those with |fa / fb - 1| > gross          [4] frames voiced in exactly one contour
+ * and row nseg = the column sums over s in ascending order.  Fixed order, no atomics: lane l of a wave adds frames l, l + 64, ..
+ * in ascending order, the 64 partial sums are folded by halving distances.  A NaN among the compared frames of either contour
+ * makes the utterance's row and the last row NaN (the rule of rtts_dtw_align).
+ * Supported: nseg in 1..65535, 0 < gross < 1; anything else or a null pointer is rejected before the launch. */
+#define RTTS_PITCH_MAX_LAG 512
+#define RTTS_PITCH_TILE_FRAMES 16
+int rtts_pitch_yin(const float* audio, const int64_t* sample_offsets_host, const int64_t* frame_offsets_host,
+                   const int64_t* sample_offsets, const int64_t* frame_offsets, int nseg, int hop, int tau_min, int tau_max,
+                   float threshold, float sample_rate, float* f0, float* aperiodicity, float* cmnd, void* stream);
+int rtts_f0_compare(const float* f0_a, const int64_t* frame_offsets_a, const float* f0_b, const int64_t* frame_offsets_b, int nseg,
+                    double gross, double* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

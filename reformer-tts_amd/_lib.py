@@ -177,6 +177,8 @@ SIGNATURES = {
     "rtts_gl_magnitudes": [_vp, _i64, _i64, _i64, _vp, C.POINTER(_i64), _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
     "rtts_gl_init": [_vp, _i64, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _i32, _u32, _i32, _i32, _vp, _vp],
     "rtts_gl_step": [_vp, _vp, _f32, _vp, _i64, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
+    "rtts_pitch_yin": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp],
+    "rtts_f0_compare": [_vp, _vp, _vp, _vp, _i32, C.c_double, _vp, _vp],
 }
 
 _lib = None

@@ -7,7 +7,11 @@ the frame distance along the alignment path (MCD-DTW when the frames are mel cep
 (``ops.dtw_align``) on the tensors where they lie: nothing is read back.  The metric is not in the reference.
 
 The kernel aligns linearly projected frames and knows nothing about cepstra; ``cepstral_basis`` is the projection that makes its
-Euclidean frame distance the usual mel-cepstral distortion in dB."""
+Euclidean frame distance the usual mel-cepstral distortion in dB.
+
+A log-mel distance is nearly blind to pitch, so the second half of the module tracks F0 (``PitchTracker``: YIN on the frame grid of
+the mel creators, one ragged ``rtts_pitch_yin`` launch) and compares two contours (``f0_errors``, ``audio_f0_errors``: F0 RMSE in
+cents, gross pitch error, voicing decision error and F0 frame error from one ``rtts_f0_compare`` launch)."""
 from __future__ import annotations
 
 import math
@@ -86,3 +90,124 @@ def audio_mcd(vocoder_waves: Sequence[torch.Tensor], spectrogram: torch.Tensor, 
                                         starts=torch.tensor([int(f) for f in foff[:-1]], dtype=torch.int64).to(dev),
                                         lengths=torch.tensor(heard, dtype=torch.int32).to(dev))
     return mcd
+
+
+class PitchTracker(torch.nn.Module):
+    """F0 contours on the frame grid of the mel creators (frame t is centred on sample t * hop_length, T = N // hop_length + 1
+    frames), by YIN with a 1024-sample integration window: one ragged ``rtts_pitch_yin`` launch (``ops.pitch_yin``, csrc/pitch.hip)
+    for any number of utterances.  A frame whose normalised difference function d' never falls below ``threshold`` between the
+    periods of ``f_max`` and ``f_min`` is unvoiced and has f0 = 0; ``aperiodicity`` is d' at the chosen period (its minimum over
+    the range in an unvoiced frame).  The lags run to 512 samples, so ``sample_rate / f_min`` must stay below 512."""
+
+    def __init__(self, sample_rate: int = 22050, hop_length: int = 256, f_min: float = 50.0, f_max: float = 500.0, threshold: float = 0.1):
+        super().__init__()
+        if not sample_rate > 0:
+            raise ValueError(f"PitchTracker: sample_rate must be positive (got {sample_rate})")
+        if hop_length not in (128, 256, 512):
+            raise ValueError(f"PitchTracker: hop_length must be 128, 256 or 512, the hops of the mel creators (got {hop_length})")
+        if not 0.0 < f_min <= f_max:
+            raise ValueError(f"PitchTracker: f_min and f_max must satisfy 0 < f_min <= f_max (got {f_min}, {f_max})")
+        if not 0.0 < threshold < 1.0:
+            raise ValueError(f"PitchTracker: threshold must lie strictly between 0 and 1 (got {threshold})")
+        self.sample_rate, self.hop_length, self.f_min, self.f_max = sample_rate, int(hop_length), float(f_min), float(f_max)
+        self.threshold = float(threshold)
+        self.tau_min, self.tau_max = math.ceil(sample_rate / f_max), math.floor(sample_rate / f_min)
+        if self.tau_min < 2:
+            raise ValueError(f"PitchTracker: f_max = {f_max} Hz is a period of tau_min = {self.tau_min} samples at {sample_rate} Hz; "
+                             "tau_min must be at least 2 (lower f_max)")
+        if self.tau_max > 511:
+            raise ValueError(f"PitchTracker: f_min = {f_min} Hz is a period of tau_max = {self.tau_max} samples at {sample_rate} Hz; "
+                             "tau_max must be at most 511 (raise f_min or resample)")
+        if self.tau_min > self.tau_max:
+            raise ValueError(f"PitchTracker: no whole period lies between f_max = {f_max} Hz and f_min = {f_min} Hz at {sample_rate} Hz "
+                             f"(tau_min = {self.tau_min} > tau_max = {self.tau_max})")
+
+    def tables(self, lengths: Sequence[int], device=None):
+        """The offset tables of one ragged call (``dataset.audio.MelTables``: the same frame grid as the log-mels)."""
+        from .dataset.audio import MelTables
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return MelTables(lengths, self.hop_length, device)
+
+    @torch.no_grad()
+    def forward_packed(self, audio: torch.Tensor, lengths: Optional[Sequence[int]] = None, *, tables=None, return_cmnd: bool = False):
+        """``audio``: the utterances end to end, a flat f32 device tensor; ``lengths``: their sample counts (host ints), or ``tables``
+        from an earlier ``self.tables(lengths)`` -> (f0 (total frames,) f32 in Hz, 0 = unvoiced; aperiodicity (total frames,) f32;
+        frame offsets: utterance i owns [offsets[i], offsets[i+1])), and with ``return_cmnd`` also d' (total frames, 513).  One
+        launch, stream-ordered."""
+        from . import _lib, ops
+        if not (torch.is_tensor(audio) and audio.is_cuda):
+            raise _lib.RttsError("PitchTracker.forward_packed runs on the GPU only (no CPU fallback for the HIP path)")
+        if tables is None:
+            if lengths is None:
+                raise ValueError("forward_packed needs lengths or tables")
+            tables = self.tables(lengths, audio.device)
+        total = tables.frame_offsets[-1]
+        out = torch.empty(2, total, dtype=torch.float32, device=audio.device)
+        cmnd = torch.empty(total, ops.PITCH_MAX_LAG + 1, dtype=torch.float32, device=audio.device) if return_cmnd else None
+        ops.pitch_yin(audio, tables.soff_host, tables.foff_host, tables.device_table, len(tables.lengths), self.hop_length, self.tau_min,
+                      self.tau_max, self.threshold, float(self.sample_rate), out[0], out[1], cmnd)
+        res = (out[0], out[1], list(tables.frame_offsets))
+        return res + (cmnd,) if return_cmnd else res
+
+    @torch.no_grad()
+    def forward(self, audio, lengths=None):
+        """``audio``: a list of 1-D device tensors, or a padded (B, N) device tensor with ``lengths`` (host ints or a tensor)
+        -> (f0 (B, T_max) f32 with 0 past an utterance's frames, frames (B,) int64 on the device)."""
+        from .dataset.audio import _utterances
+        parts, lens = _utterances(audio, lengths, type(self).__name__)
+        dev = parts[0].device
+        f0, _, foff = self.forward_packed(torch.cat([p.to(dev, torch.float32) for p in parts]), lens)
+        frames = [foff[i + 1] - foff[i] for i in range(len(lens))]
+        padded = torch.zeros(len(lens), max(frames), dtype=torch.float32, device=dev)
+        for i, t in enumerate(frames):
+            padded[i, :t] = f0[foff[i]:foff[i + 1]]
+        return padded, torch.tensor(frames, dtype=torch.int64).to(dev, non_blocking=True)
+
+
+def f0_errors_from_counts(table: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The pitch-error figures of a (B + 1, 5) f64 count table as ``rtts_f0_compare`` writes it (rows [n, both, sum of squared
+    cents, gross, voicing]; the last row the totals) -> ``rmse_cents`` = sqrt(sum / both), ``gpe`` = gross / both, ``vde`` =
+    voicing / n, ``ffe`` = (gross + voicing) / n, each (B,) f64 where the table lives, and ``totals`` (4,) = the same four figures
+    of the last row.  A division by zero (no frame voiced in both contours, no frame at all) gives NaN, never infinity."""
+    if not (torch.is_tensor(table) and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == 5 and table.shape[0] >= 2):
+        raise ValueError("f0_errors_from_counts: expected a float64 (B + 1, 5) table")
+    nan = torch.full_like(table[:, 0], float("nan"))
+    n, both, cents2, gross, voicing = table.unbind(1)
+
+    def ratio(num, den):
+        return torch.where(den == 0, nan, num / den)
+
+    figures = torch.stack([torch.sqrt(ratio(cents2, both)), ratio(gross, both), ratio(voicing, n), ratio(gross + voicing, n)])
+    return {"rmse_cents": figures[0, :-1], "gpe": figures[1, :-1], "vde": figures[2, :-1], "ffe": figures[3, :-1],
+            "totals": figures[:, -1], "counts": table}
+
+
+def f0_errors(f0_a: torch.Tensor, offsets_a, f0_b: torch.Tensor, offsets_b, gross: float = 0.2) -> Dict[str, torch.Tensor]:
+    """The usual pitch errors of contour ``f0_a`` against the reference contour ``f0_b``, both packed as
+    ``PitchTracker.forward_packed`` returns them, each with its frame offsets (a host list, or an int64 tensor on the device):
+    F0 RMSE in cents and gross pitch error (more than ``gross`` off, relative) over the frames voiced in both, voicing decision
+    error and F0 frame error over all compared frames -- utterance by utterance over the first min(T_a, T_b) frames, frame t
+    against frame t.  One ``rtts_f0_compare`` launch; see ``f0_errors_from_counts`` for what comes back (device f64 tensors)."""
+    from . import ops
+    dev = f0_a.device
+    tabs = [o if torch.is_tensor(o) else torch.tensor([int(v) for v in o], dtype=torch.int64).to(dev) for o in (offsets_a, offsets_b)]
+    return f0_errors_from_counts(ops.f0_compare(f0_a, tabs[0], f0_b, tabs[1], gross))
+
+
+@torch.no_grad()
+def audio_f0_errors(waves_a: Sequence[torch.Tensor], waves_b: Sequence[torch.Tensor], tracker: PitchTracker,
+                    gross: float = 0.2) -> Dict[str, torch.Tensor]:
+    """``f0_errors`` of two batches of waveforms, ``waves_a`` against the references ``waves_b``: Griffin-Lim against SqueezeWave
+    from the same mel, or vocoded against recorded audio.  The sibling of ``audio_mcd``: one ragged YIN launch per side and one
+    compare launch.  It is frame-synchronous by design: frame t of one side is compared with frame t of the other, over the
+    shorter of the two.  Scoring a generated utterance against a truth of other timing needs the DTW path, which
+    ``rtts_dtw_align`` does not export -- out of scope here."""
+    if len(waves_a) != len(waves_b) or not len(waves_a):
+        raise ValueError(f"audio_f0_errors: {len(waves_a)} waveforms against {len(waves_b)}")
+    sides = []
+    for waves in (waves_a, waves_b):
+        flat = [w.reshape(-1).to(torch.float32) for w in waves]
+        f0, _, foff = tracker.forward_packed(torch.cat(flat), [int(w.numel()) for w in flat])
+        sides += [f0, foff]
+    return f0_errors(*sides, gross=gross)

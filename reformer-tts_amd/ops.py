@@ -800,3 +800,67 @@ def dtw_align(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: torch.
               work.data_ptr(), work.numel(), int(_phases), cost.data_ptr(), steps.data_ptr(), totals.data_ptr(), _stream())
     TIMING.stop(ev, 0.0)
     return cost, steps, totals
+
+
+PITCH_MAX_LAG = 512    # RTTS_PITCH_MAX_LAG of include/rtts.h
+PITCH_WINDOW = 1024    # the integration window of rtts_pitch_yin
+
+
+def pitch_yin(audio: torch.Tensor, sample_offsets_host, frame_offsets_host, offsets: torch.Tensor, nseg: int, hop: int, tau_min: int,
+              tau_max: int, threshold: float, sample_rate: float, f0: torch.Tensor, aperiodicity: torch.Tensor,
+              cmnd: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """audio: the utterances end to end (flat f32); offsets: (2, nseg + 1) i64 device table [sample offsets; frame offsets] and the
+    same values as two host ``ctypes.c_int64`` arrays (what ``dataset.audio.MelTables`` holds) -> f0 and aperiodicity, flat f32
+    of >= frame_offsets[nseg] values, one per frame of the mel grid, and, when given, cmnd (>= frame_offsets[nseg],
+    PITCH_MAX_LAG + 1) f32 = every frame's d': one ``rtts_pitch_yin`` launch on the current stream."""
+    for name, t in (("audio", audio), ("f0", f0), ("aperiodicity", aperiodicity), ("cmnd", cmnd)):
+        if t is None and name == "cmnd":
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise _lib.RttsError(f"pitch_yin runs on the GPU only: {name} must be a CUDA float32 tensor "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+    if not (offsets.is_cuda and offsets.dtype == torch.int64 and offsets.shape == (2, nseg + 1) and offsets.is_contiguous()):
+        raise ValueError(f"offsets: expected a contiguous CUDA int64 (2, {nseg + 1}) table")
+    if not (audio.dim() == 1 and audio.is_contiguous() and f0.dim() == 1 and f0.is_contiguous() and aperiodicity.dim() == 1
+            and aperiodicity.is_contiguous()):
+        raise ValueError("pitch_yin: audio, f0 and aperiodicity must be flat")
+    frames = frame_offsets_host[nseg]
+    if audio.numel() < sample_offsets_host[nseg] or f0.numel() < frames or aperiodicity.numel() < frames:
+        raise ValueError(f"pitch_yin: {audio.numel()} samples / {f0.numel()} and {aperiodicity.numel()} output frames for offsets ending at "
+                         f"{sample_offsets_host[nseg]} / {frames}")
+    if cmnd is not None and not (cmnd.dim() == 2 and cmnd.is_contiguous() and cmnd.shape[1] == PITCH_MAX_LAG + 1 and cmnd.shape[0] >= frames):
+        raise ValueError(f"pitch_yin: cmnd must be contiguous of shape (>= {frames}, {PITCH_MAX_LAG + 1}), got {tuple(cmnd.shape)}")
+    ev = TIMING.start(f"rtts_pitch_yin/hop{hop}")
+    _lib.call("rtts_pitch_yin", audio.data_ptr(), sample_offsets_host, frame_offsets_host, offsets[0].data_ptr(), offsets[1].data_ptr(), nseg,
+              int(hop), int(tau_min), int(tau_max), float(threshold), float(sample_rate), f0.data_ptr(), aperiodicity.data_ptr(), _ptr(cmnd),
+              _stream())
+    TIMING.stop(ev, 3.0 * frames * PITCH_WINDOW * PITCH_MAX_LAG)
+    return f0, aperiodicity
+
+
+def f0_compare(f0_a: torch.Tensor, offsets_a: torch.Tensor, f0_b: torch.Tensor, offsets_b: torch.Tensor, gross: float = 0.2,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Two packed F0 contours, ``f0_a`` against the reference ``f0_b``: flat f32, each with its own int64 (B + 1,) frame-offset
+    table ON THE DEVICE -> f64 (B + 1, 5): per utterance [frames compared, voiced in both, sum of squared cents over those, gross
+    errors among those, voicing differences], the last row their sums.  A NaN frame makes its row and the last row NaN.  One
+    ``rtts_f0_compare`` launch on the current stream, nothing read back: capturable."""
+    named = (("f0_a", f0_a, torch.float32), ("offsets_a", offsets_a, torch.int64), ("f0_b", f0_b, torch.float32),
+             ("offsets_b", offsets_b, torch.int64))
+    for name, t, dt in named:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt):
+            raise _lib.RttsError(f"f0_compare runs on the GPU only: {name} must be a CUDA {dt} tensor "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+        if not (t.dim() == 1 and t.is_contiguous() and t.device == f0_a.device):
+            raise ValueError(f"f0_compare: {name} must be flat, contiguous and on {f0_a.device}")
+    nseg = offsets_a.numel() - 1
+    if nseg < 1 or offsets_b.numel() != nseg + 1:
+        raise ValueError(f"f0_compare: the offset tables hold {offsets_a.numel()} and {offsets_b.numel()} entries; both must hold B + 1, B >= 1")
+    if out is None:
+        out = torch.empty(nseg + 1, 5, dtype=torch.float64, device=f0_a.device)
+    elif not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (nseg + 1, 5) and out.is_contiguous()):
+        raise ValueError(f"f0_compare: out must be a contiguous CUDA float64 ({nseg + 1}, 5) tensor")
+    ev = TIMING.start("rtts_f0_compare")
+    _lib.call("rtts_f0_compare", f0_a.data_ptr(), offsets_a.data_ptr(), f0_b.data_ptr(), offsets_b.data_ptr(), nseg, float(gross), out.data_ptr(),
+              _stream())
+    TIMING.stop(ev, 0.0)
+    return out
