@@ -1022,6 +1022,56 @@ int rtts_pitch_yin(const float* audio, const int64_t* sample_offsets_host, const
 int rtts_f0_compare(const float* f0_a, const int64_t* frame_offsets_a, const float* f0_b, const int64_t* frame_offsets_b, int nseg,
                     double gross, double* table, void* stream);
 
+/* ---- Alignment scores and phoneme durations from attention matrices (evaluation; not in the reference) ----
+ * Whether the decoder's encoder-decoder attention has learnt a text-to-speech alignment, as numbers instead of the reference's
+ * pictures (plot_attention_matrix, wrappers.py:137-150), and the phoneme durations such an alignment implies.  csrc/align.hip.
+ * Both entries read the same operand where it lies and nothing on the host; no floating-point atomics; both can be captured in a
+ * hipGraph; a second call gives the same bits, and a slot's outputs do not depend on the batch around it.
+ *   a               f32, n_mat matrices of (B, Tq, Tk): element (m, b, t, k) at a[m sm + b sb + t st + k], strides in elements.  The
+ *                   base must be 16-byte aligned and sm, sb, st multiples of 4, st >= Tk, and no two slots may overlap (a slot
+ *                   spans Tq st elements: sb >= Tq st and sm >= (B - 1) sb + Tq st, or the two the other way round): the
+ *                   per-layer outputs of rtts_xattn_probs_mean, stacked or written into one (L, B, T, Tk) buffer
+ *   n_frames, n_keys  i32 (B,) ON THE DEVICE: slot b uses frames t < T = n_frames[b] and keys k < K = n_keys[b] of every matrix;
+ *                   nothing at or past them is read
+ *   a slot is UNSCORABLE when T is outside 1..Tq, K outside 1..Tk, or a value inside its region is not finite: its f64 outputs
+ *   are NaN and its integer outputs 0 (arg-max and path -1), and it makes the totals row NaN; it is never read out of range, and
+ *   every other slot keeps its bits
+ * Supported: 1 <= n_mat <= 64, 1 <= B <= 65535, 1 <= Tq <= 4096, 1 <= Tk <= 2048, no multiple-of requirement.  Anything else, a
+ * null pointer (but path), an unaligned base or stride, a short workspace, sigma <= 0 or floor <= 0 is rejected before any launch
+ * by the argument's name.
+ *
+ * rtts_align_stats: the arg-max track and the sums behind the usual alignment scores.
+ *   argmax      i32 (n_mat, B, Tq): the key with the largest a[t, .] over k < K, the lowest index on a tie; -1 for t >= T
+ *   dur_argmax  i32 (n_mat, B, Tk): the number of frames whose arg-max is k
+ *   table       f64 (n_mat, B + 1, 8), row b of matrix m:
+ *                   [0] T   [1] K   [2] sum_t sum_k a   [3] sum_t max_k a   [4] sum_t (-sum_k a ln a over a > 0)
+ *                   [5] sum_t sum_k a w(t, k),  w = 1 - exp(-(k / K - t / T)^2 / (2 sigma^2)), in f64 from the f32 values
+ *                   [6] #{t >= 1 : argmax[t] >= argmax[t-1]}   [7] #{k : dur_argmax[k] > 0}
+ *               and row B = the column sums over the slots in ascending order.  [3] / T is FastSpeech's focus rate, [5] / T
+ *               the guided-attention weight of Tachibana et al. ("mass off the diagonal")
+ *   A frame's sums have one fixed order that depends on K alone (lane l of a wave adds columns 4 l .. 4 l + 3, 4 l + 256 .., ascending;
+ *   the 64 lanes are folded by halving distances), frames are added in frame order within tiles of 16 and the tiles in order.
+ *   workspace   rtts_align_stats_workspace(n_mat, B, Tq, Tk) bytes (-1 outside the envelope), overwritten
+ *
+ * rtts_align_mas: monotonic alignment search (Glow-TTS): the path k(t) with k(0) = 0, k(T-1) = K-1 and steps of 0 or 1 that
+ * maximises sum_t log a[t, k(t)].  With c[t, k] = log(max((double)a[t, k], floor)) and every Q in f64:
+ *   Q[0, 0] = c[0, 0],  Q[0, k > 0] = -inf,  Q[t, k] = c[t, k] + max(Q[t-1, k], Q[t-1, k-1]), on an exact tie the path STAYS (k);
+ *   back-tracked from (T-1, K-1).
+ *   durations   i32 (n_mat, B, Tk): #{t : k(t) = k}; >= 1 for k < K, summing to T, 0 for k >= K
+ *   path        nullable; i32 (n_mat, B, Tq): k(t), -1 for t >= T
+ *   scores      f64 (n_mat, B + 1, 2): [Q[T-1, K-1], sum_t a[t, k(t)] added in frame order]; row B = the sums over the slots
+ *   T < K also makes a slot unscorable here (no monotonic path visits every key); rtts_align_stats still scores it.
+ *   workspace   rtts_align_mas_workspace(n_mat, B, Tq, Tk) bytes (-1 outside the envelope): the one-bit back-pointers when
+ *               (Tq, Tk) bits do not fit in LDS */
+int64_t rtts_align_stats_workspace(int n_mat, int B, int Tq, int Tk);
+int rtts_align_stats(const float* a, int64_t sm, int64_t sb, int64_t st, int n_mat, int B, int Tq, int Tk, const int32_t* n_frames,
+                     const int32_t* n_keys, double sigma, int32_t* argmax, int32_t* dur_argmax, double* table, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int64_t rtts_align_mas_workspace(int n_mat, int B, int Tq, int Tk);
+int rtts_align_mas(const float* a, int64_t sm, int64_t sb, int64_t st, int n_mat, int B, int Tq, int Tk, const int32_t* n_frames,
+                   const int32_t* n_keys, double floor, int32_t* durations, int32_t* path, double* scores, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,10 @@ SIGNATURES = {
     "rtts_gl_step": [_vp, _vp, _f32, _vp, _i64, C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp],
     "rtts_pitch_yin": [_vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp],
     "rtts_f0_compare": [_vp, _vp, _vp, _vp, _i32, C.c_double, _vp, _vp],
+    "rtts_align_stats_workspace": [_i32, _i32, _i32, _i32],
+    "rtts_align_stats": [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp],
+    "rtts_align_mas_workspace": [_i32, _i32, _i32, _i32],
+    "rtts_align_mas": [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 
 _lib = None
@@ -238,6 +242,8 @@ def load() -> C.CDLL:
         lib.rtts_full_attn_bwd_workspace.restype = C.c_int64
         lib.rtts_dtw_workspace_bytes.restype = C.c_int64
         lib.rtts_decode_attn_workspace.restype = C.c_int64
+        lib.rtts_align_stats_workspace.restype = C.c_int64
+        lib.rtts_align_mas_workspace.restype = C.c_int64
         _lib = lib
         # A/B scripts may name a run length in the environment: read ONCE, here -- the library's launch path reads none
         fw, bw = os.environ.get("RTTS_LSH_FWD_WALK"), os.environ.get("RTTS_LSH_BWD_WALK")

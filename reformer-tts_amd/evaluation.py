@@ -211,3 +211,49 @@ def audio_f0_errors(waves_a: Sequence[torch.Tensor], waves_b: Sequence[torch.Ten
         f0, _, foff = tracker.forward_packed(torch.cat(flat), [int(w.numel()) for w in flat])
         sides += [f0, foff]
     return f0_errors(*sides, gross=gross)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Alignment scores and phoneme durations from the decoder's encoder-decoder attention (not in the reference, whose only
+# instrument is ``plot_attention_matrix``).  ``mats`` is what ``ReformerTTS`` collects in eval mode: one (B, T_q, T_k) f32 matrix
+# per decoder layer (a list, or stacked (L, B, T_q, T_k)); ``n_frames`` / ``n_keys`` are int32 (B,) device tensors (other integer
+# types are converted on the device).  Everything stays on the device.
+def _lengths(n_frames: torch.Tensor, n_keys: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    return tuple(t if t.dtype == torch.int32 else t.to(torch.int32) for t in (n_frames.contiguous(), n_keys.contiguous()))
+
+
+def alignment_scores(mats, n_frames: torch.Tensor, n_keys: torch.Tensor, sigma: float = 0.2) -> Dict[str, torch.Tensor]:
+    """The usual scalar views of an attention alignment, per layer and utterance, from one ``rtts_align_stats`` call
+    (``ops.alignment_stats``) -> (L, B) f64 tensors: ``focus`` = mean_t max_k a (FastSpeech's focus rate), ``entropy`` = the
+    mean row entropy / ln K (0 at K = 1), ``guided`` = the mean row mass weighted by 1 - exp(-(k/K - t/T)^2 / 2 sigma^2)
+    (Tachibana et al.'s guided-attention weight: mass off the diagonal), ``monotonic`` = the share of frames whose arg-max key
+    does not fall back (NaN at T = 1), ``coverage`` = the share of keys that are some frame's arg-max, ``mass`` = mean_t sum_k a;
+    and ``argmax`` int32 (L, B, T_q), ``durations`` int32 (L, B, T_k) = frames per arg-max key, and the raw ``table``
+    (L, B + 1, 8).  A slot that cannot be scored is NaN."""
+    from . import ops
+    n_frames, n_keys = _lengths(n_frames, n_keys)
+    argmax, dur, table = ops.alignment_stats(mats, n_frames, n_keys, sigma)
+    t, k, total, peak, ent, guided, mono, cover = table[:, :-1].unbind(2)
+    log_k = torch.log(k)
+    return {"focus": peak / t, "entropy": torch.where(k == 1, torch.zeros_like(ent), ent / t / log_k), "guided": guided / t,
+            "monotonic": mono / (t - 1), "coverage": cover / k, "mass": total / t, "argmax": argmax, "durations": dur, "table": table}
+
+
+def alignment_durations(mats, n_frames: torch.Tensor, n_keys: torch.Tensor, floor: float = 1e-30) -> Dict[str, torch.Tensor]:
+    """Phoneme durations by monotonic alignment search (Glow-TTS) over each matrix, one ``rtts_align_mas`` call
+    (``ops.alignment_mas``) -> ``durations`` int32 (L, B, T_k) (>= 1 below K, summing to T exactly, 0 beyond), ``path`` int32
+    (L, B, T_q) (-1 beyond T), ``log_prob`` (L, B) f64 = the path's mean log-probability Q / T, ``path_mass`` (L, B) f64 = the mean
+    attention mass on the path, and the raw ``scores`` (L, B + 1, 2).  An utterance with fewer frames than keys, or one that
+    cannot be read, has durations 0 and NaN scores."""
+    from . import ops
+    n_frames, n_keys = _lengths(n_frames, n_keys)
+    dur, path, scores = ops.alignment_mas(mats, n_frames, n_keys, floor)
+    t = n_frames.to(torch.float64).unsqueeze(0)
+    return {"durations": dur, "path": path, "log_prob": scores[:, :-1, 0] / t, "path_mass": scores[:, :-1, 1] / t, "scores": scores}
+
+
+def most_focused_layer(scores: Dict[str, torch.Tensor]) -> torch.Tensor:
+    """FastSpeech's rule for picking the teacher's alignment: the layer with the highest batch-mean focus rate -> an int64 device
+    scalar, no host read.  A layer whose mean is NaN never wins against one that has a number."""
+    focus = scores["focus"].mean(dim=1)
+    return torch.where(torch.isnan(focus), torch.full_like(focus, float("-inf")), focus).argmax()

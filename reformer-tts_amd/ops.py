@@ -864,3 +864,94 @@ def f0_compare(f0_a: torch.Tensor, offsets_a: torch.Tensor, f0_b: torch.Tensor, 
               _stream())
     TIMING.stop(ev, 0.0)
     return out
+
+
+ALIGN_MAX_TQ, ALIGN_MAX_TK, ALIGN_MAX_MAT = 4096, 2048, 64    # the envelope of rtts_align_stats / rtts_align_mas (include/rtts.h)
+
+
+def _align_operand(who: str, mats, n_frames: torch.Tensor, n_keys: torch.Tensor):
+    """The common operand of the two alignment entries: a 4-D f32 (L, B, T_q, T_k) tensor or a list of L (B, T_q, T_k) matrices
+    -> (tensor that owns the memory, base pointer, sm, sb, st, L, B, T_q, T_k).  A list whose members already lie one fixed
+    distance apart in one buffer (``xattn_probs_mean(out=buf[l])``) is read in place; any other list is stacked."""
+    members = list(mats) if isinstance(mats, (list, tuple)) else [mats]
+    if not members:
+        raise ValueError(f"{who}: mats is an empty list")
+    for name, t, dt in [("mats", m, torch.float32) for m in members] + [("n_frames", n_frames, torch.int32), ("n_keys", n_keys, torch.int32)]:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt):
+            raise _lib.RttsError(f"{who} runs on the GPU only: {name} must be a CUDA {dt} tensor "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+    dev = members[0].device
+    if isinstance(mats, (list, tuple)):
+        first = members[0]
+        if any(m.dim() != 3 or m.shape != first.shape or m.device != dev for m in members):
+            raise ValueError(f"{who}: mats must be a list of (B, T_q, T_k) matrices of one shape on one device "
+                             f"(got {[tuple(m.shape) for m in members]})")
+        step = (members[1].data_ptr() - first.data_ptr()) // 4 if len(members) > 1 else 0
+        apart = all(m.stride() == first.stride() and m.data_ptr() - first.data_ptr() == 4 * step * i for i, m in enumerate(members))
+        extent = (first.shape[0] - 1) * first.stride(0) + first.shape[1] * first.stride(1)      # of one member, in elements
+        if apart and first.stride(2) == 1 and (len(members) == 1 or (step >= extent and step % 4 == 0)):
+            owner, base, sm, (sb, st) = members, first.data_ptr(), step, first.stride()[:2]
+        else:
+            owner = torch.stack(members)
+            base, (sm, sb, st) = owner.data_ptr(), owner.stride()[:3]
+        n_mat, (b, tq, tk) = len(members), first.shape
+    else:
+        if mats.dim() != 4:
+            raise ValueError(f"{who}: mats must be (L, B, T_q, T_k) or a list of (B, T_q, T_k) matrices (got {tuple(mats.shape)})")
+        if mats.stride(3) != 1 and mats.shape[3] > 1:
+            raise ValueError(f"{who}: mats must have a unit column stride (got strides {mats.stride()})")
+        owner, base, (sm, sb, st), (n_mat, b, tq, tk) = mats, mats.data_ptr(), mats.stride()[:3], mats.shape
+    for name, v, most in (("n_mat", n_mat, ALIGN_MAX_MAT), ("B", b, 65535), ("T_q", tq, ALIGN_MAX_TQ), ("T_k", tk, ALIGN_MAX_TK)):
+        if not 1 <= v <= most:
+            raise ValueError(f"{who}: {name} must be in 1..{most} (got {v})")
+    if base % 16 or sm % 4 or sb % 4 or st % 4:
+        raise ValueError(f"{who}: mats must be 16-byte aligned with strides that are multiples of 4 "
+                         f"(base {base:#x}, strides {sm}, {sb}, {st})")
+    for name, t in (("n_frames", n_frames), ("n_keys", n_keys)):
+        if not (tuple(t.shape) == (b,) and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"{who}: {name} must be contiguous of shape ({b},) on {dev}, got {tuple(t.shape)}")
+    return owner, base, int(sm), int(sb), int(st), int(n_mat), int(b), int(tq), int(tk)
+
+
+def alignment_stats(mats, n_frames: torch.Tensor, n_keys: torch.Tensor, sigma: float = 0.2) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The arg-max track and the sums behind the alignment scores of L attention matrices (``rtts_align_stats``): ``mats`` f32
+    (L, B, T_q, T_k) or a list of L (B, T_q, T_k) matrices, ``n_frames`` / ``n_keys`` int32 (B,) ON THE DEVICE (slot b uses frames
+    below n_frames[b] and keys below n_keys[b]) -> (argmax int32 (L, B, T_q), dur_argmax int32 (L, B, T_k), table f64
+    (L, B + 1, 8) = per slot [T, K, sum a, sum max, sum entropy, sum a w, monotone steps, covered keys], the last row the sums).
+    A slot that cannot be scored is NaN / 0 / -1 and makes the last row NaN.  Nothing read back: capturable."""
+    if not float(sigma) > 0.0:
+        raise ValueError(f"alignment_stats: sigma must be positive (got {sigma})")
+    owner, base, sm, sb, st, n_mat, b, tq, tk = _align_operand("alignment_stats", mats, n_frames, n_keys)
+    dev = n_frames.device
+    need = int(_lib.load().rtts_align_stats_workspace(n_mat, b, tq, tk))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    argmax = torch.empty(n_mat, b, tq, dtype=torch.int32, device=dev)
+    dur = torch.empty(n_mat, b, tk, dtype=torch.int32, device=dev)
+    table = torch.empty(n_mat, b + 1, 8, dtype=torch.float64, device=dev)
+    ev = TIMING.start("rtts_align_stats")
+    _lib.call("rtts_align_stats", base, sm, sb, st, n_mat, b, tq, tk, n_frames.data_ptr(), n_keys.data_ptr(), float(sigma), argmax.data_ptr(),
+              dur.data_ptr(), table.data_ptr(), work.data_ptr(), work.numel(), _stream())
+    TIMING.stop(ev, 0.0)
+    return argmax, dur, table
+
+
+def alignment_mas(mats, n_frames: torch.Tensor, n_keys: torch.Tensor, floor: float = 1e-30,
+                  return_path: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """Monotonic alignment search over L attention matrices (``rtts_align_mas``), operands as ``alignment_stats`` -> (durations
+    int32 (L, B, T_k): >= 1 below n_keys[b], summing to n_frames[b], 0 beyond; path int32 (L, B, T_q) = k(t), -1 beyond, or None
+    without ``return_path``; scores f64 (L, B + 1, 2) = [log-probability of the path, sum_t a[t, k(t)]], the last row the sums).
+    A slot that cannot be scored (as ``alignment_stats``, or fewer frames than keys) is 0 / -1 / NaN.  Nothing read back."""
+    if not float(floor) > 0.0:
+        raise ValueError(f"alignment_mas: floor must be positive (got {floor})")
+    owner, base, sm, sb, st, n_mat, b, tq, tk = _align_operand("alignment_mas", mats, n_frames, n_keys)
+    dev = n_frames.device
+    need = int(_lib.load().rtts_align_mas_workspace(n_mat, b, tq, tk))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    dur = torch.empty(n_mat, b, tk, dtype=torch.int32, device=dev)
+    path = torch.empty(n_mat, b, tq, dtype=torch.int32, device=dev) if return_path else None
+    scores = torch.empty(n_mat, b + 1, 2, dtype=torch.float64, device=dev)
+    ev = TIMING.start("rtts_align_mas")
+    _lib.call("rtts_align_mas", base, sm, sb, st, n_mat, b, tq, tk, n_frames.data_ptr(), n_keys.data_ptr(), float(floor), dur.data_ptr(),
+              _ptr(path), scores.data_ptr(), work.data_ptr(), work.numel(), _stream())
+    TIMING.stop(ev, 0.0)
+    return dur, path, scores

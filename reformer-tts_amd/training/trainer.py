@@ -635,14 +635,24 @@ class Trainer:
         return total / n
 
     @torch.no_grad()
-    def validate(self, batch, return_attention: bool = False):
+    def validate(self, batch, return_attention: bool = False, alignment: bool = False):
         """``LitReformerTTS.validation_step`` (``wrappers.py:107-140``): teacher-forced forward in eval mode (BatchNorm
         running statistics, no dropout), the four losses; the stacks run through the explicit executor's forward.
         -> (total, raw, post, stop, stop_mae) device scalars.  Parameters and optimizer state are untouched.
 
         ``return_attention=True``: also the decoder's encoder-decoder alignments, trimmed as ``validation_step`` trims them
         (``trim_attention_matrices``): -> (total, raw, post, stop, stop_mae, per-sample lists of per-layer (stop index, T_k
-        padded) fp32 matrices), all on the device.  The five scalars are the same bits either way."""
+        padded) fp32 matrices), all on the device.  The five scalars are the same bits either way.
+
+        ``alignment=True`` appends two dictionaries computed from the collected matrices where they lie, untrimmed and with no
+        host read (not in the reference): ``evaluation.alignment_scores`` and ``evaluation.alignment_durations`` of every decoder
+        layer, with ``n_frames = stop_tokens.argmax(1)`` (the trim of ``trim_attention_matrices``) and ``n_keys`` = the number of
+        non-padding phonemes, both taken on the device."""
+        out = self._validate(batch, return_attention, alignment)
+        return out[:-1] if alignment else out                      # without the lengths extract_durations also takes
+
+    def _validate(self, batch, return_attention: bool, alignment: bool):
+        """``validate``; with ``alignment`` the tuple ends (.., scores, durations, (n_frames, n_keys))."""
         was_training = self.model.training
         stacks = (self.model.enc.reformer.layers, self.model.dec.reformer.layers)
         dec = self.model.dec.reformer
@@ -650,7 +660,7 @@ class Trainer:
         self.model.eval()
         for st in stacks:
             st.fused_in_eval = True
-        dec.collect_attention = bool(return_attention)
+        dec.collect_attention = bool(return_attention or alignment)
         try:
             spec = batch["spectrogram"]
             raw, post, stop, mats = self.model(batch["phonemes"], spec[:, :-1], spectrogram_mask=batch["loss_mask"].mean(dim=-1))
@@ -658,12 +668,47 @@ class Trainer:
             out = (*self.loss(raw, post, stop2, spec[:, 1:], batch["stop_tokens"], batch["loss_mask"]), stop_mae(stop2, batch["stop_tokens"]))
             if return_attention:
                 out = (*out, trim_attention_matrices(list(mats), batch["stop_tokens"]))
+            if alignment:
+                out = (*out, *self._alignment(list(mats), batch))
             return out
         finally:
             for st in stacks:
                 st.fused_in_eval = False
             dec.collect_attention = was_collect
             self.model.train(was_training)
+
+    @staticmethod
+    def _alignment(mats, batch):
+        """(alignment_scores, alignment_durations, (n_frames, n_keys)) of the decoder's collected matrices, every layer, for a
+        batch in the collate layout."""
+        from .. import evaluation
+        n_frames = batch["stop_tokens"].argmax(dim=1).to(torch.int32)
+        n_keys = (batch["phonemes"] != 0).sum(dim=1).to(torch.int32)
+        return evaluation.alignment_scores(mats, n_frames, n_keys), evaluation.alignment_durations(mats, n_frames, n_keys), (n_frames, n_keys)
+
+    @staticmethod
+    def _focused(scores, durations):
+        """-> (layer int64, [focus, guided, monotonic, path_mass] batch means of that layer, f64 (4,)), all on the device."""
+        from .. import evaluation
+        layer = evaluation.most_focused_layer(scores)
+        rows = torch.stack([scores["focus"], scores["guided"], scores["monotonic"], durations["path_mass"]])     # (4, L, B)
+        return layer, rows.index_select(1, layer.view(1))[:, 0].mean(dim=1)
+
+    @torch.no_grad()
+    def extract_durations(self, corpus, ids) -> Dict[str, torch.Tensor]:
+        """The duration-extraction step of a FastSpeech-style teacher: ``validate(alignment=True)`` on the utterances ``ids`` of a
+        ``dataset.TTSCorpus`` -- ONE teacher-forced eval forward, the scores and the monotonic alignment search of every decoder
+        layer (the layers' searches run side by side in one launch) -- of which the most focused layer by FastSpeech's rule
+        (``evaluation.most_focused_layer``) is kept.  -> ``{"durations": (B, T_k) int32, "layer": int64 scalar, "log_prob": (B,)
+        f64, "path_mass": (B,) f64, "n_frames": (B,) int32, "n_keys": (B,) int32}``, all on the device, no host read:
+        ``durations[b]`` is >= 1 on utterance b's phonemes, sums to its ``n_frames`` and is 0 on the padding."""
+        from .. import evaluation
+        scores, durations, (n_frames, n_keys) = self._validate(corpus.collate([int(i) for i in ids]), False, True)[5:]
+        layer = evaluation.most_focused_layer(scores)
+        pick = layer.view(1)
+        return {"durations": durations["durations"].index_select(0, pick)[0], "layer": layer,
+                "log_prob": durations["log_prob"].index_select(0, pick)[0], "path_mass": durations["path_mass"].index_select(0, pick)[0],
+                "n_frames": n_frames, "n_keys": n_keys}
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self) -> dict:
@@ -769,9 +814,9 @@ class Trainer:
         """Seed word of the input noise of micro-batch ``micro`` of the optimizer step about to run."""
         return (self.step_seed(self.global_step) * 2654435761 + 40503 * micro + 0x5bd1e995) & 0xFFFFFFFF
 
-    def validate_corpus(self, corpus, ids, return_attention: bool = False):
+    def validate_corpus(self, corpus, ids, return_attention: bool = False, alignment: bool = False):
         """``validate`` on the utterances ``ids`` of a ``dataset.TTSCorpus``, collated on the device; never with input noise."""
-        return self.validate(corpus.collate(ids), return_attention=return_attention)
+        return self.validate(corpus.collate(ids), return_attention=return_attention, alignment=alignment)
 
     # ------------------------------------------------------------------ the generating half of validation
     def _eval_flags(self):
@@ -872,7 +917,7 @@ class Trainer:
 
     @torch.no_grad()
     def validation_epoch(self, corpus, ids, batch_size: Optional[int] = None, inference: bool = True, dtw: bool = False,
-                         **inference_kwargs) -> Dict[str, float]:
+                         alignment: bool = False, **inference_kwargs) -> Dict[str, float]:
         """The reference's validation epoch without the plotting: ``val_dataloader`` (``wrappers.py:224-232``: batches of
         ``batch_size``, default ``cfg.batch_size``, in order, the incomplete last batch dropped), ``validation_step`` on each
         (``validate_corpus``), ``validation_epoch_end``'s mean over batches of the five values (``:131-158``) and, with
@@ -880,17 +925,29 @@ class Trainer:
         ``max_len``, pass through to it).  -> the reference's log dictionary as host floats: ``val_loss``, ``val_stop_loss``,
         ``val_raw_pred_loss``, ``val_post_pred_loss``, ``val_stop_mae`` and the three ``concat_inference_*`` entries.  Everything
         is accumulated on the device and read once.  ``dtw=True`` (with ``inference``) adds ``concat_inference_mcd``, the MCD-DTW
-        of ``validate_inference_corpus(dtw=True)``, to the same single read."""
+        of ``validate_inference_corpus(dtw=True)``, to the same single read.  ``alignment=True`` adds, again to the same read,
+        ``val_alignment_focus``, ``val_alignment_guided``, ``val_alignment_monotonic`` and ``val_alignment_path_mass`` -- the batch
+        means of the most focused decoder layer (``validate(alignment=True)``), averaged over the validation batches -- and
+        ``val_alignment_layer``, that layer's index in the last batch (an int)."""
         ids = [int(i) for i in ids]
         bs = int(self.cfg.batch_size if batch_size is None else batch_size)
         if bs < 1 or len(ids) < bs:
             raise ValueError(f"validation_epoch: {len(ids)} utterances make no batch of {bs}")
         acc, n = None, len(ids) // bs
+        align_acc, layer = None, None
         for k in range(n):
-            row = torch.stack(self.validate_corpus(corpus, ids[k * bs:(k + 1) * bs]))      # total, raw, post, stop, stop_mae
+            out = self.validate_corpus(corpus, ids[k * bs:(k + 1) * bs], alignment=alignment)
+            row = torch.stack(out[:5])                                                     # total, raw, post, stop, stop_mae
             acc = row if acc is None else acc + row
+            if alignment:
+                layer, means = self._focused(out[5], out[6])
+                align_acc = means if align_acc is None else align_acc + means
         values = (acc / n).double()
         names = ["val_loss", "val_raw_pred_loss", "val_post_pred_loss", "val_stop_loss", "val_stop_mae"]
+        if alignment:
+            values = torch.cat([values, align_acc / n, layer.double().view(1)])
+            names += ["val_alignment_focus", "val_alignment_guided", "val_alignment_monotonic", "val_alignment_path_mass",
+                      "val_alignment_layer"]
         inference_time = None
         if inference:
             inf = self.validate_inference_corpus(corpus, ids[:bs], "concat", dtw=dtw, **inference_kwargs)
@@ -899,6 +956,8 @@ class Trainer:
             names += extra
             inference_time = inf["concat_inference_time"]
         logs = dict(zip(names, values.cpu().tolist()))
+        if alignment:
+            logs["val_alignment_layer"] = int(logs["val_alignment_layer"])
         if inference:
             logs["concat_inference_time"] = inference_time
         return logs
