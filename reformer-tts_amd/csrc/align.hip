@@ -20,9 +20,10 @@
 // rtts_align_mas, two kernels: the recurrence + back-track, one workgroup per (matrix, slot), and the totals kernel above.
 //   The key front lies over the lanes: wave w owns keys [64 R w, 64 R (w + 1)), lane l the R keys 64 (R w + r) + l (R = 2 beyond
 //   1024 keys).  Q[t, k] needs Q[t-1, k] (a register) and Q[t-1, k-1]: the neighbour lane's register by one DPP wave_shr:1 move
-//   per word; lane 0 takes lane 63's (r = 1: of the same wave, a v_readlane) or, for r = 0, the last key of the wave before, which
-//   comes through an LDS ring.  The waves run SKEWED as in dtw.hip: wave w works on frame chunk u - w in round u, so wave w - 1
-//   wrote the ring rows of a chunk one barrier before wave w reads them: ceil(T / 16) + waves - 1 barriers instead of T.
+//   per word (rtts_wave_shr1 of score_common.h, the move of dtw.hip's recurrence); lane 0 takes lane 63's (r = 1: of the same
+//   wave, a v_readlane) or, for r = 0, the last key of the wave before, which comes through an LDS ring.  The waves run SKEWED
+//   like those of dtw.hip's recurrence: wave w works on frame chunk u - w in round u, so wave w - 1 wrote the ring rows of a
+//   chunk one barrier before wave w reads them: ceil(T / 16) + waves - 1 barriers instead of T.
 //   A frame's values of a are loaded 16 frames ahead, into the registers the frame just taken leaves free (16 R registers, no
 //   second copy of a chunk), so the global latency is off the dependent chain.
 //   The decision of a cell (1 = came from k - 1; a tie stays) is one bit: a wave's 64 decisions are one ballot, stored as one
@@ -31,7 +32,7 @@
 //   the feasible band, so nothing is predicated.  Wave 0 walks the bits back 64 frames at a time: lane j loads frame hi - j's two
 //   words that can hold the path (k falls by at most 63 over 64 frames), the walk itself reads them by v_readlane -- no
 //   dependent memory access per frame.  sum_t a[t, k(t)] is then added in frame order.
-#include "rtts_common.h"
+#include "score_common.h"
 
 #define ALIGN_MAX_TQ 4096
 #define ALIGN_MAX_TK 2048
@@ -49,7 +50,6 @@ static_assert(ALIGN_RING >= 2 * ALIGN_CHUNK + 1 && (ALIGN_RING & (ALIGN_RING - 1
               "the ring holds the chunk being read, its predecessor row and the chunk being written");
 static_assert(ALIGN_MAX_TK <= 2 * 64 * ALIGN_MAS_MAX_WAVES, "two keys per lane cover the key envelope");
 
-__device__ __forceinline__ double align_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 __device__ __forceinline__ double align_ninf() { return __longlong_as_double(0xfff0000000000000LL); }
 
 struct AlignShape {
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(ALIGN_FOLD_THREADS) void align_fold_kernel(int B, i
     if (!s.ok || __syncthreads_or(flagged)) {                      // uniform over the workgroup
         for (int t = tid; t < Tq; t += ALIGN_FOLD_THREADS) am[t] = -1;
         for (int k = tid; k < Tk; k += ALIGN_FOLD_THREADS) du[k] = 0;
-        if (tid < 8) row[tid] = align_nan();
+        if (tid < 8) row[tid] = rtts_nan64();
         return;
     }
     const int T = s.t, K = s.k;
@@ -228,11 +228,6 @@ __global__ void align_totals_kernel(double* __restrict__ table, int B, int cols)
 }
 
 // ------------------------------------------------------------------------------------------------ monotonic alignment search
-// lane l takes `v` of lane l - 1 and lane 0 keeps `own` (v_mov_b32 with DPP wave_shr:1)
-__device__ __forceinline__ int align_from_below(int own, int v) { return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ double align_from_below(double own, double v) {
-    return __hiloint2double(align_from_below(__double2hiint(own), __double2hiint(v)), align_from_below(__double2loint(own), __double2loint(v)));
-}
 // the value of lane `lane` (uniform), in every lane
 __device__ __forceinline__ double align_lane(double v, int lane) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
@@ -286,7 +281,7 @@ __global__ __launch_bounds__(64 * ALIGN_MAS_MAX_WAVES) void align_mas_kernel(
         for (int k = tid; k < Tk; k += nthreads) du[k] = 0;
         if (po)
             for (int t = tid; t < Tq; t += nthreads) po[t] = -1;
-        if (tid < 2) sc[tid] = align_nan();
+        if (tid < 2) sc[tid] = rtts_nan64();
     };
     if (!s.ok || s.t < s.k) {                                      // uniform over the workgroup: nothing of the slot is read
         wipe();
@@ -342,8 +337,8 @@ __global__ __launch_bounds__(64 * ALIGN_MAS_MAX_WAVES) void align_mas_kernel(
                     // Q[-1, -1] = 0 makes Q[0, 0] = c[0, 0] and leaves every other cell of frame 0 at -inf
                     const double edge = w > 0 ? align_lane(edge_all, i) : (t == 0 ? 0.0 : ninf);
                     double left[R];
-                    left[0] = align_from_below(edge, q[0]);
-                    if (R == 2) left[R - 1] = align_from_below(align_lane(q[0], 63), q[R - 1]);
+                    left[0] = rtts_wave_shr1(edge, q[0]);
+                    if (R == 2) left[R - 1] = rtts_wave_shr1(align_lane(q[0], 63), q[R - 1]);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         bad |= !isfinite(x[r]);
@@ -414,7 +409,6 @@ __global__ __launch_bounds__(64 * ALIGN_MAS_MAX_WAVES) void align_mas_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------ entry points
-static inline int64_t align_256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 static inline bool align_envelope(int n_mat, int B, int Tq, int Tk) {
     return n_mat >= 1 && n_mat <= ALIGN_MAX_MAT && B >= 1 && B <= 65535 && Tq >= 1 && Tq <= ALIGN_MAX_TQ && Tk >= 1 && Tk <= ALIGN_MAX_TK;
 }
@@ -447,7 +441,7 @@ static int align_check_operand(const char* who, const float* a, int64_t sm, int6
 extern "C" int64_t rtts_align_stats_workspace(int n_mat, int B, int Tq, int Tk) {
     if (!align_envelope(n_mat, B, Tq, Tk)) return -1;
     const int64_t slots = (int64_t)n_mat * B * align_tiles(Tq);
-    return align_256(slots * 4 * 8) + align_256(slots * 4);
+    return rtts_align256(slots * 4 * 8) + rtts_align256(slots * 4);
 }
 
 extern "C" int rtts_align_stats(const float* a, int64_t sm, int64_t sb, int64_t st, int n_mat, int B, int Tq, int Tk, const int32_t* n_frames,
@@ -464,7 +458,7 @@ extern "C" int rtts_align_stats(const float* a, int64_t sm, int64_t sb, int64_t 
                  (long long)workspace_bytes, (long long)need);
     const int tiles = align_tiles(Tq);
     double* part = (double*)workspace;
-    int32_t* part_bad = (int32_t*)((char*)workspace + align_256((int64_t)n_mat * B * tiles * 4 * 8));
+    int32_t* part_bad = (int32_t*)((char*)workspace + rtts_align256((int64_t)n_mat * B * tiles * 4 * 8));
     RTTS_ENTER(stream);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(align_rows_kernel, dim3((unsigned)tiles, (unsigned)B, (unsigned)n_mat), dim3(ALIGN_ROW_THREADS), 0, s, a, sm, sb, st, B, Tq,
@@ -481,7 +475,7 @@ extern "C" int rtts_align_stats(const float* a, int64_t sm, int64_t sb, int64_t 
 extern "C" int64_t rtts_align_mas_workspace(int n_mat, int B, int Tq, int Tk) {
     if (!align_envelope(n_mat, B, Tq, Tk)) return -1;
     const AlignMasLds L = align_mas_lds(Tq, Tk);
-    return L.bits >= 0 ? 256 : align_256((int64_t)n_mat * B * Tq * L.words * 8);
+    return L.bits >= 0 ? 256 : rtts_align256((int64_t)n_mat * B * Tq * L.words * 8);
 }
 
 static RttsLdsState g_align_lds[2][2];

@@ -1,8 +1,9 @@
 // B generated spectrograms aligned to their truths by dynamic time warping (rtts_dtw_align of include/rtts.h): the path cost and
-// path length behind MCD-DTW, the timing-invariant sibling of rtts_infer_metrics, with the same addressing and nothing read back.
+// path length behind MCD-DTW, the timing-invariant sibling of rtts_infer_metrics, with the same addressing (the truth description
+// of score_common.h) and nothing read back.
 //
 // Four kernels on the caller's stream, every one reading the slot's two lengths N (generated frames) and M (truth frames) on the
-// device, as infer_metrics.hip reads its bounds:
+// device (dtw_shape over rtts_truth_pick of score_common.h):
 //   project    grid (frame tiles, B, 2).  32 frames by all n_mel channels staged in LDS (either layout, the staging of
 //              infer_metrics.hip), then p[k] = f32(sum_m f64(basis[k, m]) f64(x[m])), m ascending (a product of two f32 is exact
 //              in f64, so the sum is the same with and without contraction).  A non-finite x or p sets the frame's flag word.
@@ -28,10 +29,10 @@
 //   fold       one workgroup: the two means over the slots, by index.
 // A slot that is not to be read (N = 0, a bad description or id, M outside 1..lm) or that holds a non-finite compared value
 // skips the recurrence: cost NaN, steps 0.  The flags are OR-ed by the recurrence's workgroup before its first step: no atomics.
-#include "rtts_common.h"
+#include "score_common.h"
 
 #define DTW_MAX_FRAMES 2048
-#define DTW_MAX_DIM 128           // n_mel and n_proj
+#define DTW_MAX_DIM RTTS_SCORE_MAX_MEL   // n_mel and n_proj
 #define DTW_PROJ_THREADS 256
 #define DTW_PROJ_TILE 32
 #define DTW_DIST_THREADS 256
@@ -56,44 +57,29 @@ struct DtwShape {
     bool ok;                      // false: the slot is not to be read (cost NaN, steps 0)
 };
 
-// the slot's bounds, by the same scalar reads in every workgroup of every kernel: they agree without talking to each other
-__device__ __forceinline__ DtwShape dtw_shape(int b, const int64_t* __restrict__ gen_stop, int L, const int64_t* __restrict__ fo, int n_utt,
-                                              const int32_t* __restrict__ ids, const int64_t* __restrict__ starts,
-                                              const int32_t* __restrict__ lengths, int64_t truth_frames, int lm) {
+// the slot's bounds on top of the shared truth pick: a truth of 1..lm frames and at least one generated frame, or nothing is read
+__device__ __forceinline__ DtwShape dtw_shape(int b, const int64_t* __restrict__ gen_stop, int L, const RttsTruth& tr, int lm) {
     DtwShape s = {0, 0, 0, false};
-    int64_t c0, c1;
-    if (fo) {
-        const int64_t u = ids ? (int64_t)ids[b] : (int64_t)b;
-        if (u < 0 || u >= n_utt) return s;
-        c0 = fo[u];
-        c1 = fo[u + 1];
-    } else {
-        c0 = starts[b];
-        c1 = c0 + (int64_t)lengths[b];
-    }
-    if (c0 < 0 || c1 <= c0 || c1 > truth_frames || c1 - c0 > (int64_t)lm) return s;
+    const RttsTruthPick p = rtts_truth_pick(b, tr);
+    if (!p.ok || (uint64_t)(p.len - 1) >= (uint64_t)lm) return s;  // 1 <= len <= lm in one compare: an ok pick has len >= 0
     int64_t n = gen_stop ? gen_stop[b] : (int64_t)L;
     n = n < (int64_t)L ? n : (int64_t)L;
     if (n < 1) return s;
-    s.f0 = c0;
+    s.f0 = p.f0;
     s.n = (int)n;
-    s.m = (int)(c1 - c0);
+    s.m = (int)p.len;
     s.ok = true;
     return s;
 }
 
-__device__ __forceinline__ double dtw_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
 __global__ __launch_bounds__(DTW_PROJ_THREADS) void dtw_project_kernel(
     const float* __restrict__ gen, int64_t gs_b, int64_t gs_mel, int64_t gs_t, int L, const int64_t* __restrict__ gen_stop,
-    const float* __restrict__ truth, int64_t ts_mel, int64_t ts_t, int64_t truth_frames, const int64_t* __restrict__ fo, int n_utt,
-    const int32_t* __restrict__ ids, const int64_t* __restrict__ starts, const int32_t* __restrict__ lengths, int n_mel, int lm,
-    const float* __restrict__ basis, int n_proj, float* __restrict__ pg, float* __restrict__ pt, int32_t* __restrict__ fg,
-    int32_t* __restrict__ ft) {
+    const float* __restrict__ truth, int64_t ts_mel, int64_t ts_t, RttsTruth tr, int n_mel, int lm, const float* __restrict__ basis,
+    int n_proj, float* __restrict__ pg, float* __restrict__ pt, int32_t* __restrict__ fg, int32_t* __restrict__ ft) {
     __shared__ float tile[DTW_PROJ_TILE * (DTW_MAX_DIM + 1)];
     __shared__ int bad[DTW_PROJ_TILE];
     const int b = blockIdx.y, side = blockIdx.z, tid = threadIdx.x;
-    const DtwShape s = dtw_shape(b, gen_stop, L, fo, n_utt, ids, starts, lengths, truth_frames, lm);
+    const DtwShape s = dtw_shape(b, gen_stop, L, tr, lm);
     const int count = side ? s.m : s.n, cap = side ? lm : L;
     const int t0 = blockIdx.x * DTW_PROJ_TILE;
     if (!s.ok || t0 >= count) return;                              // uniform over the workgroup
@@ -131,13 +117,12 @@ __global__ __launch_bounds__(DTW_PROJ_THREADS) void dtw_project_kernel(
 
 template <int R>
 __global__ __launch_bounds__(DTW_DIST_THREADS) void dtw_dist_kernel(
-    const float* __restrict__ pg, const float* __restrict__ pt, int L, const int64_t* __restrict__ gen_stop, int64_t truth_frames,
-    const int64_t* __restrict__ fo, int n_utt, const int32_t* __restrict__ ids, const int64_t* __restrict__ starts,
-    const int32_t* __restrict__ lengths, int lm, int n_proj, float* __restrict__ table, int pitch, int64_t slot_words) {
+    const float* __restrict__ pg, const float* __restrict__ pt, int L, const int64_t* __restrict__ gen_stop, RttsTruth tr, int lm, int n_proj,
+    float* __restrict__ table, int pitch, int64_t slot_words) {
     __shared__ float sp[DTW_DIST_TILE * (DTW_DIST_KC + 1)];
     __shared__ float sq[DTW_DIST_TILE * (DTW_DIST_KC + 1)];
     const int b = blockIdx.z, tid = threadIdx.x;
-    const DtwShape s = dtw_shape(b, gen_stop, L, fo, n_utt, ids, starts, lengths, truth_frames, lm);
+    const DtwShape s = dtw_shape(b, gen_stop, L, tr, lm);
     const int i0 = blockIdx.y * DTW_DIST_TILE, j0 = blockIdx.x * DTW_DIST_TILE;
     if (!s.ok || i0 >= s.n || j0 >= s.m) return;                   // uniform over the workgroup
     const float* gp = pg + (int64_t)b * L * n_proj;
@@ -182,27 +167,15 @@ __global__ __launch_bounds__(DTW_DIST_THREADS) void dtw_dist_kernel(
         }
 }
 
-// lane l takes `v` of lane l - 1 and lane 0 keeps `own` (v_mov_b32 with DPP wave_shr:1, no LDS round trip)
-__device__ __forceinline__ int dtw_from_below(int own, int v) { return __builtin_amdgcn_update_dpp(own, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ double dtw_from_below(double own, double v) {
-    return __hiloint2double(dtw_from_below(__double2hiint(own), __double2hiint(v)), dtw_from_below(__double2loint(own), __double2loint(v)));
-}
-// lane l takes `v` of lane l + 1 (DPP wave_shl:1); lane 63 keeps its own
-__device__ __forceinline__ int dtw_from_above(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false); }
-__device__ __forceinline__ double dtw_from_above(double v) {
-    return __hiloint2double(dtw_from_above(__double2hiint(v)), dtw_from_above(__double2loint(v)));
-}
-
 template <int R>
 __global__ __launch_bounds__(DTW_THREADS) void dtw_recur_kernel(
     const float* __restrict__ table, int pitch, int64_t slot_words, const int32_t* __restrict__ fg, const int32_t* __restrict__ ft, int L,
-    const int64_t* __restrict__ gen_stop, int64_t truth_frames, const int64_t* __restrict__ fo, int n_utt, const int32_t* __restrict__ ids,
-    const int64_t* __restrict__ starts, const int32_t* __restrict__ lengths, int lm, double* __restrict__ cost, int32_t* __restrict__ steps) {
+    const int64_t* __restrict__ gen_stop, RttsTruth tr, int lm, double* __restrict__ cost, int32_t* __restrict__ steps) {
     __shared__ double ring_d[DTW_WAVES][DTW_RING];
     __shared__ int ring_s[DTW_WAVES][DTW_RING];
     const int b = blockIdx.x, tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);        // a scalar: the step counters below stay out of the VALU
-    const DtwShape s = dtw_shape(b, gen_stop, L, fo, n_utt, ids, starts, lengths, truth_frames, lm);
+    const DtwShape s = dtw_shape(b, gen_stop, L, tr, lm);
     int flagged = 0;
     if (s.ok) {
         for (int i = tid; i < s.n; i += DTW_THREADS) flagged |= fg[(int64_t)b * L + i];
@@ -210,7 +183,7 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_recur_kernel(
     }
     if (!s.ok || __syncthreads_or(flagged)) {                      // uniform over the workgroup
         if (tid == 0) {
-            cost[b] = dtw_nan();
+            cost[b] = rtts_nan64();
             steps[b] = 0;
         }
         return;
@@ -281,10 +254,10 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_recur_kernel(
                 for (int a = 0; a < AHEAD; ++a) {
                     const int sigma = sigma0 + a;
                     // the row above my first row at my column: the neighbour lane's last row of the step before; lane 0: the ring
-                    const double up_d = dtw_from_below(above_d, last_d);
-                    const int up_s = dtw_from_below(above_s, last_s);
-                    above_d = dtw_from_above(above_d);
-                    above_s = dtw_from_above(above_s);
+                    const double up_d = rtts_wave_shr1(above_d, last_d);
+                    const int up_s = rtts_wave_shr1(above_s, last_s);
+                    above_d = rtts_wave_shl1(above_d);
+                    above_s = rtts_wave_shl1(above_s);
                     double ab_d = up_d, dg_d = diag_d;             // above and diagonal of the current row
                     int ab_s = up_s, dg_s = diag_s;
 #pragma unroll
@@ -322,19 +295,6 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_recur_kernel(
     }
 }
 
-// sum over the workgroup in a fixed order: lanes by halving distances, then the waves by index; valid in thread 0
-__device__ __forceinline__ double dtw_block_sum(double v, double* wsum) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    const int tid = threadIdx.x;
-    __syncthreads();                                               // wsum may still be read from a previous call
-    if ((tid & 63) == 0) wsum[tid >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (tid == 0)
-        for (int w = 0; w < DTW_FOLD_THREADS / 64; ++w) s += wsum[w];
-    return s;
-}
-
 __global__ __launch_bounds__(DTW_FOLD_THREADS) void dtw_fold_kernel(const double* __restrict__ cost, const int32_t* __restrict__ steps, int B,
                                                                     double* __restrict__ totals) {
     __shared__ double wsum[DTW_FOLD_THREADS / 64];
@@ -345,16 +305,15 @@ __global__ __launch_bounds__(DTW_FOLD_THREADS) void dtw_fold_kernel(const double
         a_cost += c;
         a_steps += n;                                              // exact: at most 65535 * 4095
     }
-    const double t_mean = dtw_block_sum(a_mean, wsum);
-    const double t_cost = dtw_block_sum(a_cost, wsum);
-    const double t_steps = dtw_block_sum(a_steps, wsum);
+    const double t_mean = rtts_block_sum<DTW_FOLD_THREADS>(a_mean, wsum);
+    const double t_cost = rtts_block_sum<DTW_FOLD_THREADS>(a_cost, wsum);
+    const double t_steps = rtts_block_sum<DTW_FOLD_THREADS>(a_steps, wsum);
     if (threadIdx.x == 0) {
         totals[0] = t_mean / (double)B;
         totals[1] = t_cost / t_steps;
     }
 }
 
-static inline int64_t dtw_align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 static inline int dtw_pitch(int L) { return ((L < 1 ? 1 : L) + 63) & ~63; }
 
 struct DtwLayout {
@@ -367,11 +326,11 @@ static inline DtwLayout dtw_layout(int B, int L, int lm, int n_proj) {
     w.pitch = dtw_pitch(L);
     w.slot_words = (int64_t)(lm + 63) * w.pitch;
     w.pg = 0;
-    w.pt = w.pg + dtw_align256((int64_t)B * (L < 1 ? 1 : L) * n_proj * 4);
-    w.fg = w.pt + dtw_align256((int64_t)B * lm * n_proj * 4);
-    w.ft = w.fg + dtw_align256((int64_t)B * (L < 1 ? 1 : L) * 4);
-    w.table = w.ft + dtw_align256((int64_t)B * lm * 4);
-    w.total = w.table + dtw_align256((int64_t)B * w.slot_words * 4);
+    w.pt = w.pg + rtts_align256((int64_t)B * (L < 1 ? 1 : L) * n_proj * 4);
+    w.fg = w.pt + rtts_align256((int64_t)B * lm * n_proj * 4);
+    w.ft = w.fg + rtts_align256((int64_t)B * (L < 1 ? 1 : L) * 4);
+    w.table = w.ft + rtts_align256((int64_t)B * lm * 4);
+    w.total = w.table + rtts_align256((int64_t)B * w.slot_words * 4);
     return w;
 }
 
@@ -387,25 +346,14 @@ extern "C" int rtts_dtw_align(const float* gen, int64_t gs_b, int64_t gs_mel, in
                               const int64_t* starts, const int32_t* lengths, int B, int n_mel, int lm, const float* basis, int n_proj,
                               void* workspace, int64_t workspace_bytes, int phases, double* cost, int32_t* steps, double* totals, void* stream) {
     RTTS_REQUIRE(L >= 0 && L <= DTW_MAX_FRAMES, "rtts_dtw_align: L must be in 0..%d (got %d)", DTW_MAX_FRAMES, L);
-    RTTS_REQUIRE(gen || L == 0, "rtts_dtw_align: gen is a null pointer (and L = %d frames are to be read)", L);
-    RTTS_REQUIRE(truth, "rtts_dtw_align: truth is a null pointer");
+    if (rtts_check_scored("rtts_dtw_align", gen, L, truth, frame_offsets, n_utt, ids, starts, lengths, B, n_mel, truth_frames)) return -1;
     RTTS_REQUIRE(workspace, "rtts_dtw_align: workspace is a null pointer");
     RTTS_REQUIRE(cost, "rtts_dtw_align: cost is a null pointer");
     RTTS_REQUIRE(steps, "rtts_dtw_align: steps is a null pointer");
     RTTS_REQUIRE(totals, "rtts_dtw_align: totals is a null pointer");
-    const bool corpus = frame_offsets != nullptr, padded = starts != nullptr || lengths != nullptr;
-    RTTS_REQUIRE(corpus || padded, "rtts_dtw_align: no truth description: give frame_offsets (+ ids), or starts + lengths");
-    RTTS_REQUIRE(!(corpus && padded), "rtts_dtw_align: two truth descriptions: give frame_offsets (+ ids) OR starts + lengths");
-    RTTS_REQUIRE(corpus || (starts && lengths), "rtts_dtw_align: the padded-batch description needs both starts and lengths");
-    RTTS_REQUIRE(corpus || !ids, "rtts_dtw_align: ids belong to the corpus description (frame_offsets is a null pointer)");
-    RTTS_REQUIRE(!corpus || n_utt >= 1, "rtts_dtw_align: n_utt must be positive (got %d)", n_utt);
-    RTTS_REQUIRE(!corpus || ids || B <= n_utt, "rtts_dtw_align: without ids slot b is utterance b: B = %d exceeds n_utt = %d", B, n_utt);
-    RTTS_REQUIRE(B >= 1 && B <= 65535, "rtts_dtw_align: B must be in 1..65535 (got %d)", B);
-    RTTS_REQUIRE(n_mel >= 1 && n_mel <= DTW_MAX_DIM, "rtts_dtw_align: n_mel must be in 1..%d (got %d)", DTW_MAX_DIM, n_mel);
     RTTS_REQUIRE(lm >= 1 && lm <= DTW_MAX_FRAMES, "rtts_dtw_align: lm must be in 1..%d (got %d)", DTW_MAX_FRAMES, lm);
     RTTS_REQUIRE(n_proj >= 1 && n_proj <= DTW_MAX_DIM, "rtts_dtw_align: n_proj must be in 1..%d (got %d)", DTW_MAX_DIM, n_proj);
     RTTS_REQUIRE(basis || n_proj == n_mel, "rtts_dtw_align: without a basis n_proj must be n_mel = %d (got %d)", n_mel, n_proj);
-    RTTS_REQUIRE(truth_frames >= 0, "rtts_dtw_align: truth_frames must not be negative (got %lld)", (long long)truth_frames);
     RTTS_REQUIRE(phases >= 1 && phases <= RTTS_DTW_ALL, "rtts_dtw_align: phases must be a non-empty subset of RTTS_DTW_ALL (got %d)", phases);
     const DtwLayout w = dtw_layout(B, L, lm, n_proj);
     RTTS_REQUIRE(workspace_bytes >= w.total, "rtts_dtw_align: workspace_bytes = %lld is smaller than rtts_dtw_workspace_bytes = %lld",
@@ -418,31 +366,32 @@ extern "C" int rtts_dtw_align(const float* gen, int64_t gs_b, int64_t gs_mel, in
     float* table = (float*)(base + w.table);
     const int rows = L > DTW_THREADS ? 2 : 1;                      // rows of the table per thread of the recurrence
     const int longer = L > lm ? L : lm;
+    const RttsTruth tr = {truth_frames, frame_offsets, n_utt, ids, starts, lengths};
     RTTS_ENTER(stream);
     hipStream_t st = (hipStream_t)stream;
     if (phases & RTTS_DTW_PROJECT) {
         hipLaunchKernelGGL(dtw_project_kernel, dim3((unsigned)((longer + DTW_PROJ_TILE - 1) / DTW_PROJ_TILE), (unsigned)B, 2),
-                           dim3(DTW_PROJ_THREADS), 0, st, gen, gs_b, gs_mel, gs_t, L, gen_stop, truth, ts_mel, ts_t, truth_frames, frame_offsets,
-                           n_utt, ids, starts, lengths, n_mel, lm, basis, n_proj, pg, pt, fg, ft);
+                           dim3(DTW_PROJ_THREADS), 0, st, gen, gs_b, gs_mel, gs_t, L, gen_stop, truth, ts_mel, ts_t, tr, n_mel, lm, basis, n_proj, pg,
+                           pt, fg, ft);
         RTTS_LAUNCH_CHECK("rtts_dtw_align (project)");
     }
     if ((phases & RTTS_DTW_DISTANCES) && L > 0) {
         const dim3 grid((unsigned)((lm + DTW_DIST_TILE - 1) / DTW_DIST_TILE), (unsigned)((L + DTW_DIST_TILE - 1) / DTW_DIST_TILE), (unsigned)B);
         if (rows == 1)
-            hipLaunchKernelGGL(dtw_dist_kernel<1>, grid, dim3(DTW_DIST_THREADS), 0, st, pg, pt, L, gen_stop, truth_frames, frame_offsets, n_utt, ids,
-                               starts, lengths, lm, n_proj, table, w.pitch, w.slot_words);
+            hipLaunchKernelGGL(dtw_dist_kernel<1>, grid, dim3(DTW_DIST_THREADS), 0, st, pg, pt, L, gen_stop, tr, lm, n_proj, table, w.pitch,
+                               w.slot_words);
         else
-            hipLaunchKernelGGL(dtw_dist_kernel<2>, grid, dim3(DTW_DIST_THREADS), 0, st, pg, pt, L, gen_stop, truth_frames, frame_offsets, n_utt, ids,
-                               starts, lengths, lm, n_proj, table, w.pitch, w.slot_words);
+            hipLaunchKernelGGL(dtw_dist_kernel<2>, grid, dim3(DTW_DIST_THREADS), 0, st, pg, pt, L, gen_stop, tr, lm, n_proj, table, w.pitch,
+                               w.slot_words);
         RTTS_LAUNCH_CHECK("rtts_dtw_align (distances)");
     }
     if (phases & RTTS_DTW_RECURRENCE) {
         if (rows == 1)
             hipLaunchKernelGGL(dtw_recur_kernel<1>, dim3((unsigned)B), dim3(DTW_THREADS), 0, st, table, w.pitch, w.slot_words, fg, ft, L, gen_stop,
-                               truth_frames, frame_offsets, n_utt, ids, starts, lengths, lm, cost, steps);
+                               tr, lm, cost, steps);
         else
             hipLaunchKernelGGL(dtw_recur_kernel<2>, dim3((unsigned)B), dim3(DTW_THREADS), 0, st, table, w.pitch, w.slot_words, fg, ft, L, gen_stop,
-                               truth_frames, frame_offsets, n_utt, ids, starts, lengths, lm, cost, steps);
+                               tr, lm, cost, steps);
         RTTS_LAUNCH_CHECK("rtts_dtw_align (recurrence)");
     }
     if (phases & RTTS_DTW_FOLD) {

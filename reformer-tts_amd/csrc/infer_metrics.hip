@@ -5,7 +5,8 @@
 // Two kernels on the caller's stream:
 //   tiles  grid (tiles, B).  Workgroup (k, b) owns the frame tiles k, k + tiles, ... of slot b, IM_TILE = 32 frames by all n_mel
 //          channels each, and writes ONE f64 partial, partials[b * tiles + k].  The workgroups of a slot repeat the same scalar
-//          reads (the id, its offsets or start / length) and agree on the utterance's bounds without talking to each other.
+//          reads (the id, its offsets or start / length: rtts_truth_pick of score_common.h) and agree on the utterance's bounds
+//          without talking to each other.
 //   fold   one workgroup: sse[b] = the slot's partials added by index, stop_err[b], and the two means, again by index.
 // No atomics: every sum has one fixed order, which depends on (B, n_mel, lm, the lengths) and on nothing else -- not on the
 // strides either.  That is why there is ONE compute mapping: thread tid always owns frame (tid & 31) of the tile and the channels
@@ -21,60 +22,21 @@
 // reads tile[(lane & 31) * pitch + m]: 32 lanes, 32 multiples of an odd pitch, 32 different banks (ds_read_b32, same rule).
 // Two tiles of 32 x 129 words are 33 KB: four workgroups fit the 160 KB of a CU's LDS.  Frames at or past L read as generated zeros;
 // frames at or past len_b are not read at all, so a NaN there reaches nothing, while one in a counted frame reaches its slot's sse.
-#include "rtts_common.h"
+#include "score_common.h"
 
 #define IM_THREADS 256
 #define IM_TILE 32
-#define IM_MAX_MEL 128
+#define IM_MAX_MEL RTTS_SCORE_MAX_MEL
 #define IM_MAX_TILES 256          // partials per slot: longer batches stride over their tiles
-
-struct ImPick {
-    int64_t f0, len;              // first truth frame of the slot and its frame count
-    bool ok;                      // false: the description points outside the truth buffer (the slot's results are NaN)
-};
-
-__device__ __forceinline__ ImPick im_pick(int b, const int64_t* __restrict__ fo, int n_utt, const int32_t* __restrict__ ids,
-                                          const int64_t* __restrict__ starts, const int32_t* __restrict__ lengths, int64_t truth_frames) {
-    ImPick p = {0, 0, false};
-    int64_t c0, c1;
-    if (fo) {
-        const int64_t u = ids ? (int64_t)ids[b] : (int64_t)b;
-        if (u < 0 || u >= n_utt) return p;
-        c0 = fo[u];
-        c1 = fo[u + 1];
-    } else {
-        c0 = starts[b];
-        c1 = c0 + (int64_t)lengths[b];
-    }
-    if (c0 < 0 || c1 < c0 || c1 > truth_frames) return p;
-    p.f0 = c0;
-    p.len = c1 - c0;
-    p.ok = true;
-    return p;
-}
-
-// sum over the workgroup in a fixed order: lanes by halving distances, then the four waves by index; valid in thread 0
-__device__ __forceinline__ double im_block_sum(double v, double* wsum) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off);
-    const int tid = threadIdx.x;
-    __syncthreads();                                               // wsum may still be read from a previous call
-    if ((tid & 63) == 0) wsum[tid >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (tid == 0)
-        for (int w = 0; w < IM_THREADS / 64; ++w) s += wsum[w];
-    return s;
-}
 
 __global__ __launch_bounds__(IM_THREADS) void infer_metrics_tiles_kernel(
     const float* __restrict__ gen, int64_t gs_b, int64_t gs_mel, int64_t gs_t, int L, const float* __restrict__ truth, int64_t ts_mel,
-    int64_t ts_t, int64_t truth_frames, const int64_t* __restrict__ fo, int n_utt, const int32_t* __restrict__ ids,
-    const int64_t* __restrict__ starts, const int32_t* __restrict__ lengths, int n_mel, int tiles, double* __restrict__ partials) {
+    int64_t ts_t, RttsTruth tr, int n_mel, int tiles, double* __restrict__ partials) {
     __shared__ float tile_g[IM_TILE * (IM_MAX_MEL + 1)];
     __shared__ float tile_t[IM_TILE * (IM_MAX_MEL + 1)];
     __shared__ double wsum[IM_THREADS / 64];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const ImPick p = im_pick(b, fo, n_utt, ids, starts, lengths, truth_frames);
+    const RttsTruthPick p = rtts_truth_pick(b, tr);
     const bool stage_g = gs_t != 1, stage_t = ts_t != 1;           // uniform over the launch
     const int pitch = n_mel | 1;
     const int ft = tid & (IM_TILE - 1), ph = tid / IM_TILE;
@@ -105,34 +67,32 @@ __global__ __launch_bounds__(IM_THREADS) void infer_metrics_tiles_kernel(
             }
         }
     }
-    const double s = im_block_sum(acc, wsum);
-    if (tid == 0) partials[(int64_t)b * tiles + blockIdx.x] = p.ok ? s : __longlong_as_double(0x7ff8000000000000LL);
+    const double s = rtts_block_sum<IM_THREADS>(acc, wsum);
+    if (tid == 0) partials[(int64_t)b * tiles + blockIdx.x] = p.ok ? s : rtts_nan64();
 }
 
 __global__ __launch_bounds__(IM_THREADS) void infer_metrics_fold_kernel(
-    const double* __restrict__ partials, int tiles, const int64_t* __restrict__ gen_stop, int64_t truth_frames,
-    const int64_t* __restrict__ fo, int n_utt, const int32_t* __restrict__ ids, const int64_t* __restrict__ starts,
-    const int32_t* __restrict__ lengths, int B, int n_mel, int lm, double* __restrict__ sse, double* __restrict__ stop_err,
-    double* __restrict__ totals) {
+    const double* __restrict__ partials, int tiles, const int64_t* __restrict__ gen_stop, RttsTruth tr, int B, int n_mel, int lm,
+    double* __restrict__ sse, double* __restrict__ stop_err, double* __restrict__ totals) {
     __shared__ double wsum[IM_THREADS / 64];
     const int tid = threadIdx.x;
     double a_sse = 0.0, a_stop = 0.0;
     for (int b = tid; b < B; b += IM_THREADS) {
-        const ImPick p = im_pick(b, fo, n_utt, ids, starts, lengths, truth_frames);
+        const RttsTruthPick p = rtts_truth_pick(b, tr);
         double s = 0.0;
         for (int k = 0; k < tiles; ++k) s += partials[(int64_t)b * tiles + k];
         double e = 0.0;
         if (gen_stop) {
             const int64_t d = gen_stop[b] - (p.len - 1);
-            e = p.ok ? (double)(d < 0 ? -d : d) : __longlong_as_double(0x7ff8000000000000LL);
+            e = p.ok ? (double)(d < 0 ? -d : d) : rtts_nan64();
         }
         sse[b] = s;
         stop_err[b] = e;
         a_sse += s;
         a_stop += e;
     }
-    const double t_sse = im_block_sum(a_sse, wsum);
-    const double t_stop = im_block_sum(a_stop, wsum);
+    const double t_sse = rtts_block_sum<IM_THREADS>(a_sse, wsum);
+    const double t_stop = rtts_block_sum<IM_THREADS>(a_stop, wsum);
     if (tid == 0) {
         totals[0] = t_sse / ((double)B * (double)n_mel * (double)lm);
         totals[1] = t_stop / (double)B;
@@ -149,31 +109,21 @@ extern "C" int rtts_infer_metrics(const float* gen, int64_t gs_b, int64_t gs_mel
                                   int n_utt, const int32_t* ids, const int64_t* starts, const int32_t* lengths, int B, int n_mel, int lm,
                                   int longest, double* partials, double* sse, double* stop_err, double* totals, void* stream) {
     RTTS_REQUIRE(L >= 0, "rtts_infer_metrics: L must not be negative (got %d)", L);
-    RTTS_REQUIRE(gen || L == 0, "rtts_infer_metrics: gen is a null pointer (and L = %d frames are to be read)", L);
-    RTTS_REQUIRE(truth, "rtts_infer_metrics: truth is a null pointer");
+    if (rtts_check_scored("rtts_infer_metrics", gen, L, truth, frame_offsets, n_utt, ids, starts, lengths, B, n_mel, truth_frames)) return -1;
     RTTS_REQUIRE(partials, "rtts_infer_metrics: partials is a null pointer");
     RTTS_REQUIRE(sse, "rtts_infer_metrics: sse is a null pointer");
     RTTS_REQUIRE(stop_err, "rtts_infer_metrics: stop_err is a null pointer");
     RTTS_REQUIRE(totals, "rtts_infer_metrics: totals is a null pointer");
-    const bool corpus = frame_offsets != nullptr, padded = starts != nullptr || lengths != nullptr;
-    RTTS_REQUIRE(corpus || padded, "rtts_infer_metrics: no truth description: give frame_offsets (+ ids), or starts + lengths");
-    RTTS_REQUIRE(!(corpus && padded), "rtts_infer_metrics: two truth descriptions: give frame_offsets (+ ids) OR starts + lengths");
-    RTTS_REQUIRE(corpus || (starts && lengths), "rtts_infer_metrics: the padded-batch description needs both starts and lengths");
-    RTTS_REQUIRE(corpus || !ids, "rtts_infer_metrics: ids belong to the corpus description (frame_offsets is a null pointer)");
-    RTTS_REQUIRE(!corpus || n_utt >= 1, "rtts_infer_metrics: n_utt must be positive (got %d)", n_utt);
-    RTTS_REQUIRE(!corpus || ids || B <= n_utt, "rtts_infer_metrics: without ids slot b is utterance b: B = %d exceeds n_utt = %d", B, n_utt);
-    RTTS_REQUIRE(B >= 1 && B <= 65535, "rtts_infer_metrics: B must be in 1..65535 (got %d)", B);
-    RTTS_REQUIRE(n_mel >= 1 && n_mel <= IM_MAX_MEL, "rtts_infer_metrics: n_mel must be in 1..%d (got %d)", IM_MAX_MEL, n_mel);
     RTTS_REQUIRE(lm >= 1, "rtts_infer_metrics: lm must be positive (got %d)", lm);
     RTTS_REQUIRE(longest >= 0 && longest <= lm, "rtts_infer_metrics: lm = %d is smaller than the longest truth, %d frames", lm, longest);
-    RTTS_REQUIRE(truth_frames >= 0, "rtts_infer_metrics: truth_frames must not be negative (got %lld)", (long long)truth_frames);
+    const RttsTruth tr = {truth_frames, frame_offsets, n_utt, ids, starts, lengths};
     const int tiles = rtts_infer_metrics_tiles(lm);
     RTTS_ENTER(stream);
     hipLaunchKernelGGL(infer_metrics_tiles_kernel, dim3((unsigned)tiles, (unsigned)B), dim3(IM_THREADS), 0, (hipStream_t)stream, gen, gs_b, gs_mel,
-                       gs_t, L, truth, ts_mel, ts_t, truth_frames, frame_offsets, n_utt, ids, starts, lengths, n_mel, tiles, partials);
+                       gs_t, L, truth, ts_mel, ts_t, tr, n_mel, tiles, partials);
     RTTS_LAUNCH_CHECK("rtts_infer_metrics (tiles)");
-    hipLaunchKernelGGL(infer_metrics_fold_kernel, dim3(1), dim3(IM_THREADS), 0, (hipStream_t)stream, partials, tiles, gen_stop, truth_frames,
-                       frame_offsets, n_utt, ids, starts, lengths, B, n_mel, lm, sse, stop_err, totals);
+    hipLaunchKernelGGL(infer_metrics_fold_kernel, dim3(1), dim3(IM_THREADS), 0, (hipStream_t)stream, partials, tiles, gen_stop, tr, B,
+                       n_mel, lm, sse, stop_err, totals);
     RTTS_LAUNCH_CHECK("rtts_infer_metrics (fold)");
     return 0;
 }

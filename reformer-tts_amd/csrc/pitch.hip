@@ -27,7 +27,7 @@
 // rtts_f0_compare.  One workgroup; wave w takes utterances w, w + 4, ...: lanes stride over the frames in f64, the 64 partial
 // rows are folded by halving distances, lane 0 stores the row.  Then the five columns are summed over the utterances in
 // ascending order by five threads.
-#include "rtts_common.h"
+#include "score_common.h"
 
 #define PITCH_THREADS 512
 #define PITCH_WAVES 8
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(F0C_THREADS) void f0_compare_kernel(const float* __
                                                                  const float* __restrict__ fb, const int64_t* __restrict__ ob, int nseg,
                                                                  double gross, double* __restrict__ table) {
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63;
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const double nan = rtts_nan64();
     for (int s = w; s < nseg; s += F0C_THREADS / 64) {
         const int64_t a0 = oa[s], b0 = ob[s];
         const int64_t ta = oa[s + 1] - a0, tb = ob[s + 1] - b0;

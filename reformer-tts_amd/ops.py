@@ -666,6 +666,45 @@ def tts_collate(mel: torch.Tensor, frame_offsets: torch.Tensor, phoneme_ids: tor
     TIMING.stop(ev, 0.0)
 
 
+def _scored_operands(who: str, gen, gen_stop, truth, *, gen_frames_last, truth_frames_last, frame_offsets, ids, starts, lengths, extra=()):
+    """The operand checks ``infer_metrics`` and ``dtw_align`` share (csrc/score_common.h holds the library's side): one truth
+    description, dtypes, one device, either layout of ``gen`` and ``truth``, (B,) index tensors -> (b, n_mel, frames, gs_mel, gs_t,
+    t_frames, ts_mel, ts_t, n_utt, dev).  ``extra``: further (name, tensor, dtype, optional) rows for the dtype and device passes."""
+    corpus, padded = frame_offsets is not None, (starts is not None or lengths is not None)
+    if corpus == padded or (padded and (starts is None or lengths is None)) or (ids is not None and not corpus):
+        raise ValueError(f"{who}: describe the truth by frame_offsets (+ ids) or by starts + lengths: exactly one of the two")
+    named = (("gen", gen, torch.float32, False), ("gen_stop", gen_stop, torch.int64, True), ("truth", truth, torch.float32, False), *extra,
+             ("frame_offsets", frame_offsets, torch.int64, True), ("ids", ids, torch.int32, True), ("starts", starts, torch.int64, True),
+             ("lengths", lengths, torch.int32, True))
+    for name, t, dt, optional in named:
+        if t is None and optional:
+            continue
+        if not (torch.is_tensor(t) and t.dtype == dt):
+            raise ValueError(f"{who}: {name} must be a {dt} tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+    dev = gen.device
+    for name, t, dt, optional in named:
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise _lib.RttsError(f"{who} runs on the GPU only: {name} must be a CUDA {dt} tensor on {dev} (got one on {t.device})")
+    if gen.dim() != 3 or truth.dim() != 2:
+        raise ValueError(f"{who}: gen must be 3-D and truth 2-D (got {tuple(gen.shape)} and {tuple(truth.shape)})")
+    b = gen.shape[0]
+    n_mel, frames, gs_mel, gs_t = (gen.shape[1], gen.shape[2], gen.stride(1), gen.stride(2)) if gen_frames_last else \
+        (gen.shape[2], gen.shape[1], gen.stride(2), gen.stride(1))
+    t_mel, t_frames, ts_mel, ts_t = (truth.shape[0], truth.shape[1], truth.stride(0), truth.stride(1)) if truth_frames_last else \
+        (truth.shape[1], truth.shape[0], truth.stride(1), truth.stride(0))
+    if t_mel != n_mel:
+        raise ValueError(f"{who}: gen has {n_mel} mel channels, truth {t_mel}")
+    for name, t in (("gen_stop", gen_stop), ("ids", ids), ("starts", starts), ("lengths", lengths)):
+        if t is not None and not (tuple(t.shape) == (b,) and t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be contiguous of shape ({b},), got {tuple(t.shape)}")
+    n_utt = 0
+    if corpus:
+        n_utt = frame_offsets.numel() - 1
+        if not (frame_offsets.dim() == 1 and frame_offsets.is_contiguous() and n_utt >= 1):
+            raise ValueError(f"{who}: frame_offsets must be contiguous of shape (n + 1,), n >= 1")
+    return b, n_mel, frames, gs_mel, gs_t, t_frames, ts_mel, ts_t, n_utt, dev
+
+
 def infer_metrics(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: torch.Tensor, lm: int, *, gen_frames_last: bool = True,
                   truth_frames_last: bool = True, frame_offsets: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None,
                   starts: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None, longest: int = 0):
@@ -677,38 +716,9 @@ def infer_metrics(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: to
     DEVICE.  ``lm``: the batch's longest truth, a host int; ``longest``: the longest length where the host knows it (checked
     against ``lm``), else 0.  -> (sse f64 (B,), stop_err f64 (B,), totals f64 (2,) = [Σ sse / (B n_mel lm), mean stop_err]);
     ``gen_stop=None`` leaves stop_err and totals[1] zero.  One call on the current stream, nothing read back: capturable."""
-    corpus, padded = frame_offsets is not None, (starts is not None or lengths is not None)
-    if corpus == padded or (padded and (starts is None or lengths is None)) or (ids is not None and not corpus):
-        raise ValueError("infer_metrics: describe the truth by frame_offsets (+ ids) or by starts + lengths: exactly one of the two")
-    named = (("gen", gen, torch.float32, False), ("gen_stop", gen_stop, torch.int64, True), ("truth", truth, torch.float32, False),
-             ("frame_offsets", frame_offsets, torch.int64, True), ("ids", ids, torch.int32, True), ("starts", starts, torch.int64, True),
-             ("lengths", lengths, torch.int32, True))
-    for name, t, dt, optional in named:
-        if t is None and optional:
-            continue
-        if not (torch.is_tensor(t) and t.dtype == dt):
-            raise ValueError(f"infer_metrics: {name} must be a {dt} tensor (got {getattr(t, 'dtype', type(t).__name__)})")
-    dev = gen.device
-    for name, t, dt, optional in named:
-        if t is not None and not (t.is_cuda and t.device == dev):
-            raise _lib.RttsError(f"infer_metrics runs on the GPU only: {name} must be a CUDA {dt} tensor on {dev} (got one on {t.device})")
-    if gen.dim() != 3 or truth.dim() != 2:
-        raise ValueError(f"infer_metrics: gen must be 3-D and truth 2-D (got {tuple(gen.shape)} and {tuple(truth.shape)})")
-    b = gen.shape[0]
-    n_mel, frames, gs_mel, gs_t = (gen.shape[1], gen.shape[2], gen.stride(1), gen.stride(2)) if gen_frames_last else \
-        (gen.shape[2], gen.shape[1], gen.stride(2), gen.stride(1))
-    t_mel, t_frames, ts_mel, ts_t = (truth.shape[0], truth.shape[1], truth.stride(0), truth.stride(1)) if truth_frames_last else \
-        (truth.shape[1], truth.shape[0], truth.stride(1), truth.stride(0))
-    if t_mel != n_mel:
-        raise ValueError(f"infer_metrics: gen has {n_mel} mel channels, truth {t_mel}")
-    for name, t in (("gen_stop", gen_stop), ("ids", ids), ("starts", starts), ("lengths", lengths)):
-        if t is not None and not (tuple(t.shape) == (b,) and t.is_contiguous()):
-            raise ValueError(f"infer_metrics: {name} must be contiguous of shape ({b},), got {tuple(t.shape)}")
-    n_utt = 0
-    if corpus:
-        n_utt = frame_offsets.numel() - 1
-        if not (frame_offsets.dim() == 1 and frame_offsets.is_contiguous() and n_utt >= 1):
-            raise ValueError("infer_metrics: frame_offsets must be contiguous of shape (n + 1,), n >= 1")
+    b, n_mel, frames, gs_mel, gs_t, t_frames, ts_mel, ts_t, n_utt, dev = _scored_operands(
+        "infer_metrics", gen, gen_stop, truth, gen_frames_last=gen_frames_last, truth_frames_last=truth_frames_last, frame_offsets=frame_offsets,
+        ids=ids, starts=starts, lengths=lengths)
     lm = int(lm)
     tiles = _lib.load().rtts_infer_metrics_tiles(lm)
     out = torch.empty(2 * b + 2 + b * tiles, dtype=torch.float64, device=dev)
@@ -744,43 +754,14 @@ def dtw_align(gen: torch.Tensor, gen_stop: Optional[torch.Tensor], truth: torch.
     [mean_b cost/steps, Σ cost / Σ steps]).  A slot that cannot be scored (no generated frame, a bad description, a non-finite
     compared value) has cost NaN and steps 0, and makes the totals NaN.  One call on the current stream, nothing read back:
     capturable.  ``_phases`` / ``_state``: scripts/dtw_bench.py times the four kernels one by one on a previous call's buffers."""
-    corpus, padded = frame_offsets is not None, (starts is not None or lengths is not None)
-    if corpus == padded or (padded and (starts is None or lengths is None)) or (ids is not None and not corpus):
-        raise ValueError("dtw_align: describe the truth by frame_offsets (+ ids) or by starts + lengths: exactly one of the two")
-    named = (("gen", gen, torch.float32, False), ("gen_stop", gen_stop, torch.int64, True), ("truth", truth, torch.float32, False),
-             ("basis", basis, torch.float32, True), ("frame_offsets", frame_offsets, torch.int64, True), ("ids", ids, torch.int32, True),
-             ("starts", starts, torch.int64, True), ("lengths", lengths, torch.int32, True))
-    for name, t, dt, optional in named:
-        if t is None and optional:
-            continue
-        if not (torch.is_tensor(t) and t.dtype == dt):
-            raise ValueError(f"dtw_align: {name} must be a {dt} tensor (got {getattr(t, 'dtype', type(t).__name__)})")
-    dev = gen.device
-    for name, t, dt, optional in named:
-        if t is not None and not (t.is_cuda and t.device == dev):
-            raise _lib.RttsError(f"dtw_align runs on the GPU only: {name} must be a CUDA {dt} tensor on {dev} (got one on {t.device})")
-    if gen.dim() != 3 or truth.dim() != 2:
-        raise ValueError(f"dtw_align: gen must be 3-D and truth 2-D (got {tuple(gen.shape)} and {tuple(truth.shape)})")
-    b = gen.shape[0]
-    n_mel, frames, gs_mel, gs_t = (gen.shape[1], gen.shape[2], gen.stride(1), gen.stride(2)) if gen_frames_last else \
-        (gen.shape[2], gen.shape[1], gen.stride(2), gen.stride(1))
-    t_mel, t_frames, ts_mel, ts_t = (truth.shape[0], truth.shape[1], truth.stride(0), truth.stride(1)) if truth_frames_last else \
-        (truth.shape[1], truth.shape[0], truth.stride(1), truth.stride(0))
-    if t_mel != n_mel:
-        raise ValueError(f"dtw_align: gen has {n_mel} mel channels, truth {t_mel}")
+    b, n_mel, frames, gs_mel, gs_t, t_frames, ts_mel, ts_t, n_utt, dev = _scored_operands(
+        "dtw_align", gen, gen_stop, truth, gen_frames_last=gen_frames_last, truth_frames_last=truth_frames_last, frame_offsets=frame_offsets,
+        ids=ids, starts=starts, lengths=lengths, extra=(("basis", basis, torch.float32, True),))
     n_proj = n_mel
     if basis is not None:
         if not (basis.dim() == 2 and basis.shape[1] == n_mel and basis.shape[0] >= 1 and basis.is_contiguous()):
             raise ValueError(f"dtw_align: basis must be contiguous of shape (n_proj, {n_mel}), got {tuple(basis.shape)}")
         n_proj = basis.shape[0]
-    for name, t in (("gen_stop", gen_stop), ("ids", ids), ("starts", starts), ("lengths", lengths)):
-        if t is not None and not (tuple(t.shape) == (b,) and t.is_contiguous()):
-            raise ValueError(f"dtw_align: {name} must be contiguous of shape ({b},), got {tuple(t.shape)}")
-    n_utt = 0
-    if corpus:
-        n_utt = frame_offsets.numel() - 1
-        if not (frame_offsets.dim() == 1 and frame_offsets.is_contiguous() and n_utt >= 1):
-            raise ValueError("dtw_align: frame_offsets must be contiguous of shape (n + 1,), n >= 1")
     lm = int(lm)
     lib = _lib.load()
     most = int(lib.rtts_dtw_max_frames())

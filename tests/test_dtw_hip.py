@@ -281,6 +281,33 @@ def test_slots_that_cannot_be_scored_are_nan(gpu, ragged):
         assert np.isnan(cost[2]) and steps[2] == 0 and np.all(np.isnan(totals)) and np.array_equal(cost[:2], base[0][:2])
 
 
+def test_a_zero_length_truth_scores_nothing_or_cannot_be_scored(gpu):
+    """The one place where the two users of the shared truth pick (csrc/score_common.h) differ: a slot whose truth has no frame is
+    a valid slot of 0 frames for infer_metrics (sse 0, stop_err = |gen_stop - (0 - 1)|) and an unscorable one for dtw_align
+    (cost NaN, steps 0, totals NaN).  Either way the other slots keep their bits."""
+    from reformer_tts_amd import ops
+    rng = np.random.default_rng(31)
+    b, n_mel, frames, lm = 3, 7, 40, 50
+    gens = [(-5 + 2 * rng.standard_normal((n_mel, frames))).astype(np.float32) for _ in range(b)]
+    truths = [(-5 + 2 * rng.standard_normal((n_mel, m))).astype(np.float32) for m in (33, 21, 45)]
+    pk = _pack(gens, truths, gpu, frames=frames, lm=lm)
+    pk["stop"] = torch.tensor([40, 17, 38], dtype=torch.int64).to(gpu)
+    empty = dict(pk, lengths=pk["lengths"].clone())
+    empty["lengths"][1] = 0
+
+    def metrics(p):
+        return [t.cpu().numpy() for t in ops.infer_metrics(p["gen"], p["stop"], p["truth"], p["lm"], starts=p["starts"], lengths=p["lengths"])]
+
+    (sse0, err0, tot0), (sse1, err1, tot1) = metrics(pk), metrics(empty)
+    assert np.all(np.isfinite(sse0)) and sse0[1] > 0.0 and np.all(np.isfinite(tot0))
+    assert sse1[1] == 0.0 and err1[1] == 17 + 1 and np.all(np.isfinite(tot1))
+    assert _bits([sse1[[0, 2]], err1[[0, 2]]]) == _bits([sse0[[0, 2]], err0[[0, 2]]])
+    (cost0, steps0, dtot0), (cost1, steps1, dtot1) = _run(pk), _run(empty)
+    assert np.all(np.isfinite(cost0)) and np.all(steps0 > 0) and np.all(np.isfinite(dtot0))
+    assert np.isnan(cost1[1]) and steps1[1] == 0 and np.all(np.isnan(dtot1))
+    assert _bits([cost1[[0, 2]], steps1[[0, 2]]]) == _bits([cost0[[0, 2]], steps0[[0, 2]]])
+
+
 def test_sizes_past_the_limit_are_refused_by_name(gpu):
     from reformer_tts_amd import _lib, ops
     most = ops.dtw_max_frames()
