@@ -18,24 +18,15 @@
 // The position is read on the device, so ONE captured launch serves every frame; p outside [0, cap) writes nothing to the cache
 // and sets every o to NaN.
 #include "rtts_common.h"
+#include "attn_tile.h"   // AT_SELF
 #include <float.h>
 
 #define DA_TILE 64
 #define DA_THREADS 256
 #define DA_MAX_SPLITS 64
 #define DA_MAX_T 4096
-#define DA_SELF (-5e4f)
 #define DA_HDR 4                       // floats in front of a partial's accumulators: running maximum, normaliser, two unused
 #define DA_NAN2 0x7fc07fc0u            // two bf16 NaN
-
-__device__ __forceinline__ void da_unpack8(const uint4 t, float (&f)[8]) {
-    const uint32_t u[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        f[2 * j] = __uint_as_float(u[j] << 16);
-        f[2 * j + 1] = __uint_as_float(u[j] & 0xffff0000u);
-    }
-}
 
 // columns c0, c0 + 1 of one (batch, head): `n` partials (maximum, normaliser, accumulators) at `part`, `stride` floats apart, folded
 // in index order
@@ -94,7 +85,7 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_kernel(const bf16_t* _
             *reinterpret_cast<const uint4*>(q + (size_t)b * ld_q + off);
     }
     float qf[8];
-    da_unpack8(*reinterpret_cast<const uint4*>(qrow + li * 8), qf);
+    rtts_unpack8(*reinterpret_cast<const uint4*>(qrow + li * 8), qf);
     const float scale = DH == 64 ? 0.125f : 0.08838834764831845f;
 
     float m = -FLT_MAX, l = 0.f, acc[8] = {};
@@ -115,8 +106,8 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_kernel(const bf16_t* _
 #pragma unroll
         for (int i = 0; i < NPASS; ++i) {
             float kf[8], vf[8];
-            da_unpack8(kk[i], kf);
-            da_unpack8(vv[i], vf);
+            rtts_unpack8(kk[i], kf);
+            rtts_unpack8(vv[i], vf);
             float dot = 0.f, ss = 0.f;
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
@@ -153,8 +144,8 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_kernel(const bf16_t* _
     da_fold(part, PS, KPP, c0, M, L, a0, a1);
     if (SELF && s == 0) {                        // position p itself: logit -5e4, value from the new row
         const uint32_t u = *reinterpret_cast<const uint32_t*>(q + (size_t)b * ld_q + voff + (size_t)h * DH + c0);
-        const float mn = fmaxf(M, DA_SELF);
-        const float alpha = __expf(M - mn), pr = __expf(DA_SELF - mn);
+        const float mn = fmaxf(M, AT_SELF);
+        const float alpha = __expf(M - mn), pr = __expf(AT_SELF - mn);
         L = __builtin_fmaf(L, alpha, pr);
         a0 = __builtin_fmaf(a0, alpha, pr * __uint_as_float(u << 16));
         a1 = __builtin_fmaf(a1, alpha, pr * __uint_as_float(u & 0xffff0000u));

@@ -21,50 +21,11 @@
 // The backward kernels are held to two waves per SIMD (a few spilled registers in the dropout and causal key-pass variants), and
 // a causal grid hands out the long blocks of a (batch, head) first: together 261 -> 182 us at B 12, H 8, T 1024.
 #include "rtts_common.h"
+#include "attn_tile.h"   // the swizzled [row][128 B] images (at_off) and the row staging of the epilogues (at_store_rows)
 #include <float.h>
 
 #define FA_TILE 64
 #define FA_MAX_T 4096
-#define FA_SELF (-5e4f)
-
-typedef __attribute__((ext_vector_type(8))) short fa_short8;
-
-// xattn.hip's images (bank arithmetic in lsh_attn_bwd.hip; tests/test_lds_swizzle_model.py pins the derivation): rows of 128 B,
-// 16-byte pieces XOR-swizzled by the row; ds_read_b128 of a piece from 16 rows and ds_read_b64_tr_b16 of 4 rows x 64 B conflict free
-__device__ __forceinline__ int fa_sw(int row) { return ((row >> 1) & 3) | ((((row >> 3) ^ (row >> 1)) & 1) << 2); }
-__device__ __forceinline__ int fa_off(int row, int piece) { return row * 128 + ((piece ^ fa_sw(row)) << 4); }
-__device__ __forceinline__ bf16x8 fa_tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p0);
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p1);
-    const fa_short8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, both);
-}
-// row staging of the epilogues (xattn.hip's xa_stg_w / xa_stg_r): a wave leaves 32 full 128-byte rows through a private 4 KB image
-__device__ __forceinline__ int fa_stg_w(int r, int piece, int hh) { return r * 128 + ((piece ^ (r & 7)) << 4) + ((hh ^ ((r >> 3) & 1)) << 3); }
-__device__ __forceinline__ int fa_stg_r(int i, int srow, int spiece) { return (i * 8 + srow) * 128 + ((spiece ^ srow) << 4); }
-// acc[dt][4 g + j] of lane (r, hh) = element (row r, dh = 32 dt + 8 g + 4 hh + j), times `mul` -> 32 rows of 64 bf16 at dst + row * ld
-__device__ __forceinline__ void fa_store_rows(unsigned char* stg, const f32x16 (&acc)[2], float mul, bf16_t* dst, int64_t ld, int lane) {
-    const int r = lane & 31, hh = lane >> 5, srow = lane >> 3, spiece = lane & 7;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint2 pk;
-            pk.x = pack_bf16x2(acc[dt][4 * g] * mul, acc[dt][4 * g + 1] * mul);
-            pk.y = pack_bf16x2(acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
-            *reinterpret_cast<uint2*>(stg + fa_stg_w(r, dt * 4 + g, hh)) = pk;
-        }
-    __builtin_amdgcn_wave_barrier();
-    uint4 rowv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint4 v = *reinterpret_cast<const uint4*>(stg + fa_stg_r(i, srow, spiece));
-        rowv[i] = (i & 1) ? uint4{v.z, v.w, v.x, v.y} : v;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rtts_store16_out(dst + (size_t)(i * 8 + srow) * ld + spiece * 8, rowv[i]);
-    __builtin_amdgcn_wave_barrier();
-}
 
 // 64 rows of 64 bf16 (row stride ld) -> a swizzled [64][128 B] image, by LDS-DMA: one wave-instruction fills 8 rows in lane order,
 // the swizzle goes on the source side.  128 threads.
@@ -73,7 +34,7 @@ __device__ __forceinline__ void fa_stage(unsigned char* img, const bf16_t* base,
     for (int it = 0; it < 4; ++it) {
         const int rowb = it * 16 + wave * 8;
         const int row = rowb + (lane >> 3);
-        const int lp = (lane & 7) ^ fa_sw(row);
+        const int lp = (lane & 7) ^ at_sw(row);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + (size_t)row * ld + lp * 8),
                                          (RTTS_LDS void*)(img + rowb * 128), 16, 0, 0);
     }
@@ -148,7 +109,7 @@ __global__ __launch_bounds__(128) void full_attn_fwd_kernel(const bf16_t* __rest
             f32x16 acc = {0};
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + fa_off(kt * 32 + r, ks * 2 + hh));
+                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + at_off(kt * 32 + r, ks * 2 + hh));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
             }
             s[kt] = acc;
@@ -168,7 +129,7 @@ __global__ __launch_bounds__(128) void full_attn_fwd_kernel(const bf16_t* __rest
                     // selects, not branches: (a) self, then (b) padding on either side and (c) the future overwrite it
                     const int live = qv & vv[j] & (CAUSAL ? (int)(key <= qrow) : 1);
                     float x = s[kt][4 * g + j] * cc[j];
-                    x = key == qrow ? FA_SELF : x;
+                    x = key == qrow ? AT_SELF : x;
                     x = live ? x : -FLT_MAX;
                     s[kt][4 * g + j] = x;
                     m = fmaxf(m, x);
@@ -211,16 +172,16 @@ __global__ __launch_bounds__(128) void full_attn_fwd_kernel(const bf16_t* __rest
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     const int blk = (kt * 32 + 16 * s2) * 128;
-                    const int t0 = fa_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
-                    const int t1 = fa_off(4 * hh + trq, (dt ^ 1) * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);   // row + 8: sw flips bit 2
-                    const bf16x8 vf = fa_tr_frag(Vs + blk + t0, Vs + blk + 8 * 128 + t1);
+                    const int t0 = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+                    const int t1 = at_off(4 * hh + trq, (dt ^ 1) * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);   // row + 8: sw flips bit 2
+                    const bf16x8 vf = rtts_tr_frag(Vs + blk + t0, Vs + blk + 8 * 128 + t1);
                     oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[dt], 0, 0, 0);
                 }
             }
     }
     const float inv_l = 1.f / l_run;
     __syncthreads();                 // the K image becomes the waves' row staging (4 KB each)
-    fa_store_rows(Ks + wave * 4096, oacc, inv_l, o + ((size_t)b * T + qb * FA_TILE + wave * 32) * ld_o + (size_t)h * 64, ld_o, lane);
+    at_store_rows(Ks + wave * 4096, oacc, inv_l, o + ((size_t)b * T + qb * FA_TILE + wave * 32) * ld_o + (size_t)h * 64, ld_o, lane);
     if (hh == 0) lse[(size_t)bh * T + qrow] = (m_run == -FLT_MAX) ? -FLT_MAX : m_run + logf(l_run);
 }
 
@@ -279,9 +240,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void f
     const int trq = (lane & 15) >> 2, trp = lane & 3, trc = (lane >> 4) & 1;
     int fro[4], tro[2];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fro[ks] = fa_off(r, ks * 2 + hh);
+    for (int ks = 0; ks < 4; ++ks) fro[ks] = at_off(r, ks * 2 + hh);
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt) tro[dt] = fa_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+    for (int dt = 0; dt < 2; ++dt) tro[dt] = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
 
     // causal: a key block meets the queries from its own tile on (and earlier tiles only where they hold a masked query, whose
     // uniform row feeds dV of every key); a query block meets the keys up to its own tile
@@ -344,7 +305,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void f
                     // with nothing else) and no gradient; a masked query: uniform over all T keys, no logit depends on qk (its
                     // lse = -FLT_MAX would rebuild P = inf or 1: whatever the exp gives is discarded by the select)
                     const int live = vk & (CAUSAL ? (int)(kj <= qi) : 1);
-                    const float sl = qi == kj ? FA_SELF : sacc[i] * c_j;
+                    const float sl = qi == kj ? AT_SELF : sacc[i] * c_j;
                     float p = __expf(sl - l_i);
                     p = live ? p : 0.f;
                     float dsv = (live & (int)(qi != kj)) ? p * (pacc[i] * keep - d_i) : 0.f;
@@ -364,15 +325,15 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void f
                     const bf16x8 pb = cvt_bf16x8(pq[0], pq[1], pq[2], pq[3], pq[4], pq[5], pq[6], pq[7]);
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt) {
-                        const bf16x8 dotf = fa_tr_frag(X2 + blk + tro[dt], X2 + blk + 8 * 128 + tro[dt ^ 1]);
-                        const bf16x8 qtf = fa_tr_frag(X1 + blk + tro[dt], X1 + blk + 8 * 128 + tro[dt ^ 1]);
+                        const bf16x8 dotf = rtts_tr_frag(X2 + blk + tro[dt], X2 + blk + 8 * 128 + tro[dt ^ 1]);
+                        const bf16x8 qtf = rtts_tr_frag(X1 + blk + tro[dt], X1 + blk + 8 * 128 + tro[dt ^ 1]);
                         acc1[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dotf, pb, acc1[dt], 0, 0, 0);
                         acc2[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qtf, db, acc2[dt], 0, 0, 0);
                     }
                 } else {
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt) {
-                        const bf16x8 ktf = fa_tr_frag(X1 + blk + tro[dt], X1 + blk + 8 * 128 + tro[dt ^ 1]);
+                        const bf16x8 ktf = rtts_tr_frag(X1 + blk + tro[dt], X1 + blk + 8 * 128 + tro[dt ^ 1]);
                         acc1[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ktf, db, acc1[dt], 0, 0, 0);
                     }
                 }
@@ -428,7 +389,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void f
             }
     }
     __syncthreads();                 // the first image becomes the waves' row staging (4 KB each)
-    fa_store_rows(X1 + wave * 4096, acc1, 1.f, dst + ((size_t)b * T + ob * FA_TILE + wave * 32) * ld_d + (size_t)h * 64, ld_d, lane);
+    at_store_rows(X1 + wave * 4096, acc1, 1.f, dst + ((size_t)b * T + ob * FA_TILE + wave * 32) * ld_d + (size_t)h * 64, ld_d, lane);
 }
 
 // ------------------------------------------------------------------------------ entry points

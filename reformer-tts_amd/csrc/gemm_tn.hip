@@ -27,15 +27,6 @@
 #endif                 // transposed read (ds_read_b64_tr_b16 is served in two 32-lane groups over 64 banks) hit 64 distinct
                        // banks; 32 B of pad left them 2-way conflicted (130.6 -> 127.7 us per decoder-layer group)
 
-typedef __attribute__((ext_vector_type(8))) short gt_short8;
-
-__device__ __forceinline__ bf16x8 gt_tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p0);
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p1);
-    const gt_short8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, both);
-}
-
 struct GtProb {
     const bf16_t* a;
     const bf16_t* b;
@@ -147,11 +138,11 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_tn_kernel(const GtGroup grp
         const int mr_ = (ks_) * 16 + 8 * hh + trq;                                              \
         _Pragma("unroll") for (int t = 0; t < TN; ++t) {                                        \
             const int ca_ = (wn * 32 * TN + t * 32 + 16 * trc + 4 * trp) * 2;                   \
-            AF[t] = gt_tr_frag(Ab + mr_ * ROWA + ca_, Ab + (mr_ + 4) * ROWA + ca_);             \
+            AF[t] = rtts_tr_frag(Ab + mr_ * ROWA + ca_, Ab + (mr_ + 4) * ROWA + ca_);             \
         }                                                                                       \
         _Pragma("unroll") for (int t = 0; t < TK; ++t) {                                        \
             const int cb_ = (wk * 32 * TK + t * 32 + 16 * trc + 4 * trp) * 2;                   \
-            BF[t] = gt_tr_frag(Bb + mr_ * ROWB + cb_, Bb + (mr_ + 4) * ROWB + cb_);             \
+            BF[t] = rtts_tr_frag(Bb + mr_ * ROWB + cb_, Bb + (mr_ + 4) * ROWB + cb_);             \
         }                                                                                       \
     } while (0)
 #define GT_MFMAS(AF, BF)                                                                        \
@@ -344,15 +335,15 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_tn_ring_kernel(const GtGrou
         bf16x8 af0[TN], bf0[TK], af1[TN], bf1[TK];
 #pragma unroll
         for (int t = 0; t < TN; ++t) {
-            const gt_short8 f0 = {al[0][t][0], al[0][t][1], al[0][t][2], al[0][t][3], ah[0][t][0], ah[0][t][1], ah[0][t][2], ah[0][t][3]};
-            const gt_short8 f1 = {al[1][t][0], al[1][t][1], al[1][t][2], al[1][t][3], ah[1][t][0], ah[1][t][1], ah[1][t][2], ah[1][t][3]};
+            const short8v f0 = {al[0][t][0], al[0][t][1], al[0][t][2], al[0][t][3], ah[0][t][0], ah[0][t][1], ah[0][t][2], ah[0][t][3]};
+            const short8v f1 = {al[1][t][0], al[1][t][1], al[1][t][2], al[1][t][3], ah[1][t][0], ah[1][t][1], ah[1][t][2], ah[1][t][3]};
             af0[t] = __builtin_bit_cast(bf16x8, f0);
             af1[t] = __builtin_bit_cast(bf16x8, f1);
         }
 #pragma unroll
         for (int t = 0; t < TK; ++t) {
-            const gt_short8 f0 = {bl[0][t][0], bl[0][t][1], bl[0][t][2], bl[0][t][3], bh[0][t][0], bh[0][t][1], bh[0][t][2], bh[0][t][3]};
-            const gt_short8 f1 = {bl[1][t][0], bl[1][t][1], bl[1][t][2], bl[1][t][3], bh[1][t][0], bh[1][t][1], bh[1][t][2], bh[1][t][3]};
+            const short8v f0 = {bl[0][t][0], bl[0][t][1], bl[0][t][2], bl[0][t][3], bh[0][t][0], bh[0][t][1], bh[0][t][2], bh[0][t][3]};
+            const short8v f1 = {bl[1][t][0], bl[1][t][1], bl[1][t][2], bl[1][t][3], bh[1][t][0], bh[1][t][1], bh[1][t][2], bh[1][t][3]};
             bf0[t] = __builtin_bit_cast(bf16x8, f0);
             bf1[t] = __builtin_bit_cast(bf16x8, f1);
         }

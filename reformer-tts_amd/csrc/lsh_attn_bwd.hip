@@ -18,10 +18,11 @@
 // rows, query role + key role added on chip; slot 1: key role of the looked-back chunk's rows), every row of every
 // slot exactly once, and rtts_lsh_bwd_reduce sums slots and rounds -- deterministic, no atomics.
 #include "rtts_common.h"
+#include "attn_tile.h"   // the LDS images (K/Q and dout rows, dS'^T) and the row staging of the epilogues, with their bank arithmetic
 #include <float.h>
 
 #define AB_DH 64
-#define AB_ROWB 128   // row staging: unpadded 128-byte rows, swizzled (ab_stg_w / ab_stg_r)
+#define AB_ROWB 128   // row staging: unpadded 128-byte rows, swizzled (at_stg_w / at_stg_r)
 #ifndef AB_SPLIT_EPI
 #define AB_SPLIT_EPI 1   // walking kernel: a step's row stores run beside the next step's main loop (0: round 3's form, for A/B runs)
 #endif
@@ -31,8 +32,6 @@
 #ifndef AB_UNROLL
 #define AB_UNROLL 4   // query-tile loop fully unrolled: the tail of tile i (dV, G MFMAs, dS stores) overlaps the head of tile i+1; scripts/phase_probe.py --unroll N measures others
 #endif
-
-typedef __attribute__((ext_vector_type(8))) short short8v;
 
 // Phase probe (scripts/phase_probe.py builds a private copy of this file with -DAB_PHASE_TIMING): wave 0 of every
 // workgroup records the shader clock at the phase boundaries.  Never defined in the product build.
@@ -45,42 +44,6 @@ extern "C" int rtts_debug_ab_phases(void* dst) { return (int)hipMemcpyFromSymbol
 #define AB_STAMP(i) do { } while (0)
 #define AB_WSTAMP(i, w) do { } while (0)
 #endif
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p0);
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p1);
-    const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, both);
-}
-
-// ---- LDS images ---------------------------------------------------------------------------------------------------
-// K/Q and dout images: [row][128 B], no padding; the eight 16-byte pieces of a row are XOR-swizzled with
-//     sw(row) = row bits (2,1) | (row bit 3 ^ row bit 1) << 2
-// so that BOTH access shapes are bank-conflict free (64 banks x 4 B): ds_read_b128 of one piece from 16 rows (the MFMA
-// A/B fragments) and ds_read_b64_tr_b16 of 4 consecutive rows x 64 B (the transposed fragments).  With 144-byte padded
-// rows the transposed reads were 2-way conflicted (rows j and j+2 overlap in 8 banks).
-__device__ __forceinline__ int ab_sw(int row) { return ((row >> 1) & 3) | ((((row >> 3) ^ (row >> 1)) & 1) << 2); }
-__device__ __forceinline__ int ab_off(int row, int piece) { return row * 128 + ((piece ^ ab_sw(row)) << 4); }
-// dS'^T image: [key][BS queries] bf16, no padding, 8-byte granules (4 queries) XOR-swizzled by the key so that the
-// ds_write_b64 of 16 consecutive keys (banks mod 32) and the transposed read of 4 consecutive keys x 64 B (banks mod 64)
-// are both conflict free (the padded image was 4-way conflicted on the read side: the dQ phase ran at LDS speed / 4).
-template <int BS>
-__device__ __forceinline__ int ab_ds_off(int key, int gran) {
-    const int k0 = key & 1, k1 = (key >> 1) & 1, k2 = (key >> 2) & 1, k3 = (key >> 3) & 1;
-    if (BS == 128) return key * 256 + ((gran ^ ((k1 << 4) | (k0 << 3) | (k1 << 2) | (k2 << 1) | k3)) << 3);
-    return key * 128 + ((gran ^ ((k1 << 3) | (k0 << 2) | (k2 << 1) | k3)) << 3);
-}
-
-// Row staging of the epilogues: [32 keys][128 B].  The accumulators hold a key per lane, so lane (r, hh) writes the 8 bytes
-// (16-byte piece p, half hh) of row r with ds_write_b64 (16 consecutive lanes = 16 rows per LDS cycle, banks mod 32: the
-// 16 rows must land on the 16 distinct 8-byte slots of a 128-byte window) and the rows leave as 16-byte pieces read with
-// ds_read_b128 (lane = (row & 7, piece), groups of 16 lanes = 4 rows x 4 pieces, banks mod 64: rows of equal parity must
-// hold different pieces).  piece ^ (row & 7) serves both; the half is swapped in rows with bit 3 set, which the reader
-// undoes for free: bit 3 of its row is the compile-time index of the read.  (The padded [32][144 B] staging of rounds 1-3 was
-// 2-way conflicted on both sides: 10.9 % of this kernel's LDS cycles; tests/test_lds_swizzle_model.py holds the model.)
-__device__ __forceinline__ int ab_stg_w(int r, int piece, int hh) { return r * 128 + ((piece ^ (r & 7)) << 4) + ((hh ^ ((r >> 3) & 1)) << 3); }
-__device__ __forceinline__ int ab_stg_r(int i, int srow, int spiece) { return (i * 8 + srow) * 128 + ((spiece ^ srow) << 4); }
-__device__ __forceinline__ uint4 ab_stg_fix(int i, const uint4 v) { return (i & 1) ? uint4{v.z, v.w, v.x, v.y} : v; }
 
 // AB_KT2 = 32-key tiles owned by one wave.  1: 8 waves per 128-key chunk pair, two waves per SIMD (<= 256 registers each).
 // 2: 4 waves, ONE wave per SIMD with the whole 512-entry register file: a query tile's fragments, per-query words and
@@ -185,7 +148,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
         const int rowb = it * (NTHR / 8) + wave * 8;            // wave-uniform: first row of this instruction
-        const int lp = (lane & 7) ^ ab_sw(rowb + (lane >> 3));
+        const int lp = (lane & 7) ^ at_sw(rowb + (lane >> 3));
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qbase + (size_t)trow[it] * ld + lp * 8),
                                          (RTTS_LDS void*)(Ks + rowb * 128), 16, 0, 0);
         if (it < ITERS / 2)
@@ -238,7 +201,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
     // byte offsets of the A/B fragment pieces (ks*2+hh) of row r inside any 32-row block of a swizzled image
     int fro[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fro[ks] = ab_off(r, ks * 2 + hh);
+    for (int ks = 0; ks < 4; ++ks) fro[ks] = at_off(r, ks * 2 + hh);
     bf16x8 kf[KT2][4];
     float ksc[KT2];
     int kpk[KT2];
@@ -265,14 +228,14 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
     // sw(row + 8) = sw(row) ^ 4 and dt toggles the same piece bit, so the second read of tile dt sits at tro[dt ^ 1] + 8 rows
     int tro[2];
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt) tro[dt] = ab_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+    for (int dt = 0; dt < 2; ++dt) tro[dt] = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
     // dS'^T store offsets of this lane's key rows at query tile 0; tile qt is granule + 8*qt = byte offset ^ (qt << 6)
     // (the row base is a multiple of 128 resp. 256 bytes, so bits 6.. of the offset belong to the granule index alone)
     int dso[KT2][4];
 #pragma unroll
     for (int k2 = 0; k2 < KT2; ++k2)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) dso[k2][g] = ab_ds_off<BS>(myrow[k2], 2 * g + hh);
+        for (int g = 0; g < 4; ++g) dso[k2][g] = at_ds_off<BS>(myrow[k2], 2 * g + hh);
     const bool own_tile = wave * KT2 < BS / 32;  // wave-uniform (SGPR); the KT2 tiles of a wave sit on the same side
     const bool wrap = (cprev / nb) != (c / nb);
 #if defined(AB_STAGGER) && AB_STAGGER > 0
@@ -318,8 +281,8 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     const int blk = (qt * 32 + 16 * s2) * 128;
-                    qtf[s2][dt] = tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
-                    dotf[s2][dt] = tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
+                    qtf[s2][dt] = rtts_tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
+                    dotf[s2][dt] = rtts_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
                 }
         }
 #pragma unroll
@@ -364,7 +327,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
                         const bool self = pv[j] == mypos[k2];
                         const bool dead = kpk[k2] > ev[j];
                         float x = sacc[i] * ksc2;
-                        x = self ? (-5e4f * 1.4426950408889634f) : x;
+                        x = self ? (AT_SELF * 1.4426950408889634f) : x;
                         float p = __builtin_amdgcn_exp2f(x - lv[j]);
                         p = (dead && !self) ? 0.f : p;
                         pp[i] = p;
@@ -396,8 +359,8 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
 #pragma unroll
                     for (int dt = 0; dt < 2; ++dt) {
                         const int blk = (qt * 32 + 16 * s2) * 128;
-                        qtf[s2][dt] = tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
-                        dotf[s2][dt] = tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
+                        qtf[s2][dt] = rtts_tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
+                        dotf[s2][dt] = rtts_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
                     }
             }
 #pragma unroll
@@ -447,12 +410,12 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
                 uint2 pk;
                 pk.x = pack_bf16x2(dvacc[k2][dt][4 * g], dvacc[k2][dt][4 * g + 1]);
                 pk.y = pack_bf16x2(dvacc[k2][dt][4 * g + 2], dvacc[k2][dt][4 * g + 3]);
-                *reinterpret_cast<uint2*>(stg + ab_stg_w(r, dt * 4 + g, hh)) = pk;
+                *reinterpret_cast<uint2*>(stg + at_stg_w(r, dt * 4 + g, hh)) = pk;
             }
         __builtin_amdgcn_wave_barrier();
         uint4 rowv[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rowv[i] = ab_stg_fix(i, *reinterpret_cast<const uint4*>(stg + ab_stg_r(i, srow, spiece)));
+        for (int i = 0; i < 4; ++i) rowv[i] = at_stg_row(stg, i, srow, spiece);
 #pragma unroll
         for (int i = 0; i < 4; ++i) rtts_store16_out(dvdst + (obase + rpos[k2][i]) * AB_DH + spiece * 8, rowv[i]);
     }
@@ -477,17 +440,17 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
         for (int di = 0; di < KT2; ++di) {
             const int dt = (KT2 == 2) ? di : (wave & 1);
             const int kpc = dt * 4 + 2 * trc + (trp >> 1);     // 16-byte piece of the K row
-            ko0[di] = ab_off(rl, kpc) + 8 * (trp & 1);
-            ko1[di] = ab_off(rl + 4, kpc) + 8 * (trp & 1);
+            ko0[di] = at_off(rl, kpc) + 8 * (trp & 1);
+            ko1[di] = at_off(rl + 4, kpc) + 8 * (trp & 1);
         }
         const int gq = qt * 8 + 4 * trc + trp;             // 8-byte granule of the dS^T row
-        const int do0 = ab_ds_off<BS>(rl, gq), do1 = ab_ds_off<BS>(rl + 4, gq);
+        const int do0 = at_ds_off<BS>(rl, gq), do1 = at_ds_off<BS>(rl + 4, gq);
 #pragma unroll AB_DQ_UNROLL
         for (int kb = 0; kb < NK; kb += 16) {
-            const bf16x8 bfrag = tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
+            const bf16x8 bfrag = rtts_tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
 #pragma unroll
             for (int di = 0; di < KT2; ++di) {
-                const bf16x8 afrag = tr_frag(Ks + kb * 128 + ko0[di], Ks + kb * 128 + ko1[di]);
+                const bf16x8 afrag = rtts_tr_frag(Ks + kb * 128 + ko0[di], Ks + kb * 128 + ko1[di]);
                 dq[di] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag, dq[di], 0, 0, 0);
             }
         }
@@ -499,7 +462,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
                 uint2 pk;
                 pk.x = pack_bf16x2(dq[di][4 * g], dq[di][4 * g + 1]);
                 pk.y = pack_bf16x2(dq[di][4 * g + 2], dq[di][4 * g + 3]);
-                *reinterpret_cast<uint2*>(Os + ab_off(qt * 32 + r, dt * 4 + g) + 8 * hh) = pk;
+                *reinterpret_cast<uint2*>(Os + at_off(qt * 32 + r, dt * 4 + g) + 8 * hh) = pk;
             }
         }
     }
@@ -520,7 +483,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const uint2 kk = *reinterpret_cast<const uint2*>(Ks + ab_off(myrow[k2], dt * 4 + g) + 8 * hh);
+                const uint2 kk = *reinterpret_cast<const uint2*>(Ks + at_off(myrow[k2], dt * 4 + g) + 8 * hh);
                 kraw[dt][4 * g] = __uint_as_float(kk.x << 16);
                 kraw[dt][4 * g + 1] = __uint_as_float(kk.x & 0xffff0000u);
                 kraw[dt][4 * g + 2] = __uint_as_float(kk.y << 16);
@@ -537,7 +500,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
 #pragma unroll
                 for (int j = 0; j < 4; ++j) dk[j] = __builtin_fmaf(kraw[dt][4 * g + j], ncoef, gacc[k2][dt][4 * g + j]);
                 if (own_tile) {
-                    const uint2 dqv = *reinterpret_cast<const uint2*>(Os + ab_off(myrow[k2], dt * 4 + g) + 8 * hh);
+                    const uint2 dqv = *reinterpret_cast<const uint2*>(Os + at_off(myrow[k2], dt * 4 + g) + 8 * hh);
                     dk[0] += __uint_as_float(dqv.x << 16);
                     dk[1] += __uint_as_float(dqv.x & 0xffff0000u);
                     dk[2] += __uint_as_float(dqv.y << 16);
@@ -546,12 +509,12 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
                 uint2 pk;
                 pk.x = pack_bf16x2(dk[0], dk[1]);
                 pk.y = pack_bf16x2(dk[2], dk[3]);
-                *reinterpret_cast<uint2*>(stg + ab_stg_w(r, dt * 4 + g, hh)) = pk;
+                *reinterpret_cast<uint2*>(stg + at_stg_w(r, dt * 4 + g, hh)) = pk;
             }
         __builtin_amdgcn_wave_barrier();
         uint4 rowv[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rowv[i] = ab_stg_fix(i, *reinterpret_cast<const uint4*>(stg + ab_stg_r(i, srow, spiece)));
+        for (int i = 0; i < 4; ++i) rowv[i] = at_stg_row(stg, i, srow, spiece);
 #pragma unroll
         for (int i = 0; i < 4; ++i) rtts_store16_out(dkdst + (obase + rpos[k2][i]) * AB_DH + spiece * 8, rowv[i]);
     }
@@ -635,7 +598,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int rowb = it * (NTHR / 8) + wave * 8;            // wave-uniform: first row of this instruction
-            const int lp = (lane & 7) ^ ab_sw(rowb + (lane >> 3));
+            const int lp = (lane & 7) ^ at_sw(rowb + (lane >> 3));
             unsigned char* kdst = (rowb < BS) ? KsR + KSLOT + rowb * 128 : KsR + (rowb - BS) * 128;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qbase + (size_t)trow[it] * ld + lp * 8),
                                              (RTTS_LDS void*)kdst, 16, 0, 0);
@@ -744,7 +707,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
         const unsigned char* Kt = (own_tile ? Kown : Klb) + wt * (32 * 128);
         int fro[4];
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) fro[ks] = ab_off(r, ks * 2 + hh);
+        for (int ks = 0; ks < 4; ++ks) fro[ks] = at_off(r, ks * 2 + hh);
         if (own_tile || j == 0) {          // fresh keys (the looked-back group of the first step has nothing to keep either)
             const int pos_now = own_tile ? kq[wt * 32 + r] : kl[wt * 32 + r];
             if (j == 0) {                  // later steps: V rows and validity were requested by the previous one
@@ -778,10 +741,10 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
         const int trq = (lane & 15) >> 2, trp = lane & 3, trc = (lane >> 4) & 1;
         int tro[2];
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) tro[dt] = ab_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+        for (int dt = 0; dt < 2; ++dt) tro[dt] = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
         int dso[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) dso[g] = ab_ds_off<BS>(myrow, 2 * g + hh);
+        for (int g = 0; g < 4; ++g) dso[g] = at_ds_off<BS>(myrow, 2 * g + hh);
         const bool wrap = (cprev / nb) != (c / nb);
 #ifdef AB_PHASE_TIMING
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): V fragments (and this wave's share of the prefetch) have arrived
@@ -797,7 +760,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
                     const int it = piece >> 1;
                     const int rowb = it * (NTHR / 8) + wave * 8;
                     const int pos = pfpos[it];
-                    const int lp = (lane & 7) ^ ab_sw(rowb + (lane >> 3));
+                    const int lp = (lane & 7) ^ at_sw(rowb + (lane >> 3));
                     if ((piece & 1) == 0)
                         ab_dma16(qbase + (size_t)pos * ld + lp * 8, (RTTS_LDS void*)(Knext + rowb * 128));
                     else
@@ -866,7 +829,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
                         const bool self = pv[jj] == mypos;
                         const bool dead = kpk > ev[jj];
                         float x = sacc[i] * ksc2;
-                        x = self ? (-5e4f * 1.4426950408889634f) : x;
+                        x = self ? (AT_SELF * 1.4426950408889634f) : x;
                         float p = __builtin_amdgcn_exp2f(x - lv[jj]);
                         p = (dead && !self) ? 0.f : p;
                         pp[i] = p;
@@ -898,8 +861,8 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
                     const int blk = (qt * 32 + 16 * s2) * 128;
-                    qtf[s2][dt] = tr_frag(Kown + blk + tro[dt], Kown + blk + 8 * 128 + tro[dt ^ 1]);
-                    dotf[s2][dt] = tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
+                    qtf[s2][dt] = rtts_tr_frag(Kown + blk + tro[dt], Kown + blk + 8 * 128 + tro[dt ^ 1]);
+                    dotf[s2][dt] = rtts_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
                 }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
@@ -939,20 +902,20 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
             f32x16 dq = {0};
             const int rl = 8 * hh + trq;
             const int kpc = dt * 4 + 2 * trc + (trp >> 1);
-            const int ko0 = ab_off(rl, kpc) + 8 * (trp & 1), ko1 = ab_off(rl + 4, kpc) + 8 * (trp & 1);
+            const int ko0 = at_off(rl, kpc) + 8 * (trp & 1), ko1 = at_off(rl + 4, kpc) + 8 * (trp & 1);
             const int gq = qt * 8 + 4 * trc + trp;
-            const int do0 = ab_ds_off<BS>(rl, gq), do1 = ab_ds_off<BS>(rl + 4, gq);
+            const int do0 = at_ds_off<BS>(rl, gq), do1 = at_ds_off<BS>(rl + 4, gq);
             if (qt < NQT) {        // BS = 64: NW = 4 waves, 2 * NQT = 4 outputs -- every wave has one; BS = 128: 8 and 8
 #pragma unroll AB_DQ_UNROLL
                 for (int kb = 0; kb < BS; kb += 16) {
-                    const bf16x8 bfrag = tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
-                    const bf16x8 afrag = tr_frag(Kown + kb * 128 + ko0, Kown + kb * 128 + ko1);
+                    const bf16x8 bfrag = rtts_tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
+                    const bf16x8 afrag = rtts_tr_frag(Kown + kb * 128 + ko0, Kown + kb * 128 + ko1);
                     dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag, dq, 0, 0, 0);
                 }
 #pragma unroll AB_DQ_UNROLL
                 for (int kb = 0; kb < BS; kb += 16) {
-                    const bf16x8 bfrag = tr_frag(Ds + (BS + kb) * DSROW + do0, Ds + (BS + kb) * DSROW + do1);
-                    const bf16x8 afrag = tr_frag(Klb + kb * 128 + ko0, Klb + kb * 128 + ko1);
+                    const bf16x8 bfrag = rtts_tr_frag(Ds + (BS + kb) * DSROW + do0, Ds + (BS + kb) * DSROW + do1);
+                    const bf16x8 afrag = rtts_tr_frag(Klb + kb * 128 + ko0, Klb + kb * 128 + ko1);
                     dq = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag, dq, 0, 0, 0);
                 }
 #pragma unroll
@@ -960,7 +923,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
                     uint2 pk;
                     pk.x = pack_bf16x2(dq[4 * g], dq[4 * g + 1]);
                     pk.y = pack_bf16x2(dq[4 * g + 2], dq[4 * g + 3]);
-                    *reinterpret_cast<uint2*>(Os + ab_off(qt * 32 + r, dt * 4 + g) + 8 * hh) = pk;
+                    *reinterpret_cast<uint2*>(Os + at_off(qt * 32 + r, dt * 4 + g) + 8 * hh) = pk;
                 }
             }
         }
@@ -980,7 +943,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) kk2[dt][g] = *reinterpret_cast<const uint2*>(Kt + ab_off(r, dt * 4 + g) + 8 * hh);
+            for (int g = 0; g < 4; ++g) kk2[dt][g] = *reinterpret_cast<const uint2*>(Kt + at_off(r, dt * 4 + g) + 8 * hh);
         // (the empty asm reads the V rows requested above: the compiler's wait-count pass then KNOWS they have arrived -- otherwise it
         //  waits for them in the next main loop with vmcnt(0), i.e. behind this step's row stores, which it cannot count)
         asm volatile("" : "+v"(vf[0]), "+v"(vf[1]), "+v"(vf[2]), "+v"(vf[3]), "+v"(myvalid));
@@ -991,7 +954,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) dqp[dt][g] = *reinterpret_cast<const uint2*>(Os + ab_off(wt * 32 + r, dt * 4 + g) + 8 * hh);
+            for (int g = 0; g < 4; ++g) dqp[dt][g] = *reinterpret_cast<const uint2*>(Os + at_off(wt * 32 + r, dt * 4 + g) + 8 * hh);
         __syncthreads();   // the parked dQ rows have been read: the next step's prefetch may land in this dout image
 #else
         __syncthreads();   // dQ parked; the dS'^T image is free: it becomes the row staging
@@ -1017,7 +980,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #if AB_SPLIT_EPI
                 const uint2 kk = kk2[dt][g];
 #else
-                const uint2 kk = *reinterpret_cast<const uint2*>(Kt + ab_off(r, dt * 4 + g) + 8 * hh);
+                const uint2 kk = *reinterpret_cast<const uint2*>(Kt + at_off(r, dt * 4 + g) + 8 * hh);
 #endif
                 kraw[dt][4 * g] = __uint_as_float(kk.x << 16);
                 kraw[dt][4 * g + 1] = __uint_as_float(kk.x & 0xffff0000u);
@@ -1033,7 +996,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #if AB_SPLIT_EPI
                     const uint2 dqv = dqp[dt][g];
 #else
-                    const uint2 dqv = *reinterpret_cast<const uint2*>(Os + ab_off(myrow, dt * 4 + g) + 8 * hh);
+                    const uint2 dqv = *reinterpret_cast<const uint2*>(Os + at_off(myrow, dt * 4 + g) + 8 * hh);
 #endif
                     const float dqf[4] = {__uint_as_float(dqv.x << 16), __uint_as_float(dqv.x & 0xffff0000u), __uint_as_float(dqv.y << 16),
                                           __uint_as_float(dqv.y & 0xffff0000u)};
@@ -1070,12 +1033,12 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
                         uint2 pk;
                         pk.x = pack_bf16x2(dvacc[dt][4 * g], dvacc[dt][4 * g + 1]);
                         pk.y = pack_bf16x2(dvacc[dt][4 * g + 2], dvacc[dt][4 * g + 3]);
-                        *reinterpret_cast<uint2*>(stg + ab_stg_w(r, dt * 4 + g, hh)) = pk;
+                        *reinterpret_cast<uint2*>(stg + at_stg_w(r, dt * 4 + g, hh)) = pk;
                     }
                 __builtin_amdgcn_wave_barrier();
                 uint4 rowv[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) rowv[i] = ab_stg_fix(i, *reinterpret_cast<const uint4*>(stg + ab_stg_r(i, srow, spiece)));
+                for (int i = 0; i < 4; ++i) rowv[i] = at_stg_row(stg, i, srow, spiece);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) rtts_store16_out(dvdst + (obase + rpos[i]) * AB_DH + spiece * 8, rowv[i]);
                 __builtin_amdgcn_wave_barrier();
@@ -1100,12 +1063,12 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
                         uint2 pk;
                         pk.x = pack_bf16x2(dk[0], dk[1]);
                         pk.y = pack_bf16x2(dk[2], dk[3]);
-                        *reinterpret_cast<uint2*>(stg + ab_stg_w(r, dt * 4 + g, hh)) = pk;
+                        *reinterpret_cast<uint2*>(stg + at_stg_w(r, dt * 4 + g, hh)) = pk;
                     }
                 __builtin_amdgcn_wave_barrier();
                 uint4 rowv[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) rowv[i] = ab_stg_fix(i, *reinterpret_cast<const uint4*>(stg + ab_stg_r(i, srow, spiece)));
+                for (int i = 0; i < 4; ++i) rowv[i] = at_stg_row(stg, i, srow, spiece);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) rtts_store16_out(dkdst + (obase + rpos[i]) * AB_DH + spiece * 8, rowv[i]);
             }

@@ -24,16 +24,15 @@
 // the lazy running maximum (the rescale of O and l almost never runs), v_dot2c row norms, tree-shaped sums, and the walking form
 // below (every K / V row gathered once).  Ablations: profiles/r03_lsh_attn_fwd_ablation.log, r03_lsh_attn_fwd_walk_ablation.log.
 #include "rtts_common.h"
+#include "attn_tile.h"
 #include <float.h>
 
 #define AF_DH 64
-#define AF_ROWB 144   // LDS row stride (bytes): 128 B of bf16 + 16 B pad => conflict-free ds_read_b128
 #define AF_LOG2E 1.4426950408889634f
 #define AF_NEG (-1.0e30f)
 #define AF_BIGPOS 0x40000000
 #define AF_SLACK 8.0f   // see the tile loop: the running maximum may lag the true one by this many log2 units
 
-typedef __attribute__((ext_vector_type(8))) short af_short8;
 typedef __attribute__((ext_vector_type(2))) __bf16 af_bf2;
 
 // Phase probe (scripts/phase_probe.py --fwd builds a private copy with -DAF_PHASE_TIMING): waves 0 and NQT (the two key
@@ -59,11 +58,8 @@ extern "C" int rtts_debug_af_phases(void* dst) { return (int)hipMemcpyFromSymbol
 #ifndef AF_UNROLL
 #define AF_UNROLL BS == 64 ? 2 : 1
 #endif
-// V image: [row][128 B] without padding, the eight 16-byte pieces of a row XOR-swizzled (same function as the backward's
-// images, lsh_attn_bwd.hip) so that the transposed reads (4 consecutive rows x 64 B) are bank-conflict free; it is filled by
-// LDS-DMA, the swizzle applied on the source side.
-__device__ __forceinline__ int af_sw(int row) { return ((row >> 1) & 3) | ((((row >> 3) ^ (row >> 1)) & 1) << 2); }
-__device__ __forceinline__ int af_voff(int row, int piece) { return row * 128 + ((piece ^ af_sw(row)) << 4); }
+// K image: [row][AT_PADB], filled through registers (the row norms are reduced on the way).  V image: attn_tile.h's swizzled
+// [row][128 B] image (at_off), so that the transposed reads are bank-conflict free; it is filled by LDS-DMA.
 
 // Sum of a lane's 16 probabilities as a TREE (depth 4): the plain `l += p` loop is a chain of 16 dependent adds, and with four
 // waves per SIMD the chain's latency, not its issue slots, is what the tile pays (ablation r03: dropping the sum bought 6 %
@@ -98,7 +94,7 @@ __device__ __forceinline__ void af_tile_probs(f32x16& acc, const float* __restri
     // on early causal positions before this line read `m < -1e4`).  Real logits are bounded by |q| dh^-1/2 log2 e.
     const bool fresh = m < -1.0e4f;
     const float mref = fresh ? 0.f : m;
-    const float nref = -mref, selfv = (-5e4f * AF_LOG2E) - mref;
+    const float nref = -mref, selfv = (AT_SELF * AF_LOG2E) - mref;
     float gmax[2] = {AF_NEG, AF_NEG};                    // two independent chains, joined below
     // can a key of this tile BE the query itself?  (wave-uniform: the common path skips the test)
     if (chk_self) {
@@ -192,7 +188,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
     int* kpos = reinterpret_cast<int*>(ksc + NK);                // original position (self test)
     int* kpe = kpos + NK;                                        // effective position for the `dead` compare
     unsigned char* Ks = smem + NK * 12;
-    unsigned char* Vs = Ks + NK * AF_ROWB;                       // [NK][128] swizzled (the output staging reuses it, padded)
+    unsigned char* Vs = Ks + NK * AT_PADB;                       // [NK][128] swizzled (the output staging reuses it, padded)
 
     const int nb = T / BS;
     const int C = n_hashes * nb;
@@ -226,7 +222,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
             // V rows: global -> LDS by DMA; one wave-instruction fills 8 consecutive rows in lane order, so the lane that
             // lands on physical piece (lane & 7) of row (lane >> 3) fetches logical piece (lane & 7) ^ sw(row)
             const int rowb = it * (NTHR / 8) + wave * 8;
-            const int lp = (lane & 7) ^ af_sw(rowb + (lane >> 3));
+            const int lp = (lane & 7) ^ at_sw(rowb + (lane >> 3));
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + (size_t)trow[it] * ld + lp * 8),
                                              (RTTS_LDS void*)(Vs + rowb * 128), 16, 0, 0);
             // everything indexed by the position is requested now: two dependent global round trips, not three
@@ -236,7 +232,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int row = (it * NTHR + tid) >> 3, piece = tid & 7;
-            *reinterpret_cast<uint4*>(Ks + row * AF_ROWB + piece * 16) = kreg[it];
+            *reinterpret_cast<uint4*>(Ks + row * AT_PADB + piece * 16) = kreg[it];
             // |row piece|^2 straight from the packed pairs: v_dot2c_f32_bf16, 4 instructions per 16 bytes (unpack + fma: 16)
             float ss = 0.f;
             ss = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(af_bf2, kreg[it].x), __builtin_bit_cast(af_bf2, kreg[it].x), ss, false);
@@ -262,7 +258,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
     const int qrow = qt * 32 + r;
     bf16x8 qf[4];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(Ks + qrow * AF_ROWB + (ks * 16 + 8 * hh) * 2);
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(Ks + qrow * AT_PADB + (ks * 16 + 8 * hh) * 2);
     const int qpos = kpos[qrow];
     // an invalid query sees nothing but itself: effective position below every key's
     const int qpe = (kpe[qrow] == AF_BIGPOS) ? -1 : (CAUSAL ? qpos : 0);
@@ -270,7 +266,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
 
     int tro[2];
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt) tro[dt] = af_voff(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+    for (int dt = 0; dt < 2; ++dt) tro[dt] = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
 
     const bool wrap = (cprev / nb) != (c / nb);
     float m = AF_NEG, l = 0.f;
@@ -280,7 +276,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
         f32x16 acc = {0};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (kt * 32 + r) * AF_ROWB + (ks * 16 + 8 * hh) * 2);
+            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (kt * 32 + r) * AT_PADB + (ks * 16 + 8 * hh) * 2);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
         }
 #if AF_FOLD && !defined(AF_ABLATE)
@@ -309,7 +305,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
                 for (int j = 0; j < 4; ++j) {
                     float x = acc[4 * g + j] * scv[j];
                     x = (kev[j] > qpe) ? AF_NEG : x;
-                    x = (kpv[j] == qpos) ? (-5e4f * AF_LOG2E) : x;
+                    x = (kpv[j] == qpos) ? (AT_SELF * AF_LOG2E) : x;
                     acc[4 * g + j] = x;
                     gmax[g & 1] = fmaxf(gmax[g & 1], x);
                 }
@@ -379,7 +375,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
                 const int blk = (kt * 32 + 16 * s2) * 128;
                 const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)(Vs + blk + tro[dt]));
                 const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)(Vs + blk + 8 * 128 + tro[dt ^ 1]));
-                const af_short8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, both), pf, oacc[dt], 0, 0, 0);
             }
         }
@@ -423,7 +419,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
     // staging (the V image is dead by now) so that a row leaves as eight 16-byte pieces = one full 128-byte line.
     const int round = c / nb;
     const size_t obase = ((size_t)bh * n_hashes + round) * T;
-    unsigned char* stg = Vs + qt * (32 * AF_ROWB);
+    unsigned char* stg = Vs + qt * (32 * AT_PADB);
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
 #pragma unroll
@@ -431,7 +427,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
             uint2 pk;
             pk.x = pack_bf16x2(oacc[dt][4 * g], oacc[dt][4 * g + 1]);
             pk.y = pack_bf16x2(oacc[dt][4 * g + 2], oacc[dt][4 * g + 3]);
-            *reinterpret_cast<uint2*>(stg + r * AF_ROWB + (dt * 32 + 8 * g + 4 * hh) * 2) = pk;
+            *reinterpret_cast<uint2*>(stg + r * AT_PADB + (dt * 32 + 8 * g + 4 * hh) * 2) = pk;
         }
     }
     if (hh == 0) lse[obase + qpos] = (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;   // v_log_f32 is log2
@@ -441,7 +437,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
     int rpos[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        rowv[i] = *reinterpret_cast<const uint4*>(stg + (i * 8 + srow) * AF_ROWB + spiece * 16);
+        rowv[i] = *reinterpret_cast<const uint4*>(stg + (i * 8 + srow) * AT_PADB + spiece * 16);
         rpos[i] = kpos[qt * 32 + i * 8 + srow];
     }
 #pragma unroll
@@ -493,7 +489,7 @@ __device__ __forceinline__ void af_walk_tiles(const unsigned char* __restrict__ 
         f32x16 acc = {0};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kt + (t * 32 + r) * AF_ROWB + (ks * 16 + 8 * hh) * 2);
+            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kt + (t * 32 + r) * AT_PADB + (ks * 16 + 8 * hh) * 2);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
         }
 #if AF_FOLD && !defined(AF_ABLATE)
@@ -515,7 +511,7 @@ __device__ __forceinline__ void af_walk_tiles(const unsigned char* __restrict__ 
                 for (int j = 0; j < 4; ++j) {
                     float x = acc[4 * g + j] * scv[j];
                     x = (kev[j] > qpe) ? AF_NEG : x;
-                    x = (kpv[j] == qpos) ? (-5e4f * AF_LOG2E) : x;
+                    x = (kpv[j] == qpos) ? (AT_SELF * AF_LOG2E) : x;
                     acc[4 * g + j] = x;
                     gmax[g & 1] = fmaxf(gmax[g & 1], x);
                 }
@@ -577,7 +573,7 @@ __device__ __forceinline__ void af_walk_tiles(const unsigned char* __restrict__ 
                 const int blk = (t * 32 + 16 * s2) * 128;
                 const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)(Vt + blk + tro[dt]));
                 const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)(Vt + blk + 8 * 128 + tro[dt ^ 1]));
-                const af_short8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, both), pf, oacc[dt], 0, 0, 0);
             }
         }
@@ -611,7 +607,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
     int* tkmin = reinterpret_cast<int*>(ksc + NK);               // smallest / largest effective position of every 32-key tile of the run
     int* tkmax = tkmin + 128;                                    // ((L + 1) * BS / 32 <= 68 entries each; 128 keeps the images 16-byte aligned)
     unsigned char* Ks = reinterpret_cast<unsigned char*>(tkmax + 128);   // [2][BS][144]
-    unsigned char* Vs = Ks + NK * AF_ROWB;                       // [2][BS][128] swizzled
+    unsigned char* Vs = Ks + NK * AT_PADB;                       // [2][BS][128] swizzled
 
     const int nb = T / BS;
     const int C = n_hashes * nb;
@@ -654,14 +650,14 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
             const int pos = allpos[row < BS ? BS + row : row - BS];
             kreg[it] = *reinterpret_cast<const uint4*>(qbase + (size_t)pos * ld + piece * 8);
             const int rowb = it * (NTHR / 8) + wave * 8;
-            const int lp = (lane & 7) ^ af_sw(rowb + (lane >> 3));
+            const int lp = (lane & 7) ^ at_sw(rowb + (lane >> 3));
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(vbase + (size_t)pos * ld + lp * 8),
                                              (RTTS_LDS void*)(Vs + rowb * 128), 16, 0, 0);
         }
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int row = (it * NTHR + tid) >> 3, piece = tid & 7;
-            *reinterpret_cast<uint4*>(Ks + row * AF_ROWB + piece * 16) = kreg[it];
+            *reinterpret_cast<uint4*>(Ks + row * AT_PADB + piece * 16) = kreg[it];
             const float ss = rtts_sum8(af_piece_sumsq(kreg[it]));
             if (piece == 0) ksc[row] = (0.125f * AF_LOG2E) * __builtin_amdgcn_rsqf(fmaxf(ss, 1e-24f));   // 1 / max(|k|, 1e-12)
         }
@@ -685,7 +681,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
         const int trq = (lane & 15) >> 2, trp = lane & 3, trc = (lane >> 4) & 1;
         int tro[2];
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) tro[dt] = af_voff(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+        for (int dt = 0; dt < 2; ++dt) tro[dt] = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
         AF_WSTAMP(0);
         const int so = j & 1, sp = so ^ 1;           // own slot, looked-back slot (dead after the tiles)
         const int c = c0 + j;
@@ -694,7 +690,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
         bf16x8 qf[4];
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
-            qf[ks] = *reinterpret_cast<const bf16x8*>(Ks + (so * BS + qrow) * AF_ROWB + (ks * 16 + 8 * hh) * 2);
+            qf[ks] = *reinterpret_cast<const bf16x8*>(Ks + (so * BS + qrow) * AT_PADB + (ks * 16 + 8 * hh) * 2);
         const int qpos = allpos[(j + 1) * BS + qrow];
         // an invalid query sees nothing but itself: effective position below every key's
         const int qpe = (allkpe[(j + 1) * BS + qrow] == AF_BIGPOS) ? -1 : (CAUSAL ? qpos : 0);
@@ -703,7 +699,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
         const int self_lo = kh ? 0 : qt, self_hi = kh ? (wrap ? NQT : 0) : qt + 1;
         float m = AF_NEG, l = 0.f;
         f32x16 oacc[2] = {{0}, {0}};
-        af_walk_tiles<BS, DROP>(Ks + ms * (BS * AF_ROWB), Vs + ms * (BS * 128), ksc + ms * BS, allpos + (j + 1 - kh) * BS,
+        af_walk_tiles<BS, DROP>(Ks + ms * (BS * AT_PADB), Vs + ms * (BS * 128), ksc + ms * BS, allpos + (j + 1 - kh) * BS,
                                 allkpe + (j + 1 - kh) * BS, tkmin + (j + 1 - kh) * NQT, tkmax + (j + 1 - kh) * NQT, qf, qpos, qpe, self_lo,
                                 self_hi, r, hh, tro, m, l, oacc,
                                 ((uint32_t)(bh * C + c) * BS + (uint32_t)qrow) * (uint32_t)NK + (uint32_t)(kh * BS), seed,
@@ -712,7 +708,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
         AF_WSTAMP(1);
 
         // the dead slot as the partial buffer: per query tile 18 rows of 64 words in its K image (O[0..15], m, l), 16 in its V image
-        float* partA = reinterpret_cast<float*>(Ks + sp * (BS * AF_ROWB)) + qt * (18 * 64);
+        float* partA = reinterpret_cast<float*>(Ks + sp * (BS * AT_PADB)) + qt * (18 * 64);
         float* partB = reinterpret_cast<float*>(Vs + sp * (BS * 128)) + qt * (16 * 64);
         __syncthreads();                             // (1) every wave is done with the K / V images of this step
         AF_WSTAMP(2);
@@ -748,8 +744,8 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
 #define AF_PLACE(IT)                                                                                   \
             do {                                                                                       \
                 const int row = row0 + IT * (NTHR / 16);                                               \
-                *reinterpret_cast<uint4*>(Ks + (sp * BS + row) * AF_ROWB + piece * 16) = kreg##IT;     \
-                *reinterpret_cast<uint4*>(Vs + sp * (BS * 128) + af_voff(row, piece)) = vreg##IT;      \
+                *reinterpret_cast<uint4*>(Ks + (sp * BS + row) * AT_PADB + piece * 16) = kreg##IT;     \
+                *reinterpret_cast<uint4*>(Vs + sp * (BS * 128) + at_off(row, piece)) = vreg##IT;      \
                 const float ss = rtts_sum8(af_piece_sumsq(kreg##IT));                                  \
                 if (piece == 0) ksc[sp * BS + row] = (0.125f * AF_LOG2E) * __builtin_amdgcn_rsqf(fmaxf(ss, 1e-24f)); \
             } while (0)
@@ -778,7 +774,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
             // rows of o and lse at their UNSORTED position; the tile goes through a [32][144 B] staging in this wave's own
             // 4608 bytes of the dead slot's K image (its partial rows are in registers by now: LDS operations of a wave are in order)
             const size_t obase = ((size_t)bh * n_hashes + c / nb) * T;
-            unsigned char* stg = Ks + sp * (BS * AF_ROWB) + qt * (32 * AF_ROWB);
+            unsigned char* stg = Ks + sp * (BS * AT_PADB) + qt * (32 * AT_PADB);
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt) {
 #pragma unroll
@@ -786,7 +782,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
                     uint2 pk;
                     pk.x = pack_bf16x2(oacc[dt][4 * g], oacc[dt][4 * g + 1]);
                     pk.y = pack_bf16x2(oacc[dt][4 * g + 2], oacc[dt][4 * g + 3]);
-                    *reinterpret_cast<uint2*>(stg + r * AF_ROWB + (dt * 32 + 8 * g + 4 * hh) * 2) = pk;
+                    *reinterpret_cast<uint2*>(stg + r * AT_PADB + (dt * 32 + 8 * g + 4 * hh) * 2) = pk;
                 }
             }
             if (hh == 0) lse[obase + qpos] = (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f;   // v_log_f32 is log2
@@ -796,7 +792,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_walk_kernel(const bf16
             int rpos[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                rowv[i] = *reinterpret_cast<const uint4*>(stg + (i * 8 + srow) * AF_ROWB + spiece * 16);
+                rowv[i] = *reinterpret_cast<const uint4*>(stg + (i * 8 + srow) * AT_PADB + spiece * 16);
                 rpos[i] = allpos[(j + 1) * BS + qt * 32 + i * 8 + srow];
             }
 #pragma unroll
@@ -837,7 +833,7 @@ static int launch_attn_fwd(const bf16_t* qk, const bf16_t* v, int64_t ld, const 
     constexpr int NK = 2 * BS;
     const int L = rtts_lsh_attn_fwd_run_length(B, H, T, n_hashes, BS);
     const int C = n_hashes * (T / BS);
-    const size_t lds = L > 0 ? (size_t)(2 * (L + 1) * BS + NK + 256) * 4 + (size_t)NK * (AF_ROWB + 128) : 2 * NK * AF_ROWB + NK * 12;
+    const size_t lds = L > 0 ? (size_t)(2 * (L + 1) * BS + NK + 256) * 4 + (size_t)NK * (AT_PADB + 128) : 2 * NK * AT_PADB + NK * 12;
     const dim3 grid(L > 0 ? B * H * (C / L) : B * H * C), block(BS * 4);
     const bool drop = drop_p > 0.f;
     const int vi = (drop ? 4 : 0) + (causal ? 2 : 0) + (mask ? 1 : 0);

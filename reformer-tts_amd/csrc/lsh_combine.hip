@@ -11,15 +11,6 @@
 #define CB_DH 64
 #define CB_MAXR 16
 
-__device__ __forceinline__ void unpack8(const uint4 u, float* f) {
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __uint_as_float(w[k] << 16);
-        f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-    }
-}
-
 __device__ __forceinline__ uint4 pack8(const float* f) {
     uint4 u;
     u.x = pack_bf16x2(f[0], f[1]);
@@ -49,7 +40,7 @@ __global__ __launch_bounds__(256) void lsh_combine_fwd_kernel(const bf16_t* __re
         const float w = __expf(lv[r] - m);
         wsum += w;
         float f[8];
-        unpack8(*reinterpret_cast<const uint4*>(o + (((size_t)bh * n_hashes + r) * T + t) * CB_DH + piece * 8), f);
+        rtts_unpack8(*reinterpret_cast<const uint4*>(o + (((size_t)bh * n_hashes + r) * T + t) * CB_DH + piece * 8), f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = __builtin_fmaf(w, f[k], acc[k]);
     }
@@ -75,8 +66,8 @@ __global__ __launch_bounds__(256) void lsh_bwd_delta_kernel(const bf16_t* __rest
 #pragma unroll
         for (int pl = 0; pl < DH / 64; ++pl) {
             float a[8], g[8];
-            unpack8(*reinterpret_cast<const uint4*>(out + ((size_t)b * T + t) * ld_out + h * DH + pl * 64 + piece * 8), a);
-            unpack8(*reinterpret_cast<const uint4*>(dout + ((size_t)b * T + t) * ld_do + h * DH + pl * 64 + piece * 8), g);
+            rtts_unpack8(*reinterpret_cast<const uint4*>(out + ((size_t)b * T + t) * ld_out + h * DH + pl * 64 + piece * 8), a);
+            rtts_unpack8(*reinterpret_cast<const uint4*>(dout + ((size_t)b * T + t) * ld_do + h * DH + pl * 64 + piece * 8), g);
 #pragma unroll
             for (int k = 0; k < 8; ++k) s = __builtin_fmaf(a[k], g[k], s);
         }
@@ -103,10 +94,10 @@ __global__ __launch_bounds__(256) void lsh_bwd_reduce_kernel(const bf16_t* __res
         const int nslot = (row_flags == nullptr || row_flags[rr]) ? 2 : 1;
         float f[8];
         for (int s = 0; s < nslot; ++s) {
-            unpack8(*reinterpret_cast<const uint4*>(dqk_part + s * slot_stride + off), f);
+            rtts_unpack8(*reinterpret_cast<const uint4*>(dqk_part + s * slot_stride + off), f);
 #pragma unroll
             for (int k = 0; k < 8; ++k) aq[k] += f[k];
-            unpack8(*reinterpret_cast<const uint4*>(dv_part + s * slot_stride + off), f);
+            rtts_unpack8(*reinterpret_cast<const uint4*>(dv_part + s * slot_stride + off), f);
 #pragma unroll
             for (int k = 0; k < 8; ++k) av[k] += f[k];
         }

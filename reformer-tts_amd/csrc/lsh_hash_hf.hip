@@ -18,9 +18,9 @@
 // words l * SEG ..: ds_read_b32 banks are (address / 4) % 32 per 32-lane half, so an odd SEG puts the 32 lanes of a half on 32
 // different banks, where the even lengths that 128 or 256 bins suggest (2, 4) would make every read 2- or 4-way.
 #include "rtts_common.h"
+#include "attn_tile.h"   // AT_PADB
 
 #define HH_DH 64
-#define HH_ROWB 144   // LDS row stride in bytes of a staged 32 x 64 bf16 tile (conflict-free b128 reads)
 #define HH_W8_MIN_T 2048
 
 // HALFC = the compile-time column capacity of a round (a power of two >= half, 1 .. 128), half = n_buckets / 2 of this call.
@@ -30,27 +30,27 @@ template <int HALFC>
 __global__ __launch_bounds__(256) void lsh_hash_hf_kernel(const bf16_t* __restrict__ qk, int64_t ld, const float* __restrict__ rotations,
                                                           const uint8_t* __restrict__ mask, int H, int T, int n_hashes, int half,
                                                           int stride, int32_t* __restrict__ buckets, int32_t* __restrict__ ids) {
-    __shared__ __attribute__((aligned(16))) unsigned char tile[4 * 32 * HH_ROWB];
+    __shared__ __attribute__((aligned(16))) unsigned char tile[4 * 32 * AT_PADB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int blocks_per_head = T / 128;
     const uint32_t w = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = w / blocks_per_head, t0 = (w % blocks_per_head) * 128 + wave * 32;
     const int b = bh / H, h = bh % H;
     const bf16_t* base = qk + ((size_t)b * T + t0) * ld + (size_t)h * HH_DH;
-    unsigned char* wt = tile + wave * 32 * HH_ROWB;
+    unsigned char* wt = tile + wave * 32 * AT_PADB;
     {   // stage this wave's 32 rows: coalesced 16-byte pieces, all four loads in flight
         uint4 pre[4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) pre[p] = *reinterpret_cast<const uint4*>(base + (size_t)(p * 8 + (lane >> 3)) * ld + (lane & 7) * 8);
 #pragma unroll
-        for (int p = 0; p < 4; ++p) *reinterpret_cast<uint4*>(wt + (p * 8 + (lane >> 3)) * HH_ROWB + (lane & 7) * 16) = pre[p];
+        for (int p = 0; p < 4; ++p) *reinterpret_cast<uint4*>(wt + (p * 8 + (lane >> 3)) * AT_PADB + (lane & 7) * 16) = pre[p];
     }
     __builtin_amdgcn_wave_barrier();      // same wave wrote and reads: LDS ops of one wave execute in order
     const int hh = lane >> 5, l31 = lane & 31;
     // B operand: q[token][2j + hh], token = lane & 31: 32 registers, kept for every pass
     float bq[32];
     {
-        const unsigned char* rowp = wt + l31 * HH_ROWB;
+        const unsigned char* rowp = wt + l31 * AT_PADB;
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             const uint4 val = *reinterpret_cast<const uint4*>(rowp + p * 16);

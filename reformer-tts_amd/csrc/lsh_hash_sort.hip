@@ -18,6 +18,7 @@
 // ballot / ~ballot per bucket-id bit), a lane's stable rank is the popcount of that mask below it, and the
 // per-(wave, bucket) running offsets live in LDS -- O(log n_buckets) wave ops per group instead of O(n_buckets).
 #include "rtts_common.h"
+#include "attn_tile.h"   // AT_PADB
 #include <stdlib.h>
 
 #define HS_DH 64
@@ -27,7 +28,6 @@
 #ifndef HS_W8_MIN_T
 #define HS_W8_MIN_T 2048   // sequences from this length on get 8 waves per (head, round)
 #endif
-#define HS_ROWB 144   // LDS row stride in bytes for a staged 64 x 64 bf16 tile (conflict-free b128 reads)
 
 template <int HALF>
 __device__ __forceinline__ int hash_row(const float* q, const float* rot_lds, int half) {
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64 * WAVES) void lsh_hash_sort_kernel(
     // carve: rot [64*HALF] f32 | tile [WAVES][64 rows][144 B] | bkt [T] u16 | cntw [WAVES][64] i32 | tot [64] i32
     float* rot_lds = reinterpret_cast<float*>(smem);
     unsigned char* tile = smem + ((HS_DH * HALF * 4 + 15) & ~15);
-    uint16_t* bkt = reinterpret_cast<uint16_t*>(tile + WAVES * 64 * HS_ROWB);
+    uint16_t* bkt = reinterpret_cast<uint16_t*>(tile + WAVES * 64 * AT_PADB);
     int* cntw = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(bkt) + ((T * 2 + 15) & ~15));
     int* tot = cntw + WAVES * 64;
 
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64 * WAVES) void lsh_hash_sort_kernel(
     const int seg = T / WAVES;              // multiple of 32 because T % 128 == 0 and WAVES in {4, 8}
     const int s0 = wave * seg;
     const bf16_t* base = qk + (size_t)b * T * ld + (size_t)h * HS_DH;
-    unsigned char* wt = tile + wave * 64 * HS_ROWB;
+    unsigned char* wt = tile + wave * 64 * AT_PADB;
     // Row tiles are fetched PF at a time (all their loads in flight together): with few buckets the fmaf chains are
     // short and a wave would otherwise sit through one full memory round trip per 64 rows.  PF = 1 where the hash is
     // long enough to hide the next tile's latency behind it and the registers are needed for the accumulators.
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(64 * WAVES) void lsh_hash_sort_kernel(
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
                 const int row = p * 8 + (lane >> 3), piece = lane & 7;
-                if (row < rows) *reinterpret_cast<uint4*>(wt + row * HS_ROWB + piece * 16) = pre[u][p];
+                if (row < rows) *reinterpret_cast<uint4*>(wt + row * AT_PADB + piece * 16) = pre[u][p];
             }
             if (rows <= 0) continue;           // wave-uniform; (no break: the unrolled body keeps `pre` in registers)
             __builtin_amdgcn_wave_barrier();   // same wave wrote and reads: LDS ops of one wave execute in order
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(64 * WAVES) void lsh_hash_sort_kernel(
 #pragma unroll
                 for (int sub = 0; sub < 2; ++sub) {
                     f32x16 acc = {0};
-                    const unsigned char* rowp = wt + (32 * sub + (lane & 31)) * HS_ROWB;
+                    const unsigned char* rowp = wt + (32 * sub + (lane & 31)) * AT_PADB;
 #pragma unroll
                     for (int p = 0; p < 8; ++p) {
                         const uint4 val = *reinterpret_cast<const uint4*>(rowp + p * 16);
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(64 * WAVES) void lsh_hash_sort_kernel(
             float q[HS_DH];
 #pragma unroll
             for (int p = 0; p < 8; ++p) {
-                const uint4 val = *reinterpret_cast<const uint4*>(wt + lane * HS_ROWB + p * 16);
+                const uint4 val = *reinterpret_cast<const uint4*>(wt + lane * AT_PADB + p * 16);
                 const uint32_t uu[4] = {val.x, val.y, val.z, val.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void lsh_hash_rounds_kernel(const bf16_t* __re
     // 4 waves x 32 tokens: a wave's chain (rows -> LDS -> 32 registers, rotation columns -> 32 registers, 32 dependent
     // f32 MFMAs per pass, argmax, stores) is short and ~100 registers, so four waves per SIMD overlap each other's latencies
     // (two 64-token waves per workgroup measured 11.7 us at the decoder shape)
-    __shared__ __attribute__((aligned(16))) unsigned char tile[4 * 32 * HS_ROWB];
+    __shared__ __attribute__((aligned(16))) unsigned char tile[4 * 32 * AT_PADB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int blocks_per_head = T / 128;
     const uint32_t w = xcd_remap(blockIdx.x, gridDim.x);
@@ -304,20 +304,20 @@ __global__ __launch_bounds__(256) void lsh_hash_rounds_kernel(const bf16_t* __re
     const int b = bh / H, h = bh % H;
     const int NB = 2 * half;
     const bf16_t* base = qk + ((size_t)b * T + t0) * ld + (size_t)h * HS_DH;
-    unsigned char* wt = tile + wave * 32 * HS_ROWB;
+    unsigned char* wt = tile + wave * 32 * AT_PADB;
     {   // stage this wave's 32 rows: coalesced 16-byte pieces, all four loads in flight
         uint4 pre[4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) pre[p] = *reinterpret_cast<const uint4*>(base + (size_t)(p * 8 + (lane >> 3)) * ld + (lane & 7) * 8);
 #pragma unroll
-        for (int p = 0; p < 4; ++p) *reinterpret_cast<uint4*>(wt + (p * 8 + (lane >> 3)) * HS_ROWB + (lane & 7) * 16) = pre[p];
+        for (int p = 0; p < 4; ++p) *reinterpret_cast<uint4*>(wt + (p * 8 + (lane >> 3)) * AT_PADB + (lane & 7) * 16) = pre[p];
     }
     __builtin_amdgcn_wave_barrier();
     const int hh = lane >> 5, l31 = lane & 31;
     // B operand: q[token][2j + hh], token = lane & 31: 32 registers, kept for every pass
     float bq[1][32];
     {
-        const unsigned char* rowp = wt + l31 * HS_ROWB;
+        const unsigned char* rowp = wt + l31 * AT_PADB;
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             const uint4 val = *reinterpret_cast<const uint4*>(rowp + p * 16);
@@ -486,7 +486,7 @@ static int launch_hash_then_sort(const bf16_t* qk, int64_t ld, const float* rot,
 template <int HALF, int WAVES>
 static int launch_hash_sort_w(const bf16_t* qk, int64_t ld, const float* rot, int rot_rows, int B, int H, int T,
                               int n_hashes, int32_t* buckets, int32_t* st, int32_t* undo, int half, hipStream_t stream) {
-    const size_t lds = ((HS_DH * HALF * 4 + 15) & ~15) + WAVES * 64 * HS_ROWB + ((T * 2 + 15) & ~15) + (WAVES * 64 + 64) * 4;
+    const size_t lds = ((HS_DH * HALF * 4 + 15) & ~15) + WAVES * 64 * AT_PADB + ((T * 2 + 15) & ~15) + (WAVES * 64 + 64) * 4;
     static RttsLdsState lds_state = {};
     RTTS_ENSURE_LDS("rtts_lsh_hash_sort", (lsh_hash_sort_kernel<HALF, WAVES>), lds, lds_state);
     const dim3 grid(B * H * n_hashes);

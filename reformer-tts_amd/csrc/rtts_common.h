@@ -137,6 +137,25 @@ __device__ __forceinline__ bf16x8 cvt_bf16x8(float a0, float a1, float a2, float
     return __builtin_convertvector(v, bf16x8);
 }
 
+// one uint4 of eight bf16 -> eight floats, in memory order
+__device__ __forceinline__ void rtts_unpack8(const uint4 u, float* f) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f[2 * k] = __uint_as_float(w[k] << 16);
+        f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
+    }
+}
+
+// one MFMA fragment by hardware transpose out of a row-major LDS image: two ds_read_b64_tr_b16 (4 rows x 64 B each)
+typedef __attribute__((ext_vector_type(8))) short short8v;
+__device__ __forceinline__ bf16x8 rtts_tr_frag(const unsigned char* p0, const unsigned char* p1) {
+    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p0);
+    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p1);
+    const short8v both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, both);
+}
+
 // Cross-lane reductions without the LDS crossbar (ds_bpermute costs an LDS round trip per step):
 // sum over each aligned group of 8 lanes, result in all 8 (two quad_perm DPP adds + one row_half_mirror)
 __device__ __forceinline__ float rtts_sum8(float x) {

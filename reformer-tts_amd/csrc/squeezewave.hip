@@ -587,15 +587,6 @@ struct SwbRow {
     float dy[8], du[8], u[3][8], xh[8];
 };
 
-__device__ __forceinline__ void swb_unpack8(const uint4 v, float* o) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        o[2 * j] = __uint_as_float(w[j] << 16);
-        o[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-}
-
 __device__ __forceinline__ void swb_load8(const float* __restrict__ p, float* o) {
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
@@ -610,9 +601,9 @@ __device__ __forceinline__ void swb_load(const float* __restrict__ h, const bf16
     if (!first) dlo = *reinterpret_cast<const uint4*>(dy + (row - 1) * C + c);
     if (!last) dhi = *reinterpret_cast<const uint4*>(dy + (row + 1) * C + c);
     float d0[8], dl[8], dh[8], hm[8], hl[8], hh[8];
-    swb_unpack8(*reinterpret_cast<const uint4*>(dy + row * C + c), d0);
-    swb_unpack8(dlo, dl);
-    swb_unpack8(dhi, dh);
+    rtts_unpack8(*reinterpret_cast<const uint4*>(dy + row * C + c), d0);
+    rtts_unpack8(dlo, dl);
+    rtts_unpack8(dhi, dh);
     swb_load8(h + row * C + c, hm);
 #pragma unroll
     for (int j = 0; j < 8; ++j) hl[j] = hh[j] = 0.f;

@@ -14,32 +14,20 @@
 //             T_q/128 query blocks are written as partial slabs and summed by rtts_sum_slabs
 //             (deterministic, no atomics).
 #include "rtts_common.h"
+#include "attn_tile.h"
 #include <float.h>
 
-#define XA_ROWB 144
 #define XA_QB 128     // queries per workgroup
 #ifndef XA_UNROLL
 #define XA_UNROLL 1   // query-tile loop of the backward
 #endif
 
-typedef __attribute__((ext_vector_type(8))) short xa_short8;
-
-__device__ __forceinline__ bf16x8 xa_tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p0);
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((RTTS_LDS short4v*)p1);
-    const xa_short8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, both);
-}
-
 // ------------------------------------------------------------------------------ forward
-// LDS images of the backward (and the forward's V image) (same layouts as lsh_attn_bwd.hip, where the bank arithmetic is written out): rows of 128 B
-// without padding, 16-byte pieces XOR-swizzled by the row so that ds_read_b128 of one piece from 16 rows and
-// ds_read_b64_tr_b16 of 4 consecutive rows x 64 B are both conflict free; the dS^T image [key][128 queries] swizzles its
-// 8-byte granules by the key (conflict-free 8-byte stores of 16 consecutive keys and transposed reads of 4 keys x 64 B;
-// the padded 272-byte rows were 4-way conflicted on the read side).
+// LDS images of the backward (and the forward's V image): attn_tile.h's row images (at_off) and its dS^T image [key][128
+// queries] (at_ds_off<128>); the bank arithmetic is written out there.
 //
 // DH = 128 (256-byte rows).  A row is NOT stored as 256 contiguous bytes: every image is DH / 64 PLANES, plane p = columns
-// [64 p, 64 p + 64) of every row as a [rows][128 B] image of its own, swizzled by xa_off exactly as above.  The bank arithmetic:
+// [64 p, 64 p + 64) of every row as a [rows][128 B] image of its own, swizzled by at_off.  The bank arithmetic:
 // a bank is (byte address / 4) mod 64, i.e. the address mod 256; a plane is rows x 128 B with rows a multiple of 128, so every
 // plane starts at a multiple of 16 KB and address mod 256 of (plane, row, piece) equals that of (row, piece) in the 64 kernels.
 // Every LDS instruction of these kernels addresses ONE plane (a 32x32x16 MFMA fragment is 16 or 8 consecutive dh values, which
@@ -47,20 +35,10 @@ __device__ __forceinline__ bf16x8 xa_tr_frag(const unsigned char* p0, const unsi
 // time), so each instruction sees the bank pattern derived for 128-byte rows: ds_read_b128 of one piece from 16 rows, the
 // transposed read of 4 rows x 64 B, the 8-byte staging stores and 16-byte staging reads are all conflict free (degree 1), as at
 // DH = 64.  (Contiguous 256-byte rows start every row at bank 0: an unswizzled piece from 16 rows would be a 16-way conflict and the
-// 3-bit xa_sw cannot spread 16 rows over the 16 pieces of such a row; the planes keep the derivation that is already tested.)
+// 3-bit at_sw cannot spread 16 rows over the 16 pieces of such a row; the planes keep the derivation that is already tested.)
 // The dS^T image [key][128 queries] does not depend on DH.  On the global side a half-row is one full 128-byte line, so the DMA
 // loads stay line-sized.
-__device__ __forceinline__ int xa_sw(int row) { return ((row >> 1) & 3) | ((((row >> 3) ^ (row >> 1)) & 1) << 2); }
-__device__ __forceinline__ int xa_off(int row, int piece) { return row * 128 + ((piece ^ xa_sw(row)) << 4); }
-__device__ __forceinline__ int xa_ds_off(int key, int gran) {
-    const int k0 = key & 1, k1 = (key >> 1) & 1, k2 = (key >> 2) & 1, k3 = (key >> 3) & 1;
-    return key * 256 + ((gran ^ ((k1 << 4) | (k0 << 3) | (k1 << 2) | (k2 << 1) | k3)) << 3);
-}
-
-// Row staging of the epilogues (lsh_attn_bwd.hip's ab_stg_w / ab_stg_r, where the bank arithmetic is written out): the
-// accumulators hold a row (query / key) per lane and 4 dh values per register group, so a lane's natural store is 8 bytes into
-// 16 different 128-byte rows -- 16 store instructions per lane that each touch 32 rows.  Through a swizzled [32][128 B] image a
-// wave leaves full rows instead: 4 ds_read_b128 + 4 16-byte write-through stores (8 complete rows per instruction).
+// Row staging of the epilogues: attn_tile.h's at_store_rows, once per 64-column plane at DH = 128.
 // (Round 4 also tried the forward with TWO passes over the key tiles -- maximum first, then Q K^T again, exp, row sum, P V --
 //  so that a query's 256 logits need not sit in registers: 168 instead of 288 registers, two workgroups per CU instead of one,
 //  bit-identical, and SLOWER: 25.2 against 22.2 us.  The kernel is bound by its vector work, not by exposed latency.)
@@ -72,32 +50,6 @@ __device__ __forceinline__ int xa_ds_off(int key, int gran) {
 #ifndef XA_STAGED
 #define XA_STAGED 1    // 0: the 8-byte stores of rounds 1-3, for A/B runs
 #endif
-__device__ __forceinline__ int xa_stg_w(int r, int piece, int hh) { return r * 128 + ((piece ^ (r & 7)) << 4) + ((hh ^ ((r >> 3) & 1)) << 3); }
-__device__ __forceinline__ int xa_stg_r(int i, int srow, int spiece) { return (i * 8 + srow) * 128 + ((spiece ^ srow) << 4); }
-// acc[dt][4 g + j] of lane (r, hh) = element (row r, dh = 32 dt + 8 g + 4 hh + j), times `mul`  ->  32 rows of 64 bf16 at
-// dst + row * ld (16-byte aligned rows), through the wave-private 4 KB image `stg` (DH = 128: once per 64-column plane)
-__device__ __forceinline__ void xa_store_rows(unsigned char* stg, const f32x16 (&acc)[2], float mul, bf16_t* dst, int64_t ld, int lane) {
-    const int r = lane & 31, hh = lane >> 5, srow = lane >> 3, spiece = lane & 7;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint2 pk;
-            pk.x = pack_bf16x2(acc[dt][4 * g] * mul, acc[dt][4 * g + 1] * mul);
-            pk.y = pack_bf16x2(acc[dt][4 * g + 2] * mul, acc[dt][4 * g + 3] * mul);
-            *reinterpret_cast<uint2*>(stg + xa_stg_w(r, dt * 4 + g, hh)) = pk;
-        }
-    __builtin_amdgcn_wave_barrier();
-    uint4 rowv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint4 v = *reinterpret_cast<const uint4*>(stg + xa_stg_r(i, srow, spiece));
-        rowv[i] = (i & 1) ? uint4{v.z, v.w, v.x, v.y} : v;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) rtts_store16_out(dst + (size_t)(i * 8 + srow) * ld + spiece * 8, rowv[i]);
-    __builtin_amdgcn_wave_barrier();
-}
 
 // score scale 1 / sqrt(DH), applied in fp32
 template <int DH> struct xa_dh {
@@ -140,7 +92,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
     constexpr int NP = xa_dh<DH>::NP, NKS = xa_dh<DH>::NKS, PLANE = TK * 128;
     constexpr float SC = xa_dh<DH>::scale;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* Ks = smem;                       // [NP][TK][128] swizzled (xa_off), like V
+    unsigned char* Ks = smem;                       // [NP][TK][128] swizzled (at_off), like V
     unsigned char* Vs = Ks + NP * PLANE;
     int* kval = reinterpret_cast<int*>(Vs + NP * PLANE);
 
@@ -175,7 +127,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
         for (int it = 0; it < ITERS; ++it) {
             const int rowb = it * 32 + wave * 8;                     // wave-uniform: first row of this instruction
             const int row = rowb + (lane >> 3);
-            const int lp = (lane & 7) ^ xa_sw(row);
+            const int lp = (lane & 7) ^ at_sw(row);
             XA_PLANES(NP,
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)row * ld_kv + lp * 8),
                                                  (RTTS_LDS void*)(Ks + pl * PLANE + rowb * 128), 16, 0, 0);
@@ -192,7 +144,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
             XA_PLANES(NP,
                 _Pragma("unroll")
                 for (int ks = 0; ks < 4; ++ks) {
-                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + xa_off(kt * 32 + r, ks * 2 + hh));
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + at_off(kt * 32 + r, ks * 2 + hh));
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[pl * 4 + ks], acc, 0, 0, 0);
                 });
             s[kt] = acc;
@@ -254,9 +206,9 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
                     _Pragma("unroll")
                     for (int dt = 0; dt < 2; ++dt) {
                         const int blk = (kt * 32 + 16 * s2) * 128;
-                        const int t0 = xa_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
-                        const int t1 = xa_off(4 * hh + trq, (dt ^ 1) * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);   /* row + 8: sw flips bit 2 */
-                        const bf16x8 vf = xa_tr_frag(Vs + pl * PLANE + blk + t0, Vs + pl * PLANE + blk + 8 * 128 + t1);
+                        const int t0 = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+                        const int t1 = at_off(4 * hh + trq, (dt ^ 1) * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);   /* row + 8: sw flips bit 2 */
+                        const bf16x8 vf = rtts_tr_frag(Vs + pl * PLANE + blk + t0, Vs + pl * PLANE + blk + 8 * 128 + t1);
                         oacc[pl][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[pl][dt], 0, 0, 0);
                     });
             }
@@ -264,7 +216,7 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
     const float inv_l = 1.f / l_run;
 #if XA_STAGED
     __syncthreads();                 // every wave is done with the K image: it becomes the waves' row staging (4 KB each)
-    XA_PLANES(NP, xa_store_rows(Ks + wave * 4096, oacc[pl], inv_l,
+    XA_PLANES(NP, at_store_rows(Ks + wave * 4096, oacc[pl], inv_l,
                                 o + ((size_t)b * Tq + qb * XA_QB + wave * 32) * ld_o + (size_t)h * DH + pl * 64, ld_o, lane););
 #else
     bf16_t* optr = o + ((size_t)b * Tq + qrow) * ld_o + (size_t)h * DH;
@@ -340,14 +292,14 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
 #pragma unroll
         for (int it = 0; it < TK * 8 / NTHR; ++it) {
             const int rowb = it * (NTHR / 8) + wv * 8, row = rowb + (lane >> 3);
-            const int lp = (lane & 7) ^ xa_sw(row);
+            const int lp = (lane & 7) ^ at_sw(row);
             XA_PLANES(NP,
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)row * ld_kv + lp * 8),
                                                  (RTTS_LDS void*)(Ks + pl * KPL + rowb * 128), 16, 0, 0););
         }
         for (int rowb = wv * 8; rowb < XA_QB; rowb += NTHR / 8) {
             const int row = rowb + (lane >> 3);
-            const int lp = (lane & 7) ^ xa_sw(row);
+            const int lp = (lane & 7) ^ at_sw(row);
             XA_PLANES(NP,
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(qbase + pl * 64 + (size_t)row * ld_q + lp * 8),
                                                  (RTTS_LDS void*)(Qs + pl * QPL + rowb * 128), 16, 0, 0);
@@ -387,14 +339,14 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     const int trq = (lane & 15) >> 2, trp = lane & 3, trc = (lane >> 4) & 1;
     int fro[4], tro[2];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) fro[ks] = xa_off(r, ks * 2 + hh);
+    for (int ks = 0; ks < 4; ++ks) fro[ks] = at_off(r, ks * 2 + hh);
 #pragma unroll
-    for (int dt = 0; dt < 2; ++dt) tro[dt] = xa_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
+    for (int dt = 0; dt < 2; ++dt) tro[dt] = at_off(4 * hh + trq, dt * 4 + 2 * trc + (trp >> 1)) + 8 * (trp & 1);
     int dso[KT2][4];
 #pragma unroll
     for (int k2 = 0; k2 < KT2; ++k2)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) dso[k2][g] = xa_ds_off((wave * KT2 + k2) * 32 + r, 2 * g + hh);
+        for (int g = 0; g < 4; ++g) dso[k2][g] = at_ds_off<128>((wave * KT2 + k2) * 32 + r, 2 * g + hh);
 
 #pragma unroll XA_UNROLL
     for (int qt = 0; qt < XA_QB / 32; ++qt) {
@@ -412,8 +364,8 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
                 _Pragma("unroll")
                 for (int dt = 0; dt < 2; ++dt) {
                     const int blk = (qt * 32 + 16 * s2) * 128;     /* second read: 8 rows on, where sw flips the piece bit dt toggles */
-                    qtf[s2][pl * 2 + dt] = xa_tr_frag(Qs + pl * QPL + blk + tro[dt], Qs + pl * QPL + blk + 8 * 128 + tro[dt ^ 1]);
-                    dotf[s2][pl * 2 + dt] = xa_tr_frag(Os + pl * QPL + blk + tro[dt], Os + pl * QPL + blk + 8 * 128 + tro[dt ^ 1]);
+                    qtf[s2][pl * 2 + dt] = rtts_tr_frag(Qs + pl * QPL + blk + tro[dt], Qs + pl * QPL + blk + 8 * 128 + tro[dt ^ 1]);
+                    dotf[s2][pl * 2 + dt] = rtts_tr_frag(Os + pl * QPL + blk + tro[dt], Os + pl * QPL + blk + 8 * 128 + tro[dt ^ 1]);
                 });
 #pragma unroll
         for (int k2 = 0; k2 < KT2; ++k2) {
@@ -476,8 +428,8 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
         for (int k2 = 0; k2 < KT2; ++k2) {
             // rows of this wave's 32-key tile are consecutive keys: myrow[k2] = first key + r
             bf16_t* dkp = slab + (size_t)(myrow[k2] - r) * (2 * d);
-            XA_PLANES(NP, xa_store_rows(stg, gacc[k2][pl], 1.f, dkp + pl * 64, 2 * d, lane););
-            XA_PLANES(NP, xa_store_rows(stg, dvacc[k2][pl], 1.f, dkp + d + pl * 64, 2 * d, lane););
+            XA_PLANES(NP, at_store_rows(stg, gacc[k2][pl], 1.f, dkp + pl * 64, 2 * d, lane););
+            XA_PLANES(NP, at_store_rows(stg, dvacc[k2][pl], 1.f, dkp + d + pl * 64, 2 * d, lane););
         }
     }
 #else
@@ -510,14 +462,14 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
         f32x16 dqa = {0};
         const int rl = 8 * hh + trq;                       // key row inside a 16-key step (second read: +4)
         const int gq = qt * 8 + 4 * trc + trp;             // 8-byte granule of the dS^T row
-        const int do0 = xa_ds_off(rl, gq), do1 = xa_ds_off(rl + 4, gq);
+        const int do0 = at_ds_off<128>(rl, gq), do1 = at_ds_off<128>(rl + 4, gq);
         const int kpc = dt * 4 + 2 * trc + (trp >> 1);
         const unsigned char* Kp = Ks + dpl * KPL;
-        const int ko0 = xa_off(rl, kpc) + 8 * (trp & 1), ko1 = xa_off(rl + 4, kpc) + 8 * (trp & 1);
+        const int ko0 = at_off(rl, kpc) + 8 * (trp & 1), ko1 = at_off(rl + 4, kpc) + 8 * (trp & 1);
 #pragma unroll
         for (int kb = 0; kb < TK; kb += 16) {
-            const bf16x8 bfrag = xa_tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
-            const bf16x8 afrag = xa_tr_frag(Kp + kb * 128 + ko0, Kp + kb * 128 + ko1);
+            const bf16x8 bfrag = rtts_tr_frag(Ds + kb * DSROW + do0, Ds + kb * DSROW + do1);
+            const bf16x8 afrag = rtts_tr_frag(Kp + kb * 128 + ko0, Kp + kb * 128 + ko1);
             dqa = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, bfrag, dqa, 0, 0, 0);
         }
         bf16_t* dqp = dq + ((size_t)b * Tq + (size_t)qb * XA_QB + qt * 32 + r) * ld_dq + (size_t)h * DH;
@@ -665,7 +617,7 @@ __global__ __launch_bounds__(256) void xattn_probs_mean_kernel(const bf16_t* __r
                                                                int H, int Tq, int Tk, float* __restrict__ a, int64_t ld_a) {
     constexpr int NKT = XP_KC / 32;
     constexpr int NP = xa_dh<DH>::NP, NKS = xa_dh<DH>::NKS, PLANE = XP_KC * 128;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x [NP][XP_KC][128 B] swizzled (xa_off), kval
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x [NP][XP_KC][128 B] swizzled (at_off), kval
     const int nqb = Tq / XA_QB, nkc = Tk / XP_KC;
     const uint32_t wi = xcd_remap(blockIdx.x, gridDim.x);       // (b, query block, key chunk), key chunk fastest: the chunks of a
     const int kc = wi % nkc, qb = (wi / nkc) % nqb, b = wi / (nkc * nqb);   // query block share its Q rows in one XCD's L2
@@ -681,7 +633,7 @@ __global__ __launch_bounds__(256) void xattn_probs_mean_kernel(const bf16_t* __r
         for (int it = 0; it < ITERS; ++it) {
             const int rowb = it * 32 + wave * 8;
             const int row = rowb + (lane >> 3);
-            const int lp = (lane & 7) ^ xa_sw(row);
+            const int lp = (lane & 7) ^ at_sw(row);
             XA_PLANES(NP,
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)row * ld_kv + h * DH + lp * 8),
                                                  (RTTS_LDS void*)(dst + pl * PLANE + rowb * 128), 16, 0, 0););
@@ -713,7 +665,7 @@ __global__ __launch_bounds__(256) void xattn_probs_mean_kernel(const bf16_t* __r
             XA_PLANES(NP,
                 _Pragma("unroll")
                 for (int ks = 0; ks < 4; ++ks) {
-                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + xa_off(kt * 32 + r, ks * 2 + hh));
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + at_off(kt * 32 + r, ks * 2 + hh));
                     s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[pl * 4 + ks], s, 0, 0, 0);
                 });
             // exp(s / sqrt(DH) - lse) as one fma and v_exp_f32 (2^x); masked keys are zeroed at the store, whatever they sum to here

@@ -21,7 +21,7 @@ future included), o_i = mean(keep_i o v), lse_i = -FLT_MAX + log T = -FLT_MAX in
 from softmax (which subtracts the maximum first), never rebuilt as exp(s - lse).
 
 ``keep`` (``keep_scales``) is rebuilt from ``oracle.synth.drop_hash``: element (head, i, j), head = b H + h, has the index
-(head T + i) T + j in wrapping uint32 arithmetic (full_attn.hip:197 forward, :340 backward); the effective seed is
+(head T + i) T + j in wrapping uint32 arithmetic (full_attn.hip:158 forward, :301 backward); the effective seed is
 seed + *seed_dev; kept iff hash >= int(float32(p) 2^32), a kept element carries float32(1) / (float32(1) - float32(p)).
 
 Error bounds.  u = 2^-8 is the unit roundoff of bf16.  fp32 arithmetic between the roundings (MFMA accumulation, the column
@@ -29,17 +29,17 @@ scale, exp, the running maximum and normaliser, the fp32 workspace) is three to 
 to bf16, with their source lines in csrc/full_attn.hip:
 
     o    : 2u (keep o P)|V|
-             1. P~ keep, the unnormalised probability times the keep-scale, rounded before the P V MFMA (cvt_bf16x8, :209);
+             1. P~ keep, the unnormalised probability times the keep-scale, rounded before the P V MFMA (cvt_bf16x8, :170);
                 a later alpha rescale multiplies the fp32 accumulator and keeps the relative error
-             2. o rounded on store (fa_store_rows -> pack_bf16x2, :53-54, called at :223)
+             2. o rounded on store (at_store_rows of attn_tile.h -> pack_bf16x2, called at :184)
     delta: d_delta = sum_d B_o |dO|       delta is the rowsum over the KERNEL's rounded o, as the engine forms it
     dS   : E = u |dS| + P d_delta, 0 on filled pairs
-             3. dS rounded before the G MFMA (key pass, cvt_bf16x8 :360) and dS * column scale rounded before the dQ MFMA
+             3. dS rounded before the G MFMA (key pass, cvt_bf16x8 :321) and dS * column scale rounded before the dQ MFMA
                 (query pass, the same line); the second term is the delta error carried through dS = P (. - delta)
     dv   : u (keep o P)^T |dO| + u |dv|
-             4. P keep rounded before the dV MFMA (:364)       5. dv rounded on store (:431)
+             4. P keep rounded before the dV MFMA (:325)       5. dv rounded on store (:392)
     dqk  : E |K^| / 8 + (dg + |k^| (|k^| . dg)) / |qk| + u |dqk|,   dg = E^T |QK| / 8
-             the key-role rows stay fp32 (workspace) until they are added to the query role;  6. dqk rounded on store (:431)
+             the key-role rows stay fp32 (workspace) until they are added to the query role;  6. dqk rounded on store (:392)
 
 ``kernel_model`` walks the key tiles of 64 with a running maximum and normaliser and rounds where the kernels round, in fp32 /
 bf16 torch; tests/test_full_attn_cpu.py holds it to the bounds and requires every ``defect`` to break one."""
@@ -178,7 +178,7 @@ def kernel_model(qk, v, do, mask=None, causal=False, drop=None, defect=None):
             s = torch.where(torch.eye(t, dtype=torch.bool), slf, torch.where(dead, neg, raw * cs.transpose(-1, -2)))
         else:
             s = torch.where(dead, neg, torch.where(diag, slf, raw * cs.transpose(-1, -2)))
-        # forward: tiles of 64 keys, running maximum and normaliser (full_attn.hip:135-220)
+        # forward: tiles of 64 keys, running maximum and normaliser (full_attn.hip:96-181)
         m_run = torch.full((nh, t, 1), -big)
         l_run = torch.zeros(nh, t, 1)
         oacc = torch.zeros(nh, t, DH)
@@ -202,7 +202,7 @@ def kernel_model(qk, v, do, mask=None, causal=False, drop=None, defect=None):
             oacc = torch.where(live, o_new, oacc)
         o = bf(oacc / l_run)
         lse = torch.where(m_run == -big, m_run, m_run + torch.log(l_run)).squeeze(-1)
-        # backward: P from the forward's lse, delta from the rounded o (full_attn.hip:291-376)
+        # backward: P from the forward's lse, delta from the rounded o (full_attn.hip:252-337)
         delta = (o * dob).sum(-1, keepdim=True)
         qvalid = torch.ones(t, dtype=torch.bool) if mb is None else mb
         p = torch.exp(s - lse.unsqueeze(-1))

@@ -1,28 +1,56 @@
 """Bank arithmetic of the attention kernels' LDS images, checked on the host.
 
-The swizzles of ``csrc/lsh_attn_bwd.hip`` (``ab_sw`` / ``ab_off`` / ``ab_ds_off``; ``lsh_attn_fwd.hip`` and ``xattn.hip`` use the
-same functions) are restated here and run through the LDS banking model of the MI355X notes: an access is served in
-fixed lane groups, one LDS cycle per group when no two lanes of a group hit the same bank at different addresses;
-64 banks of 4 bytes for ``ds_read_b128`` / ``ds_read_b64`` / ``ds_read_b64_tr_b16``, 32 banks for the stores.  This pins
-the claims of DESIGN.md 5a (conflict-free fragment reads AND transposed reads of one image); it does not execute HIP."""
+The layout functions of ``csrc/attn_tile.h`` (``at_sw`` / ``at_off`` / ``at_ds_off`` / ``at_stg_w`` / ``at_stg_r``) are the ones
+``lsh_attn_fwd.hip``, ``lsh_attn_bwd.hip``, ``xattn.hip`` and ``full_attn.hip`` compile: the four kernels share the header, so the
+model covers all of them.  ``tests/attn_tile_host.cpp`` is compiled with the host compiler and prints their tables; ``ab_sw``,
+``ab_off``, ``ab_ds_off``, ``ab_stg_w`` and ``ab_stg_r`` below look the values up there.  They are run through the LDS banking
+model of the MI355X notes: an access is served in fixed lane groups, one LDS cycle per group when no two lanes of a group hit
+the same bank at different addresses; 64 banks of 4 bytes for ``ds_read_b128`` / ``ds_read_b64`` / ``ds_read_b64_tr_b16``, 32
+banks for the stores.  This pins the claims of DESIGN.md 5a (conflict-free fragment reads AND transposed reads of one image);
+it does not execute HIP."""
 import itertools
+import os
+import shutil
+import subprocess
 
 import pytest
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "reformer-tts_amd", "csrc")
+SW, OFF, DS_OFF, STG_W, STG_R = {}, {}, {}, {}, {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def tables(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler")
+    exe = str(tmp_path_factory.mktemp("attn_tile") / "attn_tile_host")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "attn_tile_host.cpp"), "-o", exe])
+    for line in subprocess.check_output([exe], text=True).splitlines():
+        kind, *v = line.split()
+        v = [int(x) for x in v]
+        if kind == "O":
+            SW[v[0]] = v[1]
+            OFF.update({(v[0], piece): off for piece, off in enumerate(v[2:])})
+        elif kind == "D":
+            DS_OFF.update({(v[0], v[1], gran): off for gran, off in enumerate(v[2:])})
+        elif kind == "W":
+            STG_W.update({(v[0], v[1], hh): off for hh, off in enumerate(v[2:])})
+        else:
+            STG_R.update({(v[0], v[1], spiece): off for spiece, off in enumerate(v[2:])})
+
 
 def ab_sw(row):
-    return ((row >> 1) & 3) | ((((row >> 3) ^ (row >> 1)) & 1) << 2)
+    return SW[row]
 
 
 def ab_off(row, piece):
-    return row * 128 + ((piece ^ ab_sw(row)) << 4)
+    return OFF[row, piece]
 
 
 def ab_ds_off(bs, key, gran):
-    k0, k1, k2, k3 = key & 1, (key >> 1) & 1, (key >> 2) & 1, (key >> 3) & 1
-    if bs == 128:
-        return key * 256 + ((gran ^ ((k1 << 4) | (k0 << 3) | (k1 << 2) | (k2 << 1) | k3)) << 3)
-    return key * 128 + ((gran ^ ((k1 << 3) | (k0 << 2) | (k2 << 1) | k3)) << 3)
+    return DS_OFF[bs, key, gran]
 
 
 def conflict_free(accesses, nbytes, banks):
@@ -116,13 +144,13 @@ def test_gemm_tn_ring_dma_fill_is_a_permutation_of_the_row():
             assert logical == list(range(32))
 
 
-# ---- the row staging of the backward kernel's epilogues (ab_stg_w / ab_stg_r of csrc/lsh_attn_bwd.hip)
+# ---- the row staging of the epilogues (at_stg_w / at_stg_r of csrc/attn_tile.h)
 def ab_stg_w(r, piece, hh):
-    return r * 128 + ((piece ^ (r & 7)) << 4) + ((hh ^ ((r >> 3) & 1)) << 3)
+    return STG_W[r, piece, hh]
 
 
 def ab_stg_r(i, srow, spiece):
-    return (i * 8 + srow) * 128 + ((spiece ^ srow) << 4)
+    return STG_R[i, srow, spiece]
 
 
 B128_GROUPS_ALL = B128_GROUPS + [[l + 32 for l in g] for g in B128_GROUPS]

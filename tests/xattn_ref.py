@@ -23,7 +23,7 @@ four orders of magnitude below u and is not counted.  Each constant below counts
 
     o   : 2u (keep o P)|V|
             1. P~ keep, the unnormalised probability times the keep-scale, rounded before the P V MFMA  (cvt_bf16x8, :205)
-            2. o rounded on store                                                   (xa_store_rows -> pack_bf16x2, :72-73)
+            2. o rounded on store                                                   (at_store_rows of attn_tile.h -> pack_bf16x2)
     delta: d_delta = sum_d B_o |dO|     delta is the rowsum over the KERNEL's rounded o (lsh_combine.hip:74-77), as the engine
                                         forms it; its own 64 fp32 fmas are not counted
     dS  : E = u |dS| + P d_delta / 8
@@ -33,7 +33,7 @@ four orders of magnitude below u and is not counted.  Each constant below counts
             4. one chunk: dQ rounded on store (:463-464).  More chunks: every chunk's SHARE is rounded on store (the same
                lines, u sum_c |share_c| <= u |dS||K|) and the sum of the shares is rounded again by rtts_sum_slabs (:485-488)
     dK  : E^T |Q| + u sum_slabs(|dS|^T |Q|) + u |dK|
-            5. every query block's slab rounded on store (xa_store_rows :418)     6. the slab sum rounded (:485-488)
+            5. every query block's slab rounded on store (at_store_rows)          6. the slab sum rounded (:485-488)
     dV  : 2u (keep o P)^T |dO| + u |dV|
             7. P keep rounded before the dV MFMA (:389)   8. slab rounded on store (:419)   9. the slab sum rounded (:485-488)
 

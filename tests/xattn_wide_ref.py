@@ -23,7 +23,7 @@ xattn_ref.reference; only the chunk count behind the "more than one chunk" term 
 
     o   : 2u (keep o P)|V|
             1. P~ keep rounded before the P V MFMA (forward, ``const bf16x8 pf = cvt_bf16x8(s[kt][o8] ...``)
-            2. o rounded on store (xa_store_rows: ``pk.x = pack_bf16x2(acc[dt][4 * g] * mul ...``), once per plane
+            2. o rounded on store (at_store_rows: ``pk.x = pack_bf16x2(acc[dt][4 * g] * mul ...``), once per plane
     delta: d_delta = sum_d B_o |dO| over all dh columns; delta is the row sum over the KERNEL's rounded o
             (lsh_combine.hip lsh_bwd_delta_kernel<DH>), its own dh fp32 fmas are not counted
     dS  : E = u |dS| + c P d_delta
@@ -34,10 +34,10 @@ xattn_ref.reference; only the chunk count behind the "more than one chunk" term 
                chunks: every chunk's share is rounded on store by the same lines and their sum again by sum_slabs_kernel
                (``o.x = pack_bf16x2(acc[0], acc[1])``).  At dh = 128 this starts at T_k = 256.
     dK  : E^T |Q| + u sum_slabs(|dS|^T |Q|) + u |dK|
-            5. every query block's slab rounded on store (xa_store_rows of gacc)      6. the slab sum rounded (sum_slabs_kernel)
+            5. every query block's slab rounded on store (at_store_rows of gacc)      6. the slab sum rounded (sum_slabs_kernel)
     dV  : 2u (keep o P)^T |dO| + u |dV|
             7. P keep rounded before the dV MFMA (``const bf16x8 pb = cvt_bf16x8(pq[0] ...``)   8. slab rounded on store
-            (xa_store_rows of dvacc)   9. the slab sum rounded
+            (at_store_rows of dvacc)   9. the slab sum rounded
 The score scale c is applied in fp32 (``xa_dh<DH>::scale``): float32(1 / sqrt(128)) is within 2^-25 of the exact value, four
 orders of magnitude below u, and is not counted (1 / 8 is exact)."""
 import math
