@@ -368,25 +368,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     GN_STAMP(1);
     if constexpr (MODE != 3) GN_READ(a0, w0, wl0, wh0, smem_base, 0);
     int buf = 0;
-#ifdef GN_ABL_NOLDS          // timing-only builds (scripts/gemm_nt_stamps.py): results are wrong by construction
-#undef GN_READ
-#define GN_READ(AF, WF, WL, WH, sb_, KS) do { } while (0)
-    gn_static_for<0, TM>([&](auto ic) { constexpr int i = decltype(ic)::value; a0[i] = a1[i] = (gn_v4i){lane, i, 3, 4}; });
-    gn_static_for<0, TN>([&](auto jc) { constexpr int j = decltype(jc)::value; w0[j] = w1[j] = (gn_v4i){j, lane, 5, 6};
-                                        wl0[j] = wl1[j] = wh0[j] = wh1[j] = (gn_v2i){lane, j}; });
-#endif
-#ifdef GN_ABL_NOMFMA
-#undef GN_MFMA
-#define GN_MFMA(AF, WF, WL, WH, COND_, ST_, BUF_, Q0, Q1)                                         \
-    do {                                                                                          \
-        if (COND_) gn_static_for<(Q0), (Q1)>([&](auto qc) { issue_piece(qc, (ST_), (BUF_)); });   \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(AF[i]));             \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                          \
-            if constexpr (!W_KN) asm volatile("" ::"v"(WF[j]));                                   \
-            else asm volatile("" ::"v"(WL[j]), "v"(WH[j]));                                       \
-        }                                                                                         \
-    } while (0)
-#endif
     int pbuf = 0;                                    // buffer of stage s-1: the second half of stage s-1+NST's pieces goes there
     static_assert(MODE != 2 || (EPI != 4 && true), "persistent form: bf16 epilogues");
   for (;;) {                                         // MODE 2: one pass per tile of this workgroup; else a single pass
@@ -512,12 +493,8 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
         __builtin_amdgcn_sched_barrier(0);
         // MODE 2: the ring does not stop at a tile boundary -- stage indices >= nk are the next tile's first stages (issue_piece),
         // the second half of the stage whose first half the previous tile's last step issued goes out at s = 0
-#ifndef GN_ABL_NODMA
         GN_MFMA(a0, w0, wl0, wh0, MODE == 2 ? ((s >= 1 || !first_tile) && (s - 1 + NST < nk || has_next)) : (s >= 1 && s - 1 + NST < nk),
                 s - 1 + NST, pbuf, SPB, PER);
-#else
-        GN_MFMA(a0, w0, wl0, wh0, false, 0, 0, 0, 0);
-#endif
         __builtin_amdgcn_sched_barrier(0);
         gn_wait_lgkm<0>();                           // F1 is back: this wave has no read of stage s left
         if (s + 1 < nk || (MODE == 2 && has_next)) {
@@ -526,11 +503,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
             GN_READ(a0, w0, wl0, wh0, smem_base + nb * STAGE, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifndef GN_ABL_NODMA
         GN_MFMA(a1, w1, wl1, wh1, s + NST < nk || (MODE == 2 && has_next), s + NST, buf, 0, SPB);    // (implies: behind the barrier)
-#else
-        GN_MFMA(a1, w1, wl1, wh1, false, 0, 0, 0, 0);
-#endif
         __builtin_amdgcn_sched_barrier(0);
         pbuf = buf;
         buf = nb;
@@ -804,13 +777,10 @@ static bool gn_conv_form(int bm, int bn, int cpt) {
     if ((bm == 256 && bn == 256) || !gn_conv_fits(bm, bn, cpt)) return false;
     return g_gn_conv.load(std::memory_order_relaxed) != 1;
 }
-#ifndef GN_DEFAULT_STORE
-#define GN_DEFAULT_STORE 2
-#endif
-// store form of a bf16 output: the 16-byte forms need 16-byte aligned rows
+// store form of a bf16 output (the library's pick: 2, write-through): the 16-byte forms need 16-byte aligned rows
 static int gn_store_mode(const void* c, int64_t ldc) {
     const int want = g_gn_store.load(std::memory_order_relaxed);
-    const int m = want >= 0 ? want : GN_DEFAULT_STORE;
+    const int m = want >= 0 ? want : 2;
     return ((((uintptr_t)c & 15) == 0 && ldc % 8 == 0) ? m : 0);
 }
 
@@ -954,16 +924,6 @@ static int gn_run(const void* a, int64_t lda, const void* w, int64_t ldw, int w_
                  "(rtts_gemm_nt_gate_words(M, N) > 0)");
     hipStream_t s = (hipStream_t)stream;
     int rc = 0;
-#ifdef GN_EXPERIMENT_ROWTILE
-    // timing experiment only (scripts/build_ab.sh ... -DGN_EXPERIMENT_ROWTILE): a tile that spans the WHOLE row of an N = 512 product
-    // (what a LayerNorm in the epilogue would need), one wave per 64 columns
-    if (g_gn_mode.load(std::memory_order_relaxed) == 1 && N == 512 && !w_is_kn && epilogue == 0 && M % 64 == 0) {
-        rc = gn_launch3<64, 512, 1, 8, false, 0, 2, 0>(G, M / 64, s);
-        if (rc) return rc;
-        RTTS_LAUNCH_CHECK("rtts_gemm_nt");
-        return 0;
-    }
-#endif
     switch (pick) {
         case 0: rc = gn_launch<256, 256, 4, 2>(G, w_is_kn, s); break;
         case 1: rc = gn_launch<192, 128, 4, 2>(G, w_is_kn, s); break;

@@ -23,9 +23,6 @@
 
 #define AB_DH 64
 #define AB_ROWB 128   // row staging: unpadded 128-byte rows, swizzled (at_stg_w / at_stg_r)
-#ifndef AB_SPLIT_EPI
-#define AB_SPLIT_EPI 1   // walking kernel: a step's row stores run beside the next step's main loop (0: round 3's form, for A/B runs)
-#endif
 #ifndef AB_DQ_UNROLL
 #define AB_DQ_UNROLL 16
 #endif
@@ -43,14 +40,6 @@ extern "C" int rtts_debug_ab_phases(void* dst) { return (int)hipMemcpyFromSymbol
 #else
 #define AB_STAMP(i) do { } while (0)
 #define AB_WSTAMP(i, w) do { } while (0)
-#endif
-
-// AB_KT2 = 32-key tiles owned by one wave.  1: 8 waves per 128-key chunk pair, two waves per SIMD (<= 256 registers each).
-// 2: 4 waves, ONE wave per SIMD with the whole 512-entry register file: a query tile's fragments, per-query words and
-// transposed fragments are read once for two key tiles, and the two tiles' MFMA bursts and softmax arithmetic are
-// independent instruction streams the scheduler can interleave inside one wave.
-#ifndef AB_KT2
-#define AB_KT2 1
 #endif
 
 // DROP: dropout on the attention probabilities (lsh_attn_fwd.hip): with keep = 0 | 1/(1-p) from the same counter hash of the
@@ -81,12 +70,15 @@ struct AbDrop {
 };
 
 template <int BS, bool CAUSAL, bool MASKED, bool DROP>
-__global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn_bwd_kernel(
+__global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_kernel(
     const bf16_t* __restrict__ qk, const bf16_t* __restrict__ v, int64_t ld, const int32_t* __restrict__ st,
     const uint8_t* __restrict__ mask, const bf16_t* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse_tot,
     const float* __restrict__ delta, int H, int T, int n_hashes, bf16_t* __restrict__ dqk_part, bf16_t* __restrict__ dv_part,
     size_t slot_stride, AbDrop dr) {
-    constexpr int KT2 = AB_KT2;
+    // 32-key tiles owned by one wave: 8 waves per 128-key chunk pair, two per SIMD.  The one-trip `k2` / `di` loops and [KT2]
+    // arrays below are kept as statements: written as scalars the kernel is the same program but not the same instructions (the
+    // optimizer canonicalises the address sums before instead of after it unrolls; 212-213 against 213-214 VGPRs).
+    constexpr int KT2 = 1;
     constexpr int NK = 2 * BS;
     constexpr int NQT = BS / 32;
     constexpr int NW = NK / (32 * KT2);
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
     // ---- gather K rows (all 2*BS) and dout rows (own chunk) into LDS -----------------------
     // Two dependent global round trips, not three: everything that is indexed by the token position (rows AND the
     // per-token words mask / lse / delta) is requested as soon as the positions are known.
-    constexpr int ITERS = NK * 8 / NTHR;   // 4 (KT2 = 1) or 8
+    constexpr int ITERS = NK * 8 / NTHR;   // 4
     int trow[ITERS];
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
@@ -238,12 +230,6 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
         for (int g = 0; g < 4; ++g) dso[k2][g] = at_ds_off<BS>(myrow[k2], 2 * g + hh);
     const bool own_tile = wave * KT2 < BS / 32;  // wave-uniform (SGPR); the KT2 tiles of a wave sit on the same side
     const bool wrap = (cprev / nb) != (c / nb);
-#if defined(AB_STAGGER) && AB_STAGGER > 0
-    // The two waves of a SIMD run the same program from the same barrier: their MFMA bursts and their softmax arithmetic
-    // coincide, so the matrix pipe idles while both do vector work.  Holding the second-dispatched half back by a fraction
-    // of a tile puts one wave's vector phase under the other's MFMA burst (MI355X_MICROARCH.md, two waves per SIMD, item 9).
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= NTHR / 2) __builtin_amdgcn_s_sleep(AB_STAGGER);
-#endif
 
 #pragma unroll AB_UNROLL
     for (int qt = 0; qt < NQT; ++qt) {
@@ -275,16 +261,6 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
         }
         // A fragments of the transposed products (element j <-> query 16*s2 + 8*(j>>2) + 4*hh + (j&3))
         bf16x8 qtf[2][2], dotf[2][2];   // [s2][dh tile]
-        if (KT2 == 2) {                 // read once for both key tiles (at KT2 = 1 they are read late: registers)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const int blk = (qt * 32 + 16 * s2) * 128;
-                    qtf[s2][dt] = rtts_tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
-                    dotf[s2][dt] = rtts_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
-                }
-        }
 #pragma unroll
         for (int k2 = 0; k2 < KT2; ++k2) {
             // Can a key of this tile BE one of this tile's queries (the self logit)?  Own keys: only on the diagonal
@@ -353,16 +329,15 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
 #pragma unroll
                 for (int i = 0; i < 16; ++i) pp[i] = ((kbits >> i) & 1u) ? pp[i] * dr.scale : 0.f;
             }
-            if (KT2 == 1) {   // read only now, so that their registers are free during the softmax arithmetic above
+            // read only now, so that their registers are free during the softmax arithmetic above
 #pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
+            for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) {
-                        const int blk = (qt * 32 + 16 * s2) * 128;
-                        qtf[s2][dt] = rtts_tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
-                        dotf[s2][dt] = rtts_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
-                    }
-            }
+                for (int dt = 0; dt < 2; ++dt) {
+                    const int blk = (qt * 32 + 16 * s2) * 128;
+                    qtf[s2][dt] = rtts_tr_frag(Ks + blk + tro[dt], Ks + blk + 8 * 128 + tro[dt ^ 1]);
+                    dotf[s2][dt] = rtts_tr_frag(Os + blk + tro[dt], Os + blk + 8 * 128 + tro[dt ^ 1]);
+                }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const float* pq = pp + 8 * s2;
@@ -426,11 +401,10 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
 
     AB_STAMP(5);
     // ---- dQ^T[dh][q] = K^T dS'^T over all 2*BS keys: the 2*NQT (query tile, dh half) outputs are dealt over the waves
-    //      (KT2 = 1: one each; KT2 = 2: both dh halves of query tile `wave`, sharing the dS'^T fragments) and parked
-    //      (bf16) in the dout image's rows: a chunk row is both a query and an own key, so its query-role and
-    //      key-role gradients are added before they leave the chip
+    //      (one each) and parked (bf16) in the dout image's rows: a chunk row is both a query and an own key, so its
+    //      query-role and key-role gradients are added before they leave the chip
     {
-        const int qt = (KT2 == 2) ? wave : (wave >> 1);
+        const int qt = wave >> 1;
         f32x16 dq[KT2];
 #pragma unroll
         for (int di = 0; di < KT2; ++di) dq[di] = (f32x16){0};
@@ -438,7 +412,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
         int ko0[KT2], ko1[KT2];
 #pragma unroll
         for (int di = 0; di < KT2; ++di) {
-            const int dt = (KT2 == 2) ? di : (wave & 1);
+            const int dt = wave & 1;
             const int kpc = dt * 4 + 2 * trc + (trp >> 1);     // 16-byte piece of the K row
             ko0[di] = at_off(rl, kpc) + 8 * (trp & 1);
             ko1[di] = at_off(rl + 4, kpc) + 8 * (trp & 1);
@@ -456,7 +430,7 @@ __global__ __launch_bounds__(BS * 4 / AB_KT2, AB_KT2 == 2 ? 1 : 2) void lsh_attn
         }
 #pragma unroll
         for (int di = 0; di < KT2; ++di) {
-            const int dt = (KT2 == 2) ? di : (wave & 1);
+            const int dt = wave & 1;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 uint2 pk;
@@ -569,7 +543,6 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
     unsigned char* KsR = reinterpret_cast<unsigned char*>(qpeS + 2 * BS);   // [3][BS][128] qk rows, swizzled
     unsigned char* OsR = KsR + 3 * KSLOT;                            // [2][BS][128] dout rows, later the parked dQ
     unsigned char* Ds = OsR + 2 * KSLOT;                             // [NK][DSROW] dS'^T; after the dQ product: row staging
-    unsigned char* Stg = Ds;
 
     const int nb = T / BS;
     const int C = n_hashes * nb;
@@ -627,12 +600,10 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
         }
         if (R > 1 && tid < BS) kposS[2 * BS + tid] = pnext;
     }
-#if AB_SPLIT_EPI
     // the builtin, so that the compiler's wait-count pass knows the gather's LDS-DMA has landed: it treats a pending LDS-DMA as a
     // store that may alias any LDS read, and would wait with vmcnt(0) in front of the first LDS read of EVERY step
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     __syncthreads();
-#endif
 
     // Per-lane state that crosses a step: the K and V fragments, scale and position of this wave's 32 keys.  The wave groups
     // swap roles every step -- the group that works the OWN keys of chunk j works the same keys as LOOKED-BACK keys of chunk
@@ -671,17 +642,12 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 
 #define AB_JSTAMP(i) do { if (j == 2) AB_STAMP(i); } while (0)
         AB_JSTAMP(0);
-#if AB_SPLIT_EPI
         // Only the first step waits here (for the prologue's gather).  Later steps: every wave has waited for its share of the
         // prefetch in front of the barrier that ends the previous step's dQ phase, and the previous step's row stores are NOT
         // waited for -- the group that stores rows (four of the eight waves) arrives late at this step's main loop, the other
         // group is already in it: one wave of each group shares a SIMD, so the stores' staging / store issue of one wave runs
         // under the MFMAs of the other instead of in front of an idle matrix pipe.
         // (that first wait sits in front of the loop)
-#else
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's share of the prefetch (issued from assembly) has landed
-        __syncthreads();   // this step's rows and words are on chip (each wave waited for its own DMA); the previous step is over
-#endif
         AB_JSTAMP(1);
 
         // ---- prefetch of chunk j + 1 (rows by LDS-DMA, query words, positions of chunk j + 2): issued piecewise INSIDE the main
@@ -714,12 +680,10 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
                 myvalid = MASKED ? (int)mask[(size_t)b * T + pos_now] : 1;
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks) vf[ks] = *reinterpret_cast<const bf16x8*>(vbase + (size_t)pos_now * ld + ks * 16 + 8 * hh);
-#if AB_SPLIT_EPI
                 // used HERE (an empty asm that reads them), on the first step's path only: the compiler waits for the loads in front of
                 // it; where the two paths into the code below meet it would otherwise wait with vmcnt(0) in every step -- behind the
                 // previous step's row stores, which leave from asm statements it cannot count
                 asm volatile("" : "+v"(vf[0]), "+v"(vf[1]), "+v"(vf[2]), "+v"(vf[3]), "+v"(myvalid));
-#endif
             }
             mypos = pos_now;
 #pragma unroll
@@ -928,7 +892,6 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
             }
         }
         AB_JSTAMP(6);
-#if AB_SPLIT_EPI
         // What the NEXT step's main loop overwrites is read out in front of the two barriers below, so that a wave may enter that
         // main loop while others still store rows: the next chunk's words are published, the raw key rows (slot j % 3 = the
         // slot the next step's prefetch lands in) are taken into registers, and each wave waits for ITS share of this step's
@@ -956,18 +919,6 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
 #pragma unroll
             for (int g = 0; g < 4; ++g) dqp[dt][g] = *reinterpret_cast<const uint2*>(Os + at_off(wt * 32 + r, dt * 4 + g) + 8 * hh);
         __syncthreads();   // the parked dQ rows have been read: the next step's prefetch may land in this dout image
-#else
-        __syncthreads();   // dQ parked; the dS'^T image is free: it becomes the row staging
-        AB_JSTAMP(7);
-
-        // the prefetched words of the next chunk have long arrived: publish them (read after the barrier at the top of the next step)
-        if (more && tid < BS) {
-            qlseS[(par ^ 1) * BS + tid] = nlse * 1.4426950408889634f;
-            qdelS[(par ^ 1) * BS + tid] = -ndel;
-            qpeS[(par ^ 1) * BS + tid] = nval ? (CAUSAL ? npos : 0) : -1;
-            if (j + 2 < R) kposS[((j + 3) & 3) * BS + tid] = p2;
-        }
-#endif
 
         // ---- end of the step.  Own keys: the parked query-role gradient of the row joins the key-role accumulator (they are the
         //      same rows).  Looked-back keys (and the own keys of a run's last step): the row is complete -- dK = G - k^ (k^ . G) on
@@ -977,11 +928,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-#if AB_SPLIT_EPI
                 const uint2 kk = kk2[dt][g];
-#else
-                const uint2 kk = *reinterpret_cast<const uint2*>(Kt + at_off(r, dt * 4 + g) + 8 * hh);
-#endif
                 kraw[dt][4 * g] = __uint_as_float(kk.x << 16);
                 kraw[dt][4 * g + 1] = __uint_as_float(kk.x & 0xffff0000u);
                 kraw[dt][4 * g + 2] = __uint_as_float(kk.y << 16);
@@ -993,11 +940,7 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-#if AB_SPLIT_EPI
                     const uint2 dqv = dqp[dt][g];
-#else
-                    const uint2 dqv = *reinterpret_cast<const uint2*>(Os + at_off(myrow, dt * 4 + g) + 8 * hh);
-#endif
                     const float dqf[4] = {__uint_as_float(dqv.x << 16), __uint_as_float(dqv.x & 0xffff0000u), __uint_as_float(dqv.y << 16),
                                           __uint_as_float(dqv.y & 0xffff0000u)};
 #pragma unroll
@@ -1012,15 +955,11 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_bwd_walk_kernel(
             const int slot = (!own_tile && j == 0) ? 1 : 0;
             const size_t obase = ((size_t)bh * n_hashes + (own_tile ? c / nb : cprev / nb)) * T;
             const int srow = lane >> 3, spiece = lane & 7;
-#if AB_SPLIT_EPI
             // the staging (4 KB) must not lie where another wave's next main loop writes dS'^T: it takes the rows of the dS'^T
             // image this wave itself writes NEXT (32 keys x DSROW >= 4 KB: own keys after a looked-back step; the own keys of a
             // run's last step take their looked-back twin's rows)
             unsigned char* stg = Ds + ((own_tile ? BS : 0) + wt * 32) * DSROW;
             static_assert(32 * DSROW >= 32 * AB_ROWB, "the staging must fit a wave's rows of the dS'^T image");
-#else
-            unsigned char* stg = Stg + wave * (32 * AB_ROWB);
-#endif
             int rpos[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) rpos[i] = own_tile ? kq[wt * 32 + i * 8 + srow] : kl[wt * 32 + i * 8 + srow];
@@ -1099,11 +1038,10 @@ extern "C" int rtts_lsh_attn_bwd_run_length(int B, int H, int T, int n_hashes, i
     const int C = n_hashes * (T / bucket_size);
     const long long chunks = (long long)B * H * C;
     int R = 0;
-    if (AB_KT2 == 1)
-        for (int cand = 8; cand >= 4; cand >>= 1)
-            if (C % cand == 0 && chunks / cand >= 768) { R = cand; break; }
+    for (int cand = 8; cand >= 4; cand >>= 1)
+        if (C % cand == 0 && chunks / cand >= 768) { R = cand; break; }
     const int w = rtts_walk_override(1);          // tests / A-B runs only (rtts_debug_set_walk); -1 in every product call
-    if (w >= 0 && AB_KT2 == 1) R = (w >= 1 && C % w == 0) ? w : 0;
+    if (w >= 0) R = (w >= 1 && C % w == 0) ? w : 0;
     return R;
 }
 
@@ -1120,11 +1058,10 @@ static int launch_attn_bwd(const bf16_t* qk, const bf16_t* v, int64_t ld, const 
     const int C = n_hashes * (T / BS);
     const long long chunks = (long long)B * H * C;
     const int R = rtts_lsh_attn_bwd_run_length(B, H, T, n_hashes, BS);
-    if (R >= 1 && AB_KT2 == 1) {
+    if (R >= 1) {
         RTTS_REQUIRE(row_flags, "rtts_lsh_attn_bwd: this shape is worked by the walking kernel (rtts_lsh_attn_bwd_run_length() = %d): "
                                 "row_flags (B*H*n_hashes*T bytes) is required", R);
-        const size_t ds_bytes = (size_t)NK * (BS * 2), stg_bytes = (size_t)(NK / 32) * 32 * AB_ROWB;
-        const size_t wlds = (size_t)BS * 40 + 5 * (size_t)BS * 128 + (ds_bytes > stg_bytes ? ds_bytes : stg_bytes);
+        const size_t wlds = (size_t)BS * 40 + 5 * (size_t)BS * 128 + (size_t)NK * (BS * 2);   // words, row images, dS'^T (= row staging)
         static RttsLdsState wattr[8];
         const dim3 wgrid((unsigned)(chunks / R)), wblock(BS * 4);
 #define AB_WGO(C_, M_, D_)                                                                                                 \
@@ -1146,7 +1083,7 @@ static int launch_attn_bwd(const bf16_t* qk, const bf16_t* v, int64_t ld, const 
         return 0;
     }
     const size_t lds = NK * 128 + BS * 128 + NK * (BS * 2) + (NK / 32) * 32 * AB_ROWB + NK * 12 + BS * 12;
-    const dim3 grid(B * H * n_hashes * (T / BS)), block(BS * 4 / AB_KT2);
+    const dim3 grid(B * H * n_hashes * (T / BS)), block(BS * 4);
     static RttsLdsState attr[8];                 // per device: the dynamic-LDS limit is an attribute of the loaded function
 #define AB_GO(C_, M_, D_)                                                                                                  \
     do {                                                                                                                   \

@@ -76,16 +76,10 @@ __device__ __forceinline__ float af_sum16(const f32x16& a) {
 // key row, the same index in the backward kernels, so no mask is stored and the reversible recompute redraws the same one.
 // ---- the softmax arithmetic of one 32 x 32 tile, shared by both kernel forms (so that they agree bit for bit) -------------
 // acc: this lane's query against the tile's 32 keys, raw q.k (rows = keys 8g + 4hh + j).  -> acc = 2^(x - m) with x = q.k * scale[key],
-// masked; (m, l, O) updated.  AF_FOLD (default): scale and the reference ride in ONE fma, x' = fma(q.k, scale, -mref), so the tile
+// masked; (m, l, O) updated.  Scale and the reference ride in ONE fma, x' = fma(q.k, scale, -mref), so the tile
 // costs 16 fma + the masks + the maxima + 16 exp + the sums -- the separate 16 multiplies and 16 subtractions of round 3 are gone
 // (the ISA census had them at 32 of 113 vector instructions per tile).  mref = m, or 0 for a lane that has seen no live key but itself yet
 // (m = AF_NEG, or the self constant, would swallow the logit in the fma); when the lazy reference moves (rarely), the 16 values are shifted once.
-#ifndef AF_FOLD
-#define AF_FOLD 1
-#endif
-#ifndef AF_TILE_SKIP
-#define AF_TILE_SKIP 1
-#endif
 __device__ __forceinline__ void af_tile_probs(f32x16& acc, const float* __restrict__ ksc_t, const int* __restrict__ kpos_t,
                                               const int* __restrict__ kpe_t, int keyt, int hh, bool chk_self, int qpos, int qpe, float& m,
                                               float& l, f32x16 (&oacc)[2], bool live_all = false) {
@@ -279,92 +273,13 @@ __global__ __launch_bounds__(BS * 4, 2) void lsh_attn_fwd_kernel(const bf16_t* _
             const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (kt * 32 + r) * AT_PADB + (ks * 16 + 8 * hh) * 2);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
         }
-#if AF_FOLD && !defined(AF_ABLATE)
         af_tile_probs(acc, ksc, kpos, kpe, kt * 32, hh, (kt < NQT) ? (kt == qt) : wrap, qpos, qpe, m, l, oacc);
-#else
-        float tmax = AF_NEG;
-        float gmax[2] = {AF_NEG, AF_NEG};                    // two independent chains, joined below
-#if defined(AF_ABLATE) && AF_ABLATE == 3
-        // timing experiment only: no scale, no masks, no max, no exp
-        tmax = 0.f;
-#else
-        // can a key of this tile BE the query itself?  own keys: only the diagonal tile; looked-back keys: only when the
-        // previous chunk belongs to another hash round.  Wave-uniform: the common path skips the test.
-        const bool chk_self = (kt < NQT) ? (kt == qt) : wrap;
-        if (chk_self) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int key0 = kt * 32 + 8 * g + 4 * hh;
-                const float4 sc = *reinterpret_cast<const float4*>(ksc + key0);
-                const int4 kp = *reinterpret_cast<const int4*>(kpos + key0);
-                const int4 ke = *reinterpret_cast<const int4*>(kpe + key0);
-                const float scv[4] = {sc.x, sc.y, sc.z, sc.w};
-                const int kpv[4] = {kp.x, kp.y, kp.z, kp.w};
-                const int kev[4] = {ke.x, ke.y, ke.z, ke.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float x = acc[4 * g + j] * scv[j];
-                    x = (kev[j] > qpe) ? AF_NEG : x;
-                    x = (kpv[j] == qpos) ? (AT_SELF * AF_LOG2E) : x;
-                    acc[4 * g + j] = x;
-                    gmax[g & 1] = fmaxf(gmax[g & 1], x);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int key0 = kt * 32 + 8 * g + 4 * hh;
-                const float4 sc = *reinterpret_cast<const float4*>(ksc + key0);
-                const int4 ke = *reinterpret_cast<const int4*>(kpe + key0);
-                const float scv[4] = {sc.x, sc.y, sc.z, sc.w};
-                const int kev[4] = {ke.x, ke.y, ke.z, ke.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float x = acc[4 * g + j] * scv[j];
-#if !defined(AF_ABLATE) || AF_ABLATE != 2
-                    x = (kev[j] > qpe) ? AF_NEG : x;
-#endif
-                    acc[4 * g + j] = x;
-                    gmax[g & 1] = fmaxf(gmax[g & 1], x);
-                }
-            }
-        }
-        tmax = rtts_xhalf_max(fmaxf(gmax[0], gmax[1]));
-#endif
-        // LAZY reference: m follows the running maximum only when a tile exceeds it by more than AF_SLACK (log2 units), so
-        // probabilities stay below 2^AF_SLACK (exact in fp32, and bf16 keeps its relative precision) and the rescale of O
-        // and l -- 34 multiplies and an exp per tile -- runs for the first live tile of a wave and then almost never
-        // (wave-uniform branch).  (m, l, O) stay a consistent triple, so the merge and lse = m + log2 l need no change.
-        if (__any(tmax > m + AF_SLACK)) {
-            const float mnew = fmaxf(m, tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m - mnew);
-            m = mnew;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                oacc[0][i] *= alpha;
-                oacc[1][i] *= alpha;
-            }
-            l *= alpha;
-        }
-#if defined(AF_ABLATE) && AF_ABLATE == 3
-#pragma unroll
-        for (int i = 0; i < 16; ++i) l += acc[i];
-#else
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = __builtin_amdgcn_exp2f(acc[i] - m);
-        l += af_sum16(acc);
-#endif
-#endif
         if constexpr (DROP) {
             const uint32_t seed = drop_seed + (seed_dev ? seed_dev[0] : 0u);
             const uint32_t pair0 = ((uint32_t)wi * BS + (uint32_t)qrow) * (uint32_t)NK + (uint32_t)(kt * 32 + 4 * hh);
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[i] *= rtts_drop_keep(seed, pair0 + 8 * (i >> 2) + (i & 3), drop_thresh, drop_scale);
         }
-#if defined(AF_ABLATE) && AF_ABLATE == 4
-        oacc[0][0] += acc[0] + acc[5] + acc[10] + acc[15];      // timing experiment only: no P V product
-        if (false)
-#endif
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             const int o8 = 8 * s2;
@@ -473,92 +388,24 @@ __device__ __forceinline__ void af_walk_tiles(const unsigned char* __restrict__ 
     constexpr int NT = BS / 32;
 #pragma unroll AF_UNROLL
     for (int t = 0; t < NT; ++t) {
-        // AF_TILE_SKIP: positions inside a bucket are sorted, so whole 32 x 32 tiles are often uniformly dead (every key behind every
+        // Tile skip: positions inside a bucket are sorted, so whole 32 x 32 tiles are often uniformly dead (every key behind every
         // query of this wave: nothing to add -- the tile is skipped, MFMAs included) or uniformly live (no masks needed): 18 % and
         // 19 % of the tiles at random inputs, more on real text.  Both decisions are wave-uniform, from the tile's smallest / largest
         // effective key position (kmin_t / kmax_t, one word per tile, written once per run); a tile that may hold the query itself is
         // never skipped.  A skipped tile contributes exact zeros either way: results are bit-identical with and without.
         const bool self_tile = t >= self_lo && t < self_hi;
         bool live_all = false;
-#if AF_TILE_SKIP
         if (!self_tile) {
             if (__all(kmin_t[t] > qpe)) continue;
             live_all = __all(kmax_t[t] <= qpe);
         }
-#endif
         f32x16 acc = {0};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Kt + (t * 32 + r) * AT_PADB + (ks * 16 + 8 * hh) * 2);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], acc, 0, 0, 0);
         }
-#if AF_FOLD && !defined(AF_ABLATE)
         af_tile_probs(acc, ksc_t, kpos_t, kpe_t, t * 32, hh, self_tile, qpos, qpe, m, l, oacc, live_all);
-#else
-        float tmax = AF_NEG;
-        float gmax[2] = {AF_NEG, AF_NEG};                    // two independent chains, joined below
-        if (t >= self_lo && t < self_hi) {          // wave-uniform: a key of this tile can be the query itself
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int key0 = t * 32 + 8 * g + 4 * hh;
-                const float4 sc = *reinterpret_cast<const float4*>(ksc_t + key0);
-                const int4 kp = *reinterpret_cast<const int4*>(kpos_t + key0);
-                const int4 ke = *reinterpret_cast<const int4*>(kpe_t + key0);
-                const float scv[4] = {sc.x, sc.y, sc.z, sc.w};
-                const int kpv[4] = {kp.x, kp.y, kp.z, kp.w};
-                const int kev[4] = {ke.x, ke.y, ke.z, ke.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float x = acc[4 * g + j] * scv[j];
-                    x = (kev[j] > qpe) ? AF_NEG : x;
-                    x = (kpv[j] == qpos) ? (AT_SELF * AF_LOG2E) : x;
-                    acc[4 * g + j] = x;
-                    gmax[g & 1] = fmaxf(gmax[g & 1], x);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int key0 = t * 32 + 8 * g + 4 * hh;
-                const float4 sc = *reinterpret_cast<const float4*>(ksc_t + key0);
-                const int4 ke = *reinterpret_cast<const int4*>(kpe_t + key0);
-                const float scv[4] = {sc.x, sc.y, sc.z, sc.w};
-                const int kev[4] = {ke.x, ke.y, ke.z, ke.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float x = acc[4 * g + j] * scv[j];
-#if !defined(AF_ABLATE) || AF_ABLATE != 2
-                    x = (kev[j] > qpe) ? AF_NEG : x;
-#endif
-                    acc[4 * g + j] = x;
-                    gmax[g & 1] = fmaxf(gmax[g & 1], x);
-                }
-            }
-        }
-        tmax = rtts_xhalf_max(fmaxf(gmax[0], gmax[1]));
-        if (__any(tmax > m + AF_SLACK)) {           // lazy reference, as in the one-chunk kernel
-            const float mnew = fmaxf(m, tmax);
-            const float alpha = __builtin_amdgcn_exp2f(m - mnew);
-            m = mnew;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                oacc[0][i] *= alpha;
-                oacc[1][i] *= alpha;
-            }
-            l *= alpha;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-#if defined(AF_ABLATE) && AF_ABLATE == 5
-            acc[i] = acc[i] - m;                              // timing experiment only: no v_exp_f32
-#else
-            acc[i] = __builtin_amdgcn_exp2f(acc[i] - m);
-#endif
-        }
-#if !defined(AF_ABLATE) || AF_ABLATE != 6
-        l += af_sum16(acc);
-#endif
-#endif
         if constexpr (DROP) {
             const uint32_t pair0 = pair_base + (uint32_t)(t * 32 + 4 * hh);
 #pragma unroll

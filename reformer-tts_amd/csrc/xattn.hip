@@ -4,12 +4,12 @@
 // config/legacy/attention-depth-3-heads-4.yml and attention-depth-3-heads-3.yml).
 //
 // Replaces nn.MultiheadAttention as wrapped by MultiheadAttentionWrapper
-// (/root/reference/reformer_tts/model/reformer.py:161-186): scores = (q W_q)(k W_k)^T / sqrt(dh),
+// (reformer_tts/model/reformer.py:161-186): scores = (q W_q)(k W_k)^T / sqrt(dh),
 // key_padding_mask -> -inf, softmax, P V, per head; the four projections stay GEMMs outside.
 //
 // Same MFMA dataflow as the LSH chunk kernels (lsh_attn_fwd.hip / lsh_attn_bwd.hip):
 //   forward : lane = query, S^T = K Q^T, in-register softmax over all keys, O^T = V^T P^T
-//   backward: lane = key, wave w owns keys [32w, 32w+32) of the chunk (XA_KT2 = 1): dV, dK complete in registers for the
+//   backward: lane = key, wave w owns keys [32w, 32w+32) of the chunk: dV, dK complete in registers for the
 //             workgroup's 128 queries; dS^T crosses LDS once for dQ^T = K^T dS^T.  dK/dV of the
 //             T_q/128 query blocks are written as partial slabs and summed by rtts_sum_slabs
 //             (deterministic, no atomics).
@@ -47,9 +47,6 @@
 //  rows arrive (every CU at once: ~3 us) -> products and softmax (~2.5 us) -> rows leave"; neither fewer instructions nor more
 //  resident waves shorten it.  A third variant -- a workgroup loads the K / V images once and works TWO query blocks -- was 29.7
 //  against 21.9 us: the load is not what a block's 7.3 us are spent on either.  All three removed again; profiles/r04_xattn_ab.log.)
-#ifndef XA_STAGED
-#define XA_STAGED 1    // 0: the 8-byte stores of rounds 1-3, for A/B runs
-#endif
 
 // score scale 1 / sqrt(DH), applied in fp32
 template <int DH> struct xa_dh {
@@ -214,38 +211,20 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
             }
     }
     const float inv_l = 1.f / l_run;
-#if XA_STAGED
     __syncthreads();                 // every wave is done with the K image: it becomes the waves' row staging (4 KB each)
     XA_PLANES(NP, at_store_rows(Ks + wave * 4096, oacc[pl], inv_l,
                                 o + ((size_t)b * Tq + qb * XA_QB + wave * 32) * ld_o + (size_t)h * DH + pl * 64, ld_o, lane););
-#else
-    bf16_t* optr = o + ((size_t)b * Tq + qrow) * ld_o + (size_t)h * DH;
-#pragma unroll
-    for (int pl = 0; pl < NP; ++pl)
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                uint2 pk;
-                pk.x = pack_bf16x2(oacc[pl][dt][4 * g] * inv_l, oacc[pl][dt][4 * g + 1] * inv_l);
-                pk.y = pack_bf16x2(oacc[pl][dt][4 * g + 2] * inv_l, oacc[pl][dt][4 * g + 3] * inv_l);
-                *reinterpret_cast<uint2*>(optr + pl * 64 + dt * 32 + 8 * g + 4 * hh) = pk;
-            }
-#endif
     if (hh == 0) lse[(size_t)bh * Tq + qrow] = m_run + logf(l_run);
 }
 
 // ------------------------------------------------------------------------------ backward
-// XA_KT2 = 32-key tiles per wave: 2 = one wave per 64 keys (one wave per SIMD at TK = 256), 1 = one wave per 32 keys (two per SIMD,
-// the decomposition of lsh_attn_bwd.hip, which runs the same 128 x 256 tile in under half the cycles)
-#ifndef XA_KT2
-#define XA_KT2 1
-#endif
+// One wave per 32 keys (two per SIMD at TK = 256): the decomposition of lsh_attn_bwd.hip, and like there the one-trip `k2` loops
+// and [KT2] arrays are kept as statements (as scalars: the same program, other instructions).
 // DH = 128 is instantiated for TK = 128 only (rtts_xattn_bwd_key_chunks): four waves of 32 keys hold dK and dV in 2 x 64 fp32 per
 // lane, the accumulator count of a 64-key wave at DH = 64, and the images are K 32 KB + Q, dout 2 x 32 KB + dS^T 32 KB + 1 KB of
 // lse / delta = 129 KB of the CU's 160 KB (TK = 256 would need 64 + 64 + 64 KB).  DH = 64: 65 KB (TK = 128), 129 KB (TK = 256).
 template <int DH, int TK, bool DROP>
-__global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
+__global__ __launch_bounds__(TK * 2) void xattn_bwd_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
                                                        int64_t ld_kv, const uint8_t* __restrict__ kvalid,
                                                        const bf16_t* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
                                                        const float* __restrict__ delta, int H, int Tq, int TKtot, bf16_t* __restrict__ dq,
@@ -257,8 +236,8 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
     // share (dq_chunk_stride elements between the chunks' partial dQ arrays; one chunk: dq itself)
     const int kc0 = blockIdx.y * TK;
     dq += (size_t)blockIdx.y * dq_chunk_stride;
-    constexpr int KT2 = XA_KT2;
-    constexpr int NTHR = TK * 2 / KT2;       // one wave per 32 * KT2 keys
+    constexpr int KT2 = 1;
+    constexpr int NTHR = TK * 2;             // one wave per 32 keys
     constexpr int NW = NTHR / 64;
     if (DROP && seed_dev) seed += seed_dev[0];
     constexpr int DSROW = XA_QB * 2;
@@ -419,7 +398,6 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
 
     // dK | dV partial slab of this query block: layout (nqb, B, TKtot, 2d)
     bf16_t* slab = dkv_part + (((size_t)qb * B + b) * TKtot + kc0) * (size_t)(2 * d) + (size_t)h * DH;
-#if XA_STAGED
     __syncthreads();                 // every dS^T tile is in Ds; nobody reads the Q / dout images any more: they become the row staging
     {
         static_assert(2 * NP * QPL >= NW * 4096, "the Q and dout images must hold a 4 KB staging per wave");
@@ -432,28 +410,6 @@ __global__ __launch_bounds__(TK * 2 / XA_KT2) void xattn_bwd_kernel(const bf16_t
             XA_PLANES(NP, at_store_rows(stg, dvacc[k2][pl], 1.f, dkp + d + pl * 64, 2 * d, lane););
         }
     }
-#else
-#pragma unroll
-    for (int k2 = 0; k2 < KT2; ++k2) {
-        bf16_t* dkp = slab + (size_t)myrow[k2] * (2 * d);
-        bf16_t* dvp = dkp + d;
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x16& ga = gacc[k2][dt >> 1][dt & 1];
-                const f32x16& dva = dvacc[k2][dt >> 1][dt & 1];
-                uint2 pk;
-                pk.x = pack_bf16x2(ga[4 * g], ga[4 * g + 1]);
-                pk.y = pack_bf16x2(ga[4 * g + 2], ga[4 * g + 3]);
-                *reinterpret_cast<uint2*>(dkp + dt * 32 + 8 * g + 4 * hh) = pk;
-                pk.x = pack_bf16x2(dva[4 * g], dva[4 * g + 1]);
-                pk.y = pack_bf16x2(dva[4 * g + 2], dva[4 * g + 3]);
-                *reinterpret_cast<uint2*>(dvp + dt * 32 + 8 * g + 4 * hh) = pk;
-            }
-    }
-    __syncthreads();
-#endif
 
     // dQ^T[dh][q] = K^T dS^T: the 8 (DH = 128: 16) (query tile, 32-wide dh tile) outputs are dealt over the waves
     constexpr int NOUT = (XA_QB / 32) * NDT;
@@ -589,7 +545,7 @@ extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64
     do {                                                                                                                  \
         auto kern = drop_p > 0.f ? xattn_bwd_kernel<DH_, TK_, true> : xattn_bwd_kernel<DH_, TK_, false>;                  \
         RTTS_ENSURE_LDS("rtts_xattn_bwd", kern, lds, g_xa_lds[DH_ == 128][1 + (drop_p > 0.f)][TK_ == 256]);               \
-        hipLaunchKernelGGL(kern, grid, dim3(TK_ * 2 / XA_KT2), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
+        hipLaunchKernelGGL(kern, grid, dim3(TK_ * 2), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
                            kvalid, (const bf16_t*)dout, ld_dout, lse, delta, H, Tq, Tk, dq_dst, ld_dq, dq_stride, (bf16_t*)dkv_part, B, \
                            seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p));                               \
     } while (0)

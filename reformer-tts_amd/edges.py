@@ -72,8 +72,7 @@ class Halo:
         return body[:self.rows].view(self.b, self.p, -1)[:, self.H:self.H + self.l]
 
 
-import os as _os
-CONVS_PER_WGRAD_LAUNCH = int(_os.environ.get("RTTS_CONVS_PER_WGRAD", "4"))   # tap problems of up to 4 convolutions are launched together
+CONVS_PER_WGRAD_LAUNCH = 4   # tap problems of up to 4 convolutions are launched together
 
 
 def flush_conv_wgrad(queue=None) -> None:
@@ -220,7 +219,6 @@ class ConvK5:
 # all-reduced between the stage that produces them and the stage that uses them: 2*C + 1 floats per BatchNorm layer and
 # direction, six layers.  Eager steps only: a collective inside a hipGraph capture is not attempted.
 SYNC_BN = None
-CONV_MOMENTS = _os.environ.get("RTTS_CONV_MOMENTS", "1") != "0"      # A/B: the BatchNorm statistics from a second pass over y (rtts_bn_stats)
 
 
 class ConvBNAct:
@@ -232,7 +230,7 @@ class ConvBNAct:
 
     def forward(self, xh, g: Halo, plain_out: bool = False):
         """-> z (halo buffer (alloc, C) bf16, or (B*L, C) plain rows for the last layer of a stack), saved state."""
-        fused = SYNC_BN is None and CONV_MOMENTS
+        fused = SYNC_BN is None            # synchronised statistics come from a second pass over y (rtts_bn_stats)
         y, partial, nrows = self.c.forward_moments(xh, g) if fused else (self.c.forward(xh, g), None, 0)
         c = y.shape[1]
         dev = y.device

@@ -17,8 +17,6 @@ from __future__ import annotations
 
 from typing import List, Optional
 
-import os
-
 import torch
 
 from . import _lib, ops
@@ -378,8 +376,6 @@ def residual(acc, g, bias, sign: float, next_norm=None, drop=None, out=None):
 def gate_words(m: int, n: int, device) -> Optional[torch.Tensor]:
     """Buffer for the 1-bit ReLU gate of an (m, n) feed-forward activation (one word per lane and tile of the GEMM that
     produces it), or None where the tile shape chosen for (m, n) has no word form."""
-    if os.environ.get("RTTS_NO_GATE_WORDS"):          # A/B runs: gate by the activation
-        return None
     words = _lib.load().rtts_gemm_nt_gate_words(m, n)
     return torch.empty(words, dtype=torch.int64, device=device) if words > 0 else None
 
@@ -491,10 +487,6 @@ def dgrad_delta_ok(m: int, n: int) -> bool:
     return (m % 192 == 0 and n % 128 == 0) or (m % 128 == 0 and n % 64 == 0)
 
 
-FUSE_DELTA = os.environ.get("RTTS_FUSE_DELTA", "1") != "0"          # A/B: the separate rtts_lsh_bwd_delta launch
-GROUP_XATTN = os.environ.get("RTTS_GROUP_XATTN", "1") != "0"        # A/B: the q and k|v projections as two launches
-GROUP_XATTN_BWD = os.environ.get("RTTS_GROUP_XATTN_BWD", "0") == "1"   # A/B: dxn and dkeys as one grouped launch (measured: no gain)
-
 _SLAB_FLOATS = 16 * 1024 * 1024   # 64 MB: 16 splits of a 2048 x 512 gradient
 
 # Weight gradients are leaves of the backward's dependency graph: nothing reads them before the block's all-reduce /
@@ -503,11 +495,9 @@ _SLAB_FLOATS = 16 * 1024 * 1024   # 64 MB: 16 splits of a 2048 x 512 gradient
 # split factor and the fp32 slab traffic drop ~7x and launch ramps/tails are paid once per layer.
 DEFER_WGRAD = True
 # The queue is flushed once per layer's worth of problems, on one GPU too, where nobody waits for a block's gradients: holding
-# the weight gradients of the WHOLE backward back for a few large mixed groups at its end (RTTS_WGRAD_FLUSH=end) measured
-# 6.57 against 6.23 ms/step -- a layer's dy / x operands are still in the 256 MB Infinity Cache right after its backward and
-# have left it by the end of the step.
-WGRAD_FLUSH_PER_LAYER = os.environ.get("RTTS_WGRAD_FLUSH", "layer") == "layer"
-WGRAD_MAX_PENDING = 64
+# the weight gradients of the WHOLE backward back for a few large mixed groups at its end measured 6.57 against 6.23 ms/step
+# -- a layer's dy / x operands are still in the 256 MB Infinity Cache right after its backward and have left it by the end
+# of the step.
 # measurement only (scripts/replay_stamps.py): STAMPS = (uint64 device buffer, {name: slot}) makes stamp(name) launch a marker kernel
 # on the current stream; None (always, in product runs): stamp() does nothing
 STAMPS = None
@@ -521,8 +511,6 @@ def stamp(name: str) -> None:
     _lib.call("rtts_debug_stamp", buf.data_ptr(), slot, _s())
 
 
-JOIN_STREAMS = os.environ.get("RTTS_JOIN_STREAMS", "1") != "0"      # A/B: d(input) = g1 + g2 as a separate (ATen) pass after the stack's backward
-COPY_STREAMS = os.environ.get("RTTS_STREAM_COPIES", "0") == "1"     # A/B: copy x / dout into both streams instead of aliasing them
 # (A second HIP stream for the weight gradients, forked/joined by events = parallel branches of the captured hipGraph,
 #  was measured SLOWER on MI355X in round 1: 9.35 vs 8.94 ms/step; the cross-branch dependencies of the replayed graph
 #  cost more than the overlapped tails recover.  Removed.)
@@ -838,7 +826,7 @@ class LSHExec:
         out2 = out.view(b * t, e)
         wgrad(_grad(lyr.to_out.weight), dyb, out2)
         delta = None
-        if FUSE_DELTA and e == 64 * lyr.heads and dgrad_delta_ok(b * t, e):
+        if e == 64 * lyr.heads and dgrad_delta_ok(b * t, e):
             dout, delta = gemm_dgrad_delta(dyb, _bf16(lyr.to_out.weight), out2, t, lyr.heads)     # delta rides in the dgrad's epilogue
             dout = dout.view(b, t, e)
         else:
@@ -960,10 +948,8 @@ class XAttnExec:
         xn, mean, rstd = pre if pre is not None else ln_fwd(inp, self.norm)
         if proj is not None:
             q, kv = proj
-        elif GROUP_XATTN:      # the two in_proj products of nn.MultiheadAttention (reformer.py:161-186) in one launch
+        else:                  # the two in_proj products of nn.MultiheadAttention (reformer.py:161-186) in one launch
             q, kv = gemm_group([dict(a=xn, w=w[:e], bias=bias[:e]), dict(a=keys_bf16, w=w[e:], bias=bias[e:])])
-        else:
-            q, kv = gemm(xn, w[:e], bias=bias[:e]), gemm(keys_bf16, w[e:], bias=bias[e:])
         if stash is not None:
             o, lse = stash
         else:
@@ -1008,7 +994,7 @@ class XAttnExec:
         dyb = _out_grad(d_acc, _grad(m.out_proj.bias), None, pre_cast)
         wgrad(_grad(m.out_proj.weight), dyb, o)
         dev = inp.device
-        if FUSE_DELTA and e == 64 * h and dgrad_delta_ok(b * t, e):
+        if e == 64 * h and dgrad_delta_ok(b * t, e):
             do, delta = gemm_dgrad_delta(dyb, _bf16(m.out_proj.weight), o, t, h)
         else:                  # heads of 128 always come here: epilogue 5 sums 64-wide heads
             do = gemm(dyb, _bf16(m.out_proj.weight), kn=True)
@@ -1034,11 +1020,8 @@ class XAttnExec:
         # dkeys (fp32) += dkv W_kv in the product's own epilogue (no separate add launch).  Grouping it with dxn = dq W_q into one
         # launch measured no gain (28.7 against 27.7 us for the two launches + the add: a K = 1024 tile beside K = 512 tiles on two
         # workgroups per CU; profiles/r04_gemm_nt_persistent_ab.log), so the two products stay two launches
-        if GROUP_XATTN_BWD:
-            dxn, _ = gemm_group([dict(a=dq, w=w[:e]), dict(a=dkv, w=w[e:], into=dkeys)], kn=True)
-        else:
-            dxn = gemm(dq, w[:e], kn=True)
-            gemm_group([dict(a=dkv, w=w[e:], into=dkeys)], kn=True)
+        dxn = gemm(dq, w[:e], kn=True)
+        gemm_group([dict(a=dkv, w=w[e:], into=dkeys)], kn=True)
         nxt = ln_bwd(dxn, inp, mean, rstd, self.norm, d_inp, next_cast, dx_in=d_src, join=join)
         return post, nxt
 
@@ -1046,8 +1029,7 @@ class XAttnExec:
 # ------------------------------------------------------------------------------------------ stacks
 # LayerNorm chaining: every executor reads (through its LayerNorm) the stream the previous executor has just updated
 # (forward) or reconstructed (backward), so that executor's residual epilogue also emits the next one's LayerNorm
-# (rtts_residual_ln).  FUSE_RESIDUAL_LN = False launches the two kernels separately.
-FUSE_RESIDUAL_LN = __import__("os").environ.get("RTTS_FUSE_RESIDUAL_LN", "1") != "0"
+# (rtts_residual_ln); the last executor of a pass has no successor and launches the plain residual epilogue.
 
 
 def _flat_calls(steps):
@@ -1077,7 +1059,7 @@ class _Chain:
 
     def args(self, i, which, inp):
         pre = self.pre if (self.pre is not None and self.ptr == inp.data_ptr()) else None
-        return dict(pre=pre, next_norm=self.next_norm.get((i, which)) if FUSE_RESIDUAL_LN else None)
+        return dict(pre=pre, next_norm=self.next_norm.get((i, which)))
 
     def done(self, post, acc):
         self.pre, self.ptr = post, (acc.data_ptr() if post is not None else None)
@@ -1086,7 +1068,7 @@ class _Chain:
     # executor that runs next in backward order; its bf16 cast + bias partial sums ride in that LayerNorm backward
     def grad_args(self, i, which, d_acc):
         pre_cast = self.cast if (self.cast is not None and self.cast_ptr == d_acc.data_ptr()) else None
-        nxt = self.next_exec.get((i, which)) if FUSE_RESIDUAL_LN else None
+        nxt = self.next_exec.get((i, which))
         # "drop" = an executor's dropout on its OUTPUT (the LSH layers' post_attn_dropout); only that one masks d_acc
         return dict(pre_cast=pre_cast, next_cast=None if nxt is None else (self.next_slot[(i, which)].get("drop"),))
 
@@ -1174,8 +1156,6 @@ class FusedStackFn(torch.autograd.Function):
                 s1 = x.detach().reshape(b * t, d)
                 s1 = s2 = s1 if s1.dtype == torch.float32 and s1.is_contiguous() else s1.float().contiguous()
             own1 = own2 = kept            # does the stream have a buffer of its own?  (kept: every update is out of place anyway)
-            if not kept and COPY_STREAMS:          # A/B switch: round 2's form, two copies of x up front
-                s1, s2, own1, own2 = s1.clone(), s1.clone(), True, True
             extra = {}
             if context is not None:
                 kpm = next((k.get("key_padding_mask") for k in kwargs_list if "key" in k), None)
@@ -1278,8 +1258,6 @@ def stack_backward_steps(ctx, dout, complete_layers: Optional[bool] = None, noti
     g1 = dout.detach().reshape(b * t, d)
     g1 = g2 = g1 if g1.dtype == torch.float32 and g1.is_contiguous() else g1.float().contiguous()
     gown1 = gown2 = False
-    if COPY_STREAMS:
-        g1, g2, gown1, gown2 = g1.clone(), g1.clone(), True, True
 
     def target(g, owned):
         """-> (buffer the executor accumulates into, its source when that differs)"""
@@ -1290,7 +1268,7 @@ def stack_backward_steps(ctx, dout, complete_layers: Optional[bool] = None, noti
         #                                  so that the taker can start on the first blocks' while the chain is still in the last ones
         steal["armed"] = True            # only the STACK's: what the prenet queues behind it stays on this stream (its event would be the
         #                                  end of the chain, and the taker would wait for that)
-    join_last = JOIN_STREAMS and steps[0][0] != "swap"
+    join_last = steps[0][0] != "swap"
 
     def joined(i):
         """The stack's LAST LayerNorm backward (block 0's f) writes d(input) = g1 + g2 itself: the other stream joins in its pass."""
@@ -1333,16 +1311,12 @@ def stack_backward_steps(ctx, dout, complete_layers: Optional[bool] = None, noti
         done.append(i)
         hook = seq.block_done_hook
         waited_for = (hook is not None and getattr(hook, "active", lambda: True)()) if complete_layers is None else bool(complete_layers)
-        if WGRAD_FLUSH_PER_LAYER or waited_for:
-            if pending_wgrads() >= flush_at or i == 0:
-                # one grouped launch per layer's worth of weight gradients; only then are the finished blocks'
-                # gradient slices final, so their all-reduce hooks run here
-                flush_wgrad(colsums=waited_for)
-                yield seq, list(done)
-                done.clear()
-        elif pending_wgrads() >= WGRAD_MAX_PENDING:
-            flush_wgrad()      # nobody waits for a block's gradients (one GPU): they go out in a few large groups at the
-            #                    end of the backward; this only bounds the operands held
+        if pending_wgrads() >= flush_at or i == 0:
+            # one grouped launch per layer's worth of weight gradients; only then are the finished blocks'
+            # gradient slices final, so their all-reduce hooks run here
+            flush_wgrad(colsums=waited_for)
+            yield seq, list(done)
+            done.clear()
     if steal is not None:
         steal["armed"] = False
     dx = (g2 if join_last else g1 + g2).view(b, t, d)

@@ -1,7 +1,6 @@
 """Top-level module (``/root/reference/reformer_tts/model/reformer_tts.py``)."""
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -10,9 +9,6 @@ import torch.nn.functional as F
 
 from .modules import DecoderPreNet, EncoderPreNet, PostConvNet, ScaledPositionalEncoding
 from .reformer import ReformerDec, ReformerEnc
-
-
-FUSED_INPUTS = os.environ.get("RTTS_FUSED_INPUTS", "1") != "0"      # A/B: the ATen sequence of _encode_inputs in the training step
 
 
 class Encoder(nn.Module):
@@ -127,7 +123,7 @@ class ReformerTTS(nn.Module):
         fused heads + postnet + loss executor (``edges.PostnetLoss``).  ``keys_hook`` (encoder output -> tensor the
         decoder reads) lets the data-parallel trainer cut the autograd graph between encoder and decoder so that the
         two halves of the backward are separate launches with a gradient all-reduce in between."""
-        fused_inputs = (FUSED_INPUTS and loss_mask is not None and spectrogram_mask is None and phonemes.is_cuda and phonemes.dtype == torch.long
+        fused_inputs = (loss_mask is not None and spectrogram_mask is None and phonemes.is_cuda and phonemes.dtype == torch.long
                         and phonemes.dim() == 2 and phonemes.stride(1) == 1 and loss_mask.dtype == torch.float32 and loss_mask.dim() == 3
                         and loss_mask.stride(2) == 1 and loss_mask.shape[1] == spectrogram.shape[1])
         if fused_inputs:

@@ -15,7 +15,6 @@ MI355X-first mechanics:
 from __future__ import annotations
 
 import math
-import os
 import time
 from typing import Dict, List, Optional
 
@@ -545,8 +544,6 @@ class Trainer:
         self.optimizer_step(update_hyper)
         return total.detach(), raw_l.detach(), post_l.detach(), stop_l.detach()
 
-    handover_encoder_wgrads = os.environ.get("RTTS_HANDOVER_WGRADS", "1") != "0"     # A/B: the encoder's weight gradients on its own stream
-
     def forward_backward_overlapped(self, batch, loss_scale=None):
         """Forward + loss + backward of one (micro-)batch in the two-stream schedule of ``train_step_overlapped``; gradients
         accumulate into the flat buffer.  ``loss_scale``: a device scalar multiplied into the loss before the backward (1 / number
@@ -565,7 +562,7 @@ class Trainer:
             gen = engine.stack_backward_steps(ctx, dec_out.grad, notify_dkeys=True)
             dx = None
             idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            steal = dict(src=(idx, side.cuda_stream), src_stream=side, pending=[]) if self.handover_encoder_wgrads else None
+            steal = dict(src=(idx, side.cuda_stream), src_stream=side, pending=[])
             while True:
                 try:
                     with torch.no_grad():
@@ -592,7 +589,7 @@ class Trainer:
             dec_x.backward(dx)                                 # decoder prenet + positional encoding
             engine.flush_wgrad()
             engine.stamp("decoder branch: backward done")
-            if steal is not None and steal["pending"]:
+            if steal["pending"]:
                 # the encoder stack's weight gradients, handed over by its stream: the main stream has nothing left to do, the
                 # encoder's chain is still running (engine.STEAL).  (The prenet's convolution weight gradients handed over the same
                 # way measured null / slightly worse -- 6.22 vs 6.24 ms, stash 5.10 vs 5.05: profiles/r04_handover_ab.log -- removed.)
@@ -1282,7 +1279,7 @@ class Trainer:
         self._finish_chain(segs, tail_main, tail_side)
         return self._graph_out
 
-    two_lane_tail = os.environ.get("RTTS_TWO_LANE_TAIL", "1") != "0"      # A/B: the encoder's graphs behind decoder layer 0's, one lane
+    two_lane_tail = True      # False (scripts/comm_overlap_probe.py): the encoder's graphs behind decoder layer 0's, one lane
 
     def _distinct_stream(self, avoid):
         """A pool stream whose handle is none of ``avoid``'s (torch.cuda.Stream() objects share 32 streams per device)."""

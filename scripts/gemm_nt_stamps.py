@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Where a rtts_gemm_nt launch spends its time (GPU box; needs the diagnostic build: scripts/build_ab.sh stamps -DGN_STAMPS
--DRTTS_GEMM_NT_AB, RTTS_LIB=.../librtts_stamps.so).  Wave 0 of every workgroup stamps the shader clock and the chip-wide
+"""Where a rtts_gemm_nt launch spends its time (GPU box; needs the diagnostic build: scripts/build_ab.sh stamps -DGN_STAMPS,
+RTTS_LIB=.../librtts_stamps.so).  Wave 0 of every workgroup stamps the shader clock and the chip-wide
 100 MHz real-time clock at: kernel entry | first stage landed | main loop done | stores issued | stores retired."""
 import os
 import sys
