@@ -543,14 +543,19 @@ typedef struct {
 } rtts_gemm_nt_problem;
 #define RTTS_GEMM_NT_MAX_GROUP 4
 int rtts_gemm_nt_grouped(const rtts_gemm_nt_problem* problems, int n, int w_is_kn, void* stream);
-/* TEST / A-B ONLY, process-wide: launch form of rtts_gemm_nt problems with several tiles per CU.  0 = the library's pick,
- * 1 = one tile per workgroup (round 3), 2 = persistent workgroups on a 2-deep ring (two per CU), 3 = persistent on the deepest
- * ring (one per CU).  10 / 11 / 12: store form of the bf16 epilogues (8-byte stores / 16-byte stores after a lane-pair exchange /
+/* TEST / A-B ONLY, process-wide: forms of the rtts_gemm_nt kernels.
+ * 10 / 11 / 12: store form of the bf16 epilogues (8-byte stores / 16-byte stores after a lane-pair exchange /
  * 16-byte write-through stores), 9: the library's pick again.  Results are identical bit for bit in every form.
  * 21 / 22: main loop of the convolutions (rtts_conv1d_k5*): the plain loop, which fetches the input rows once per tap / the convolution
  * form wherever it fits (the rows of all channel blocks stay in LDS and serve the five taps; not for the 256 x 256 tile, nor where the
- * images exceed LDS), 20: the library's pick again.  Same K order: identical bit for bit as well. */
+ * images exceed LDS), 20: the library's pick again.  Same K order: identical bit for bit as well.
+ * Every other value is refused (-1, rtts_last_error): 0..3 once chose among launch forms that no longer exist. */
 int rtts_debug_set_gemm_mode(int mode);
+/* TEST-ONLY, process-wide (one atomic word): tile of rtts_gemm_tn / rtts_gemm_tn_grouped.  0 = the library's pick (the default:
+ * what every product call gets), 1 = 128 x 128 tiles for every group, also where the library would take the 256 x 256 ring
+ * kernel; anything else is refused (-1, rtts_last_error).  Replaces the RTTS_GEMM_TN_SMALL_TILES environment variable the
+ * launch path used to read on every call. */
+int rtts_debug_set_gemm_tn_tiles(int small_tiles);
 /* FeedForward pair with a 1-bit ReLU gate: the forward GEMM (epilogue 2: bias + ReLU) also writes one 64-bit word per
  * lane and tile -- bit b set <=> the b-th output of that lane is a positive bf16 -- and the input-gradient GEMM of the same
  * (M, N) (epilogue 3, [K][N] weight) reads the words instead of re-reading the (M, N) activation (50 MB at the baseline

@@ -135,6 +135,7 @@ SIGNATURES = {
     "rtts_gemm_nt_partial_rows": [_i32, _i32],
     "rtts_gemm_nt_grouped": [C.POINTER(GemmNtProblem), _i32, _i32, _vp],
     "rtts_debug_set_gemm_mode": [_i32],
+    "rtts_debug_set_gemm_tn_tiles": [_i32],
     "rtts_gemm_nt_gate_words": [_i32, _i32],
     "rtts_gemm_nt_gated": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _vp, _vp],
     "rtts_peak_copy": [_vp, _vp, _i64, _vp],

@@ -22,14 +22,12 @@
 //     columns of one row: the epilogue stores 8 bytes per lane straight from the accumulators, bias / gate are 16 / 8-byte loads;
 //   * XCD-aware tile order: the N/BN tiles that share an A row panel run on one XCD back to back (one fetch of the panel
 //     from HBM / Infinity Cache per XCD, the weight stays resident in every L2).
-// Three launch forms of the same body (template MODE):
-//   0  one problem, one tile per workgroup (the form every small problem keeps);
+// Two launch forms of the same body, plus the convolution form of its main loop (template MODE; 2 was the persistent form,
+// removed: DESIGN.md 5f).  Every form runs one tile per workgroup:
+//   0  one problem;
 //   1  GROUPED: one grid over the tiles of up to GN_MAX_GROUP independent problems of one layout and epilogue (the cross-attention's
 //      q and k|v projections; its input-gradient pair dxn / dkeys): a workgroup looks its problem up by tile range -- one launch
 //      ramp, one tail and one kernel boundary instead of one per problem;
-//   2  PERSISTENT: problems of several tiles per CU (N >= 1024 at M = 12288) run on a grid of resident workgroups that walk the
-//      tiles; the LDS ring keeps turning across a tile boundary -- the first NST stages of the next tile are in flight while the
-//      current tile's accumulators are stored -- so the 1.8 us launch-to-first-stage latency is paid once per workgroup, not per tile.
 //   3  CONVOLUTION (conv_cpt > 0, where the images fit LDS; not 256 x 256): the input rows [m0 - 2, m0 + BM + 2) of all channel
 //      blocks stay in LDS, one image per 64-channel block, and the five taps read them at five row shifts -- the plain loop brings
 //      the same BM x 64 block of rows in once per tap.  K order and results are the plain loop's, bit for bit; the stages of taps
@@ -42,7 +40,6 @@
 // separate rtts_lsh_bwd_delta launch and its re-read of dout are gone).
 #include "rtts_common.h"
 #include "conv_taps.h"
-#include <stdlib.h>
 #include <atomic>
 
 typedef __attribute__((ext_vector_type(4))) int gn_v4i;
@@ -178,12 +175,9 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     }
     const GnArgs& P = G.p[pi];
     const int ntn = P.N / BN;
-    int m0 = (int)(tile / ntn) * BM, n0 = (int)(tile % ntn) * BN;
+    const int m0 = (int)(tile / ntn) * BM, n0 = (int)(tile % ntn) * BN;
     const int nk = P.K / GN_BK;
     const int64_t lda = P.lda, ldw = P.ldw;
-    // MODE 2: this workgroup works tiles tile, tile + gridDim.x, ... of the one problem
-    const uint32_t ntiles = MODE == 2 ? (uint32_t)(P.M / BM) * (uint32_t)ntn : 0u;
-    (void)ntiles;
 
     // ---- DMA sources: ONE per-lane pointer per operand (the wave's piece 0 of stage 0).  Piece t of a wave is 8 NW t rows
     // further on ([row][k] images; (1024 / RP) NW t k rows for the [K][N] weight image) -- a wave-uniform offset -- and needs
@@ -208,10 +202,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     const size_t pstepA = (size_t)8 * NW * lda, pstepW = W_KN ? (size_t)(1024 / RP) * NW * ldw : (size_t)8 * NW * ldw;
     const size_t wstep = W_KN ? (size_t)GN_BK * ldw : (size_t)GN_BK;
     const int conv_cpt = P.conv_cpt;
-    // MODE 2: element offsets from this tile's operand rows to the next tile's (wave-uniform); stages >= nk name the next tile
-    int64_t nxtA = 0, nxtW = 0;
-    bool has_next = false, first_tile = true;
-    (void)nxtA; (void)nxtW; (void)has_next; (void)first_tile;
     // element offsets of K stage `st` into the A rows / the weight (wave-uniform scalar arithmetic)
     auto a_off = [&](int st) -> int64_t {
         if (conv_cpt == 0) return (int64_t)st * GN_BK;
@@ -303,16 +293,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     auto issue_piece = [&](auto qc, int stage_, int bufi_) {
         constexpr int q = decltype(qc)::value;
         unsigned char* sb_ = smem + bufi_ * STAGE;
-        int64_t ka_, kw_;
-        if constexpr (MODE == 2) {             // a stage index beyond this tile's last stage: the next tile's stage (stage_ - nk)
-            const bool nx_ = stage_ >= nk;
-            const int st_ = nx_ ? stage_ - nk : stage_;
-            ka_ = a_off(st_) + (nx_ ? nxtA : 0);
-            kw_ = w_off(st_) + (nx_ ? nxtW : 0);
-        } else {
-            ka_ = a_off(stage_);
-            kw_ = w_off(stage_);
-        }
+        const int64_t ka_ = a_off(stage_), kw_ = w_off(stage_);
         if constexpr (q < PA)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA0 + q * pstepA + ka_),
                                              (RTTS_LDS void*)(sb_ + (wave + NW * q) * 1024), 16, 0, 0);
@@ -369,17 +350,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
     if constexpr (MODE != 3) GN_READ(a0, w0, wl0, wh0, smem_base, 0);
     int buf = 0;
     int pbuf = 0;                                    // buffer of stage s-1: the second half of stage s-1+NST's pieces goes there
-    static_assert(MODE != 2 || (EPI != 4 && true), "persistent form: bf16 epilogues");
-  for (;;) {                                         // MODE 2: one pass per tile of this workgroup; else a single pass
-    if constexpr (MODE == 2) {
-        const uint32_t nt_ = tile + gridDim.x;
-        has_next = nt_ < ntiles;
-        if (has_next) {
-            const int m0n = (int)(nt_ / ntn) * BM, n0n = (int)(nt_ % ntn) * BN;
-            nxtA = (int64_t)(m0n - m0) * lda;
-            nxtW = W_KN ? (int64_t)(n0n - n0) : (int64_t)(n0n - n0) * ldw;
-        }
-    }
+    static_assert(MODE == 0 || MODE == 1 || MODE == 3, "launch forms: 0 one problem, 1 grouped, 3 convolution main loop");
     if constexpr (MODE == 3) {
         // ---- CONVOLUTION FORM (conv_cpt > 0, where gn_conv_fits()): the input rows [m0 - 2, m0 + BM + 2) of ALL conv_cpt channel
         // blocks stay in LDS -- one image per channel block, conv_taps.h has the piece -> row arithmetic, checked on the CPU -- and the
@@ -491,19 +462,16 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
         // reads per half stage (the 256-wide tile's transposed weight fragments) "at most 15 outstanding" already implies it
         gn_wait_lgkm<(RD_PER_KS < 15 ? RD_PER_KS : 15)>();
         __builtin_amdgcn_sched_barrier(0);
-        // MODE 2: the ring does not stop at a tile boundary -- stage indices >= nk are the next tile's first stages (issue_piece),
-        // the second half of the stage whose first half the previous tile's last step issued goes out at s = 0
-        GN_MFMA(a0, w0, wl0, wh0, MODE == 2 ? ((s >= 1 || !first_tile) && (s - 1 + NST < nk || has_next)) : (s >= 1 && s - 1 + NST < nk),
-                s - 1 + NST, pbuf, SPB, PER);
+        GN_MFMA(a0, w0, wl0, wh0, s >= 1 && s - 1 + NST < nk, s - 1 + NST, pbuf, SPB, PER);
         __builtin_amdgcn_sched_barrier(0);
         gn_wait_lgkm<0>();                           // F1 is back: this wave has no read of stage s left
-        if (s + 1 < nk || (MODE == 2 && has_next)) {
-            GN_WAIT_STAGE((MODE == 2 && has_next) ? NST - 2 : min(NST - 2, nk - 2 - s));
+        if (s + 1 < nk) {
+            GN_WAIT_STAGE(min(NST - 2, nk - 2 - s));
             asm volatile("s_barrier" ::: "memory");  // stage s+1 complete in LDS; everybody is done reading stage s
             GN_READ(a0, w0, wl0, wh0, smem_base + nb * STAGE, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
-        GN_MFMA(a1, w1, wl1, wh1, s + NST < nk || (MODE == 2 && has_next), s + NST, buf, 0, SPB);    // (implies: behind the barrier)
+        GN_MFMA(a1, w1, wl1, wh1, s + NST < nk, s + NST, buf, 0, SPB);    // (implies: behind the barrier)
         __builtin_amdgcn_sched_barrier(0);
         pbuf = buf;
         buf = nb;
@@ -700,22 +668,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
                 if (r == 0) *reinterpret_cast<f32x4*>(dst + pl * P.N + ncol + 16 * j) = v;
             }
     }
-    if constexpr (MODE != 2) break;
-    else {
-        if (!has_next) break;
-        // next tile: the ring already holds (or has in flight) its first stages, F0 of its stage 0 is in a0 / w0
-        tile += gridDim.x;
-        m0 = (int)(tile / ntn) * BM;
-        n0 = (int)(tile % ntn) * BN;
-        srcA0 += nxtA;
-        srcW0 += nxtW;
-        first_tile = false;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  }
 #undef GN_READ
 #undef GN_READ_W
 #undef GN_MFMA
@@ -742,20 +694,17 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 192 && NST == 2) ? 4 : 1) void
 template <int BM, int BN>
 constexpr int gn_nst() { return (4 * (BM + BN) * 128 <= 160 * 1024) ? 4 : ((3 * (BM + BN) * 128 <= 160 * 1024) ? 3 : 2); }
 
-// TEST / A-B ONLY (rtts_debug_set_gemm_mode): how problems of several tiles per CU are launched.  0 = the library's pick,
-// 1 = never persistent (round 3's forms), 2 = persistent on a 2-deep ring, two workgroups per CU, 3 = persistent on the
-// deepest ring, one workgroup per CU.  Process-wide, atomic; no environment is read on the launch path.
-static std::atomic<int> g_gn_mode{0};
+// TEST / A-B ONLY (rtts_debug_set_gemm_mode): the store form of the bf16 epilogues and the main loop of the convolutions.
+// Process-wide, atomic; no environment is read on the launch path.
 static std::atomic<int> g_gn_store{-1};
 static std::atomic<int> g_gn_conv{0};            // main loop of the convolutions: see gn_conv_form()
 extern "C" int rtts_debug_set_gemm_mode(int mode) {
-    // 0..3: launch form (see above); 10 + s: store form s of the bf16 epilogues (0 = 8-byte, 1 = 16-byte, 2 = 16-byte write-through),
-    // 9 = the library's pick of the store form again
+    // 10 + s: store form s of the bf16 epilogues (0 = 8-byte, 1 = 16-byte, 2 = 16-byte write-through), 9 = the library's pick of
+    // the store form again; 20..22: see gn_conv_form().  (0..3 chose among launch forms that are gone: DESIGN.md 5f.)
     if (mode >= 9 && mode <= 12) { g_gn_store.store(mode - 10, std::memory_order_relaxed); return 0; }
     if (mode >= 20 && mode <= 22) { g_gn_conv.store(mode - 20, std::memory_order_relaxed); return 0; }
-    if (mode < 0 || mode > 3) { rtts_set_error("rtts_debug_set_gemm_mode: 0..3, 9..12 or 20..22 (got %d)", mode); return -1; }
-    g_gn_mode.store(mode, std::memory_order_relaxed);
-    return 0;
+    rtts_set_error("rtts_debug_set_gemm_mode: 9..12 or 20..22 (got %d)", mode);
+    return -1;
 }
 // MEASURED (profiles/r04_gemm_nt_store_forms_ab.log, one box, interleaved, us per launch inside a replayed graph):
 //   M = 12288, N x K = 512 x 512: 12.9 (8-byte) / 11.7 (16-byte) / 10.3 (16-byte write-through);  1024 x 512: 20.7 / 18.3 / 15.6;
@@ -805,22 +754,9 @@ static int gn_launch2(const GnGroup& G, hipStream_t s) {
             return gn_launch3<BM, BN, WM, WN, W_KN, EPI, GN_CONV_NST, 3>(G, tiles, s);
     }
     if constexpr (BM == 192 && BN == 128 && EPI != 4 && EPI != 5 && EPI != 7) {
-        // Several tiles per CU (N >= 1024 at M = 12288: 512 / 1024 tiles).  Round 3 launched them all, two workgroups per CU on a
-        // 2-deep ring, so that one workgroup's prologue / epilogue fills with the other's MFMAs (N = 2048, K = 512: 37.4 vs 45.5 us
-        // on the deep ring; profiles/r02_gemm_nt_probe.log).  Round 4: a grid of RESIDENT workgroups walks the tiles (MODE 2)
-        // and the ring keeps turning across the tile boundary -- measured forms in profiles/r04_gemm_nt_persistent_ab.log.
-        const int mode = g_gn_mode.load(std::memory_order_relaxed);
-        const bool multi = tiles >= 512 && tiles % 256 == 0 && P.K / GN_BK >= NST && P.conv_cpt == 0;
-        // MEASURED (profiles/r04_gemm_nt_persistent_ab.log, one box, interleaved): the persistent forms LOSE -- N = 2048, K = 512:
-        // 41.0 us one tile per workgroup, 44.9 persistent on the 2-deep ring, 49.8 on the deep ring; N = 1024: 20.3 / 21.3 / 24.2.
-        // Two co-resident workgroups already hide each other's prologue and epilogue, the dispatcher re-fills a CU slot the moment a
-        // workgroup retires (its stores drain while the successor's first stage loads), and a resident workgroup has to wait for its
-        // own epilogue stores before the counted vmcnt of its next tile's second stage.  The library's pick stays round 3's form;
-        // the persistent forms remain selectable (bit-identical results: tests/test_gemm_hip.py) for A/B runs on other shapes.
-        if (multi && mode >= 2) {
-            if (mode == 3) return gn_launch3<BM, BN, WM, WN, W_KN, EPI, NST, 2>(G, 256, s);
-            return gn_launch3<BM, BN, WM, WN, W_KN, EPI, 2, 2>(G, 512, s);
-        }
+        // Several tiles per CU (N >= 1024 at M = 12288: 512 / 1024 tiles): two workgroups per CU on a 2-deep ring, so that one
+        // workgroup's prologue / epilogue fills with the other's MFMAs (N = 2048, K = 512: 37.4 vs 45.5 us on the deep ring;
+        // profiles/r02_gemm_nt_probe.log).  A grid of resident workgroups that walk the tiles lost to it: DESIGN.md 5f.
         if (tiles >= 512) return gn_launch3<BM, BN, WM, WN, W_KN, EPI, 2, 0>(G, tiles, s);
     }
     return gn_launch3<BM, BN, WM, WN, W_KN, EPI, NST, 0>(G, tiles, s);
@@ -873,9 +809,8 @@ static int gn_launch_group(const GnGroup& G, int total_tiles, int w_kn, hipStrea
 #define GN_NCAND 5
 static const int gn_cand[GN_NCAND][3] = {{256, 256, 4}, {192, 128, 4}, {256, 128, 4}, {96, 64, 2}, {128, 64, 2}};   // BM, BN, WM
 static int gn_pick(int M, int N) {
-    static const int no256 = [] { const char* e = getenv("RTTS_GEMM_NT_NO256"); return e ? atoi(e) : 0; }();      // A/B runs
     int best = -1;
-    for (int i = (no256 ? 1 : 0); i < GN_NCAND; ++i) {
+    for (int i = 0; i < GN_NCAND; ++i) {
         if (M % gn_cand[i][0] || N % gn_cand[i][1]) continue;
         const int wgs = (M / gn_cand[i][0]) * (N / gn_cand[i][1]);
         if (i == 0 && wgs % 256 != 0) continue;   // 256 x 256: whole waves only

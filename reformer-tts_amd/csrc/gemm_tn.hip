@@ -19,12 +19,11 @@
 // together.  One grid then holds 240 tiles instead of 16..64, the split factor drops from 8..32 to 2, and the fp32
 // slab traffic (split x output size, written and read back) drops ~7x; per-launch ramp-up and tails are paid once.
 #include "rtts_common.h"
-#include <stdlib.h>
+#include <atomic>
 
 #define GT_BM 64       // contraction rows per stage
-#ifndef GT_PAD
 #define GT_PAD 64      // bytes of padding per LDS row: a row shift of 16 banks, so the 4 rows x 16 dwords of a 32-lane
-#endif                 // transposed read (ds_read_b64_tr_b16 is served in two 32-lane groups over 64 banks) hit 64 distinct
+                       // transposed read (ds_read_b64_tr_b16 is served in two 32-lane groups over 64 banks) hit 64 distinct
                        // banks; 32 B of pad left them 2-way conflicted (130.6 -> 127.7 us per decoder-layer group)
 
 struct GtProb {
@@ -49,7 +48,8 @@ struct GtGroup {
 // rate of one per 8 clk per CU:
 //   <2,2,2,2>: 128 x 128, 256 threads, 2 workgroups per CU -- any shape that tiles by 128; 1 KB per MFMA = LDS-bound
 //              (measured ~600 TFLOP/s, a 4 x 4-wave 256-tile variant with the same 2 x 2 register tile just as slow)
-//   <4,2,2,4>: 256 x 256, 512 threads, 1 workgroup per CU, 128 accumulator registers -- 0.75 KB per MFMA
+//   <4,2,2,4>: 256 x 256, 512 threads, 1 workgroup per CU, 128 accumulator registers -- 0.75 KB per MFMA: launched as the
+//              ring variant below only (gemm_tn_ring_kernel); this kernel is instantiated for 128 x 128
 template <int WN, int WK, int TN, int TK>
 __global__ __launch_bounds__(64 * WN * WK) void gemm_tn_kernel(const GtGroup grp) {
     constexpr int BN = 32 * TN * WN, BK = 32 * TK * WK, NTHR = 64 * WN * WK;
@@ -202,9 +202,7 @@ __global__ __launch_bounds__(64 * WN * WK) void gemm_tn_kernel(const GtGroup grp
 // chunks of a row XOR-swizzled with (row & 3) on the SOURCE side so that the transposed fragment reads (4 consecutive rows
 // x 64 B) stay bank-conflict free.
 #define GT_RS 32       // rows per ring stage
-#ifndef GT_NST
 #define GT_NST 4       // ring depth
-#endif
 
 template <int WN, int WK, int TN, int TK>
 __global__ __launch_bounds__(64 * WN * WK) void gemm_tn_ring_kernel(const GtGroup grp) {
@@ -428,12 +426,24 @@ static bool gt_c_overlap(const rtts_gemm_tn_problem& p, const rtts_gemm_tn_probl
     return s + hi.K > lo.ldc && r + 1 < lo.N;                // hi's rows wrap round into column 0 of lo's next rows
 }
 
+// Test-only: 1 = 128 x 128 tiles for every group, ring-sized ones included (tests run both kernels on one set of operands);
+// 0 = the library's pick, what every product call gets.  Process-wide and atomic; the launch path reads one word and no environment.
+static std::atomic<int> g_gt_small{0};
+extern "C" int rtts_debug_set_gemm_tn_tiles(int small_tiles) {
+    if (small_tiles != 0 && small_tiles != 1) {
+        rtts_set_error("rtts_debug_set_gemm_tn_tiles: 0 (library's pick) or 1 (128 x 128 tiles for every group) (got %d)", small_tiles);
+        return -1;
+    }
+    g_gt_small.store(small_tiles, std::memory_order_relaxed);
+    return 0;
+}
+
 extern "C" int rtts_gemm_tn_grouped(const rtts_gemm_tn_problem* problems, int n, float* slab_ws, int64_t slab_ws_floats, void* stream) {
     RTTS_ENTER(stream);
     RTTS_REQUIRE(problems && n > 0 && n <= RTTS_GEMM_TN_MAX_GROUP, "rtts_gemm_tn_grouped: 1..%d problems", RTTS_GEMM_TN_MAX_GROUP);
     GtGroup grp;
     grp.n = n;
-    bool big = getenv("RTTS_GEMM_TN_SMALL_TILES") == nullptr;     // 256 x 256 tiles when every problem tiles by 256
+    bool big = g_gt_small.load(std::memory_order_relaxed) == 0;   // 256 x 256 tiles (the ring kernel) when every problem tiles by 256
     long long flops = 0;
     for (int i = 0; i < n; ++i) {
         const rtts_gemm_tn_problem& q = problems[i];
@@ -455,8 +465,7 @@ extern "C" int rtts_gemm_tn_grouped(const rtts_gemm_tn_problem* problems, int n,
     // small groups cannot fill 256 CUs with 256 x 256 tiles without splitting the token range very finely
     // (measured: one 25.8 GFLOP problem 45 us with 128-tiles / 50 us with 256-tiles; the 87 GFLOP group of a decoder
     // layer 143 us / 127 us)
-    static const long long big_min = [] { const char* e = getenv("RTTS_GEMM_TN_BIG_MIN_GFLOP"); return (e ? atoll(e) : 40LL) * 1000000000LL; }();
-    if (flops < big_min) big = false;
+    if (flops < 40LL * 1000000000LL) big = false;
     const int bt = big ? 256 : 128;
     int total_tiles = 0;
     for (int i = 0; i < n; ++i) total_tiles += (problems[i].N / bt) * (problems[i].K / bt);
@@ -495,14 +504,11 @@ extern "C" int rtts_gemm_tn_grouped(const rtts_gemm_tn_problem* problems, int n,
         }
     }
     hipStream_t s = (hipStream_t)stream;
-    static const bool ring = getenv("RTTS_GEMM_TN_NO_RING") == nullptr;
-    if (big && ring) {
+    if (big) {
         const size_t lds = 2 * GT_NST * GT_RS * 512;
         static RttsLdsState st = {};
         RTTS_ENSURE_LDS("rtts_gemm_tn", (gemm_tn_ring_kernel<4, 2, 2, 4>), lds, st);
         hipLaunchKernelGGL((gemm_tn_ring_kernel<4, 2, 2, 4>), dim3(wg), dim3(512), lds, s, grp);
-    } else if (big) {
-        if (gt_launch<4, 2, 2, 4>(grp, wg, s)) return -1;
     } else if (gt_launch<2, 2, 2, 2>(grp, wg, s)) return -1;
     if (any_split) hipLaunchKernelGGL(slab_reduce_kernel, dim3(rb), dim3(256), 0, s, grp);
     RTTS_LAUNCH_CHECK("rtts_gemm_tn");

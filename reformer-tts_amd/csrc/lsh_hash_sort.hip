@@ -19,15 +19,10 @@
 // per-(wave, bucket) running offsets live in LDS -- O(log n_buckets) wave ops per group instead of O(n_buckets).
 #include "rtts_common.h"
 #include "attn_tile.h"   // AT_PADB
-#include <stdlib.h>
 
 #define HS_DH 64
-#ifndef HS_PF32
 #define HS_PF32 1
-#endif
-#ifndef HS_W8_MIN_T
-#define HS_W8_MIN_T 2048   // sequences from this length on get 8 waves per (head, round)
-#endif
+#define HS_W8_MIN_T 2048   // the sort of the two-launch form: sequences from this length on get 8 waves per (head, round)
 
 template <int HALF>
 __device__ __forceinline__ int hash_row(const float* q, const float* rot_lds, int half) {
@@ -483,9 +478,11 @@ static int launch_hash_then_sort(const bf16_t* qk, int64_t ld, const float* rot,
     return 0;
 }
 
-template <int HALF, int WAVES>
-static int launch_hash_sort_w(const bf16_t* qk, int64_t ld, const float* rot, int rot_rows, int B, int H, int T,
-                              int n_hashes, int32_t* buckets, int32_t* st, int32_t* undo, int half, hipStream_t stream) {
+// the one-launch kernel serves T < 1024 only (rtts_lsh_hash_sort_launches): 4 waves per (head, round)
+template <int HALF>
+static int launch_hash_sort(const bf16_t* qk, int64_t ld, const float* rot, int rot_rows, int B, int H, int T,
+                            int n_hashes, int32_t* buckets, int32_t* st, int32_t* undo, int half, hipStream_t stream) {
+    constexpr int WAVES = 4;
     const size_t lds = ((HS_DH * HALF * 4 + 15) & ~15) + WAVES * 64 * AT_PADB + ((T * 2 + 15) & ~15) + (WAVES * 64 + 64) * 4;
     static RttsLdsState lds_state = {};
     RTTS_ENSURE_LDS("rtts_lsh_hash_sort", (lsh_hash_sort_kernel<HALF, WAVES>), lds, lds_state);
@@ -496,23 +493,8 @@ static int launch_hash_sort_w(const bf16_t* qk, int64_t ld, const float* rot, in
     return 0;
 }
 
-// 4 waves per (head, round) for short sequences; 8 from T = 2048 on (one workgroup still owns a whole sort, and a
-// long row has enough tokens to keep 8 waves = 2 per SIMD busy through the fmaf chains)
-template <int HALF>
-static int launch_hash_sort(const bf16_t* qk, int64_t ld, const float* rot, int rot_rows, int B, int H, int T,
-                            int n_hashes, int32_t* buckets, int32_t* st, int32_t* undo, int half, hipStream_t stream) {
-    if (T >= HS_W8_MIN_T && T % 256 == 0)
-        return launch_hash_sort_w<HALF, 8>(qk, ld, rot, rot_rows, B, H, T, n_hashes, buckets, st, undo, half, stream);
-    return launch_hash_sort_w<HALF, 4>(qk, ld, rot, rot_rows, B, H, T, n_hashes, buckets, st, undo, half, stream);
-}
-
-static int hs_use_v1() {
-    static const int v1 = [] { const char* e = getenv("RTTS_HASH_SORT_V1"); return e ? atoi(e) : 0; }();      // A/B runs: the one-launch kernel
-    return v1;
-}
-
 // how rtts_lsh_hash_sort works a sequence length: 2 = lsh_hash_rounds_kernel + lsh_sort_ids_kernel, 1 = lsh_hash_sort_kernel
-extern "C" int rtts_lsh_hash_sort_launches(int T) { return (!hs_use_v1() && T >= 1024) ? 2 : 1; }
+extern "C" int rtts_lsh_hash_sort_launches(int T) { return T >= 1024 ? 2 : 1; }
 
 extern "C" int rtts_lsh_hash_sort(const void* qk, int64_t ld_qk, const float* rotations, int rot_rows, int B, int H,
                                   int T, int dh, int n_hashes, int bucket_size, int32_t* buckets, int32_t* st,

@@ -6,7 +6,6 @@
 //                    matrix rate the chip sustains at the clock it holds under that load
 // Neither is on the training path.
 #include "rtts_common.h"
-#include <stdlib.h>
 
 // FOUR 16-byte loads in flight per thread before the first store (one in flight -- round 3's probe -- reached 4.8 TB/s where
 // MI355X_MICROARCH.md measures 6.29 TB/s for a float4 copy: a probe that understates the peak flatters every "fraction of the
@@ -98,7 +97,7 @@ extern "C" int rtts_debug_stamp(void* buf, int slot, void* stream) {
 extern "C" int rtts_peak_copy(const void* src, void* dst, int64_t bytes, void* stream) {
     RTTS_ENTER(stream);
     RTTS_REQUIRE(src && dst && bytes > 0 && bytes % 16 == 0, "rtts_peak_copy: bytes must be a positive multiple of 16");
-    static const int grid = [] { const char* e = getenv("RTTS_PEAK_COPY_GRID"); return e ? atoi(e) : 16384; }();     // probe tuning only (1024: 5.27, 8192: 5.59, 32768: 5.67 TB/s on one box)
+    const int grid = 16384;                      // workgroups (measured on one box: 1024: 5.27, 8192: 5.59, 32768: 5.67 TB/s)
     hipLaunchKernelGGL(peak_copy_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float4*)src, (float4*)dst, (size_t)bytes / 16);
     RTTS_LAUNCH_CHECK("rtts_peak_copy");
     return 0;

@@ -29,9 +29,7 @@
 #define DN_SPAN ((DN_FT - 1) * DN_HOP + DN_NFFT)                  // samples the frames of a tile cover
 #define DN_FR_LD (DN_NFFT + 1)                                    // row stride of the resynthesised frames: 32 frames on 32 banks
 #define DN_W2_AT (DN_FT * DN_FR_LD)                               // the squared window sits behind every image
-#ifndef DN_U
 #define DN_U 8                                                    // k-pairs per block of the A operand (two blocks in registers)
-#endif
 #define DN_LDS_BYTES ((size_t)(DN_W2_AT + DN_NFFT) * sizeof(float))
 
 static_assert(DN_SPAN + DN_SPAN / DN_HOP + 4 <= DN_W2_AT && DN_NFFT * DN_FT <= DN_W2_AT, "the span and the spectrum lie below the window");

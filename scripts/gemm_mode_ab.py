@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""A/B of the launch forms of csrc/gemm_nt.hip in ONE process on one box (interleaved rounds, medians):
-  * several tiles per CU: one tile per workgroup (round 3) vs persistent workgroups on the 2-deep / the deep ring;
+"""A/B of the forms of csrc/gemm_nt.hip in ONE process on one box (interleaved rounds, medians):
+  * the store forms of the bf16 epilogues: 8-byte, 16-byte, 16-byte write-through;
   * the cross-attention's q | kv projections and dxn | dkeys input gradients: two launches (+ the add) vs one grouped launch;
   * the to_out input gradient + rtts_lsh_bwd_delta vs the delta epilogue.
-    python scripts/gemm_mode_ab.py > gpurun_out/r04_gemm_nt_persistent_ab.log"""
+(The persistent launch forms this script also timed are gone: DESIGN.md 5f, profiles/r04_gemm_nt_persistent_ab.log.)
+    python scripts/gemm_mode_ab.py > gemm_nt_forms_ab.log"""
 import os
 import statistics
 import sys
@@ -50,37 +51,6 @@ def ab(title, variants, rounds=5, flop=None):
                                     for k, v in res.items())
     print(line, flush=True)
 
-
-# ---- persistent tiles
-for m, n, k, kind in ((12288, 2048, 512, "bias+relu"), (12288, 1024, 512, "plain"), (12288, 2048, 512, "kn+gate"), (12288, 1024, 512, "kn"),
-                      (12288, 512, 2048, "plain"), (12288, 512, 512, "plain")):
-    a = rnd(m, k).bfloat16()
-    w = rnd(n, k, scale=k ** -0.5).bfloat16()
-    wkn = w.t().contiguous()
-    bias = rnd(n)
-    words = engine.gate_words(m, n, dev)
-    if kind == "kn+gate":
-        engine.gemm(a, w, bias=bias, relu=True, words=words)
-
-    def call():
-        if kind == "plain":
-            engine.gemm(a, w)
-        elif kind == "kn":
-            engine.gemm(a, wkn, kn=True)
-        elif kind == "bias+relu":
-            engine.gemm(a, w, bias=bias, relu=True, words=words)
-        else:
-            engine.gemm(a, wkn, kn=True, gate=True, words=words)
-
-    def variant(mode):
-        def run():
-            _lib.call("rtts_debug_set_gemm_mode", mode)
-            try:
-                return timed(call)
-            finally:
-                _lib.call("rtts_debug_set_gemm_mode", 0)
-        return run
-    ab(f"M={m} N={n} K={k} {kind:9s}", {"one tile/WG": variant(1), "persistent 2-deep x2": variant(2), "persistent deep x1": variant(3)}, flop=2.0 * m * n * k)
 
 # ---- store forms of the bf16 epilogues: inside a chain (the consumer of a GEMM's output is the next launch: what a dirty L2 costs
 #      shows at the kernel boundary, so the GEMM is timed together with a streaming reader of its output)

@@ -2,20 +2,19 @@
 recipes both it and tests/test_gemm_nt_plan_cpu.py use.  No GPU and no library is needed to import or call anything here.
 
 What is restated, with the lines of csrc/gemm_nt.hip it follows:
-  gn_nst(bm, bn)            741-743   ring depth: as many 64-deep K stages of both operands as 160 KB of LDS hold, at most 4
-  gn_store_mode(c, ldc)     781-785   16-byte (write-through) stores need a 16-byte aligned C and ldc % 8 == 0, else 8-byte stores
-  gn_launch2                797-827   192 x 128: >= 512 tiles -> 2-deep ring (not for the fp32 / delta epilogues); `multi` and the
-                                      debug modes 2 / 3 -> persistent grid of 512 on the 2-deep resp. 256 on the deep ring
-  gn_launch                 829-849   which epilogues each layout takes
-  gn_launch_group           853-866   groups: 192 x 128 with more than 256 tiles -> 2-deep ring (`two`)
-  gn_pick(M, N)             873-889   the tile of a single problem
-  rtts_gemm_nt_partial_rows 891-894,  rtts_gemm_nt_gate_words 1038-1042
-  rtts_gemm_nt_grouped      978-985   the tile of epilogue 5;  998-1024 the tile of a group, its tile_end and `spread`
+  gn_nst(bm, bn)            693-695   ring depth: as many 64-deep K stages of both operands as 160 KB of LDS hold, at most 4
+  gn_store_mode(c, ldc)     730-734   16-byte (write-through) stores need a 16-byte aligned C and ldc % 8 == 0, else 8-byte stores
+  gn_launch2                746-763   192 x 128: >= 512 tiles -> 2-deep ring (not for the fp32 / delta epilogues)
+  gn_launch                 765-785   which epilogues each layout takes
+  gn_launch_group           789-802   groups: 192 x 128 with more than 256 tiles -> 2-deep ring (`two`)
+  gn_pick(M, N)             809-824   the tile of a single problem
+  rtts_gemm_nt_partial_rows 826-829,  rtts_gemm_nt_gate_words 973-977
+  rtts_gemm_nt_grouped      913-920   the tile of epilogue 5;  933-959 the tile of a group, its tile_end and `spread`
 OUT OF SCOPE: the convolution forms (conv_cpt > 0: launch form 3, gn_conv_form) and epilogue 7; tests/test_conv_taps_hip.py owns
 them.  Everything here is a plain GEMM: conv_cpt == 0.
 
-A path tag reads  "<BM>x<BN><WM,WN> NST<n> form<0|1|2> <NT|KN> epi<e> st<s>[ spread<0|1>]":
-  form   0 one tile per workgroup, 1 grouped, 2 persistent
+A path tag reads  "<BM>x<BN><WM,WN> NST<n> form<0|1> <NT|KN> epi<e> st<s>[ spread<0|1>]":
+  form   0 one problem, 1 grouped (one tile per workgroup in both)
   epi    0 plain, 1 bias, 2 bias + ReLU, 2w the same writing gate words, 3 ReLU gate from the activation, 3w from the words,
          4 fp32, 4b fp32 + bias, 4a fp32 accumulated into C, 5 input gradient + delta, 6 a group's run-time choice of 0 / 1 / 4
   st     the store form of a bf16 output (0 8-byte, 1 16-byte, 2 16-byte write-through), "f" for an fp32 output; a group lists
@@ -27,10 +26,10 @@ CAND = [(256, 256, 4), (192, 128, 4), (256, 128, 4), (96, 64, 2), (128, 64, 2)] 
 GN_MAX_GROUP = 4
 
 
-def gn_pick(m, n, no256=False):
-    """Index into CAND of the tile a single (M, N) problem takes, or -1 (gn_pick, 873-889)."""
+def gn_pick(m, n):
+    """Index into CAND of the tile a single (M, N) problem takes, or -1 (gn_pick, 809-824)."""
     best = -1
-    for i in range(1 if no256 else 0, len(CAND)):
+    for i in range(len(CAND)):
         bm, bn, _ = CAND[i]
         if m % bm or n % bn:
             continue
@@ -86,13 +85,13 @@ NT_EPIS = ("0", "1", "2", "2w", "4", "4b", "4a")
 KN_EPIS = ("0", "3", "3w", "4", "4b", "4a", "5")
 
 
-def nt_plan(m, n, k, kn=False, epi="0", c_addr=0, ldc=None, mode=0, forced_store=-1):
+def nt_plan(m, n, k, kn=False, epi="0", c_addr=0, ldc=None, forced_store=-1):
     """The path of ONE plain problem through rtts_gemm_nt / rtts_gemm_nt_gated / rtts_gemm_nt_grouped(n = 1).  ``epi`` as in the
-    module docstring; ``mode`` what rtts_debug_set_gemm_mode(0..3) left; ``c_addr``, ``ldc`` where C lies.  -> path tag."""
+    module docstring; ``c_addr``, ``ldc`` where C lies.  -> path tag."""
     epi = str(epi)
     assert k > 0 and k % 64 == 0 and epi in (KN_EPIS if kn else NT_EPIS), (k, kn, epi)
     ldc = n if ldc is None else ldc
-    if epi == "5":                                                       # 978-985
+    if epi == "5":                                                       # 913-920
         assert kn
         if m % 192 == 0 and n % 128 == 0 and (m // 192) * (n // 128) >= 192:
             bm, bn, wm, wn = 192, 128, 4, 2
@@ -109,24 +108,14 @@ def nt_plan(m, n, k, kn=False, epi="0", c_addr=0, ldc=None, mode=0, forced_store
         if epi in ("2w", "3w") and i == 0:
             raise ValueError("256 x 256 has no gate words")
         (bm, bn, wm), wn = CAND[i], 2
-    nst, form = gn_nst(bm, bn), 0
-    tiles = (m // bm) * (n // bn)
-    if (bm, bn) == (192, 128) and epi[0] not in "45":                    # 807-825
-        multi = tiles >= 512 and tiles % 256 == 0 and k // 64 >= nst
-        if multi and mode >= 2:
-            form, nst = 2, (nst if mode == 3 else 2)
-        elif tiles >= 512:
-            nst = 2
-    return _tag(bm, bn, wm, wn, nst, form, kn, epi, _st(epi, c_addr, ldc, forced_store))
-
-
-def persistent_walk(m, n, mode):
-    """Tiles one workgroup of the persistent form walks (grid 512 on the 2-deep ring, 256 on the deep one)."""
-    return (m // 192) * (n // 128) // (512 if mode == 2 else 256)
+    nst = gn_nst(bm, bn)
+    if (bm, bn) == (192, 128) and epi[0] not in "45" and (m // bm) * (n // bn) >= 512:      # 756-761
+        nst = 2
+    return _tag(bm, bn, wm, wn, nst, 0, kn, epi, _st(epi, c_addr, ldc, forced_store))
 
 
 def group_plan(problems, kn=False, forced_store=-1):
-    """rtts_gemm_nt_grouped with n > 1.  ``problems``: (M, N, K, epi, c_addr, ldc) each -> (path tag, tile_end).  998-1024, 853-866."""
+    """rtts_gemm_nt_grouped with n > 1.  ``problems``: (M, N, K, epi, c_addr, ldc) each -> (path tag, tile_end).  933-959, 789-802."""
     assert 2 <= len(problems) <= GN_MAX_GROUP
 
     def tiles_by(bm, bn):
@@ -158,23 +147,23 @@ def group_plan(problems, kn=False, forced_store=-1):
 def reachable_plain_tags():
     """Every path tag a plain single problem can take, enumerated from the STRUCTURE of the dispatcher (which tile has which
     ring depths, launch forms, epilogues and store forms), not from the case list:
-      * 192 x 128 runs its deep ring below 512 tiles, the 2-deep ring from 512 tiles on (bf16 epilogues only), and the two
-        persistent forms under the debug modes; every other tile has one ring depth and form 0;
-      * 256 x 256 has no gate words; epilogue 5 runs on 192 x 128 <4,2> and on 128 x 64 as <4,1>, deep ring, form 0;
+      * 192 x 128 runs its deep ring below 512 tiles and the 2-deep ring from 512 tiles on (bf16 epilogues only); every other
+        tile has one ring depth; a single problem is form 0;
+      * 256 x 256 has no gate words; epilogue 5 runs on 192 x 128 <4,2> and on 128 x 64 as <4,1>, deep ring;
       * a bf16 output is stored in form 2 (aligned) or 0 (not), and in form 1 on request."""
     tags = set()
     for i, (bm, bn, wm) in enumerate(CAND):
-        rings = [(gn_nst(bm, bn), 0)]
+        rings = [gn_nst(bm, bn)]
         for kn, epis in ((False, NT_EPIS), (True, KN_EPIS)):
             for epi in epis:
                 if epi == "5" or (i == 0 and epi.endswith("w")):
                     continue
                 r = list(rings)
                 if (bm, bn) == (192, 128) and epi[0] != "4":
-                    r += [(2, 0), (2, 2), (4, 2)]
-                for nst, form in r:
+                    r.append(2)
+                for nst in r:
                     for st in (("f",) if epi[0] == "4" else ("0", "1", "2")):
-                        tags.add(_tag(bm, bn, wm, 2, nst, form, kn, epi, st))
+                        tags.add(_tag(bm, bn, wm, 2, nst, 0, kn, epi, st))
     for bm, bn, wm, wn in ((192, 128, 4, 2), (128, 64, 4, 1)):
         for st in ("0", "1", "2"):
             tags.add(_tag(bm, bn, wm, wn, 4, 0, True, "5", st))
@@ -186,13 +175,14 @@ def _nks(nst):
     return sorted({1, nst - 1, nst, nst + 1, 2 * nst + 1})
 
 
-# name (goes into the test id) -> what the case runs.  ``shapes``: (M, N) each; ``nks``: K = 64 nk; ``mode``: launch-form debug
-# modes to run; ``delta``: the T of an epilogue-5 run per shape (None: the shape runs the plain epilogues)
+# name (goes into the test id) -> what the case runs.  ``shapes``: (M, N) each; ``nks``: K = 64 nk; ``delta``: the T of an
+# epilogue-5 run per shape (None: the shape runs the plain epilogues).  "192x128_persistent" keeps the name it had when it also ran
+# the persistent launch forms: 1024 tiles (four per CU) on the 2-deep ring, at K of 4, 5 and 9 stages
 CASES = {
     "256x256_nst2": dict(shapes=[(8192, 2048)], nks=_nks(2), tile=(256, 256), nst=2),
     "192x128_nst4": dict(shapes=[(3072, 1536)], nks=_nks(4), tile=(192, 128), nst=4),
     "192x128_nst2": dict(shapes=[(6144, 2048)], nks=_nks(2), tile=(192, 128), nst=2),
-    "192x128_persistent": dict(shapes=[(6144, 4096)], nks=[4, 5, 9], tile=(192, 128), nst=2, modes=(1, 2, 3)),
+    "192x128_persistent": dict(shapes=[(6144, 4096)], nks=[4, 5, 9], tile=(192, 128), nst=2),
     "256x128_nst3": dict(shapes=[(4096, 1536)], nks=_nks(3), tile=(256, 128), nst=3),
     "96x64_nst4": dict(shapes=[(96, 64), (192, 128), (288, 64), (1536, 768)], nks=_nks(4), tile=(96, 64), nst=4),
     "128x64_nst4": dict(shapes=[(128, 64), (384, 256), (2048, 768)], nks=_nks(4), tile=(128, 64), nst=4),
@@ -220,17 +210,16 @@ def case_tags(name, nk):
         for pl, off, pad, dbg in PLACEMENTS:
             forced = dbg - 10 if dbg >= 10 else -1
             if "delta" in c:
-                tags.add(nt_plan(m, n, k, True, "5", off, n + pad, 0, forced))
+                tags.add(nt_plan(m, n, k, True, "5", off, n + pad, forced))
                 continue
             words = gate_words(m, n) > 0
-            for mode in c.get("modes", (0,)):
-                for kn, epis in ((False, SINGLE_NT + GROUPED_N1_NT), (True, SINGLE_KN + GROUPED_N1_KN)):
-                    for epi in epis:
-                        if epi.endswith("w") and not words:
-                            continue
-                        if epi[0] == "4" and off:
-                            continue                     # an fp32 C is 16-byte aligned by contract
-                        tags.add(nt_plan(m, n, k, kn, epi, off, n + pad, mode, forced))
+            for kn, epis in ((False, SINGLE_NT + GROUPED_N1_NT), (True, SINGLE_KN + GROUPED_N1_KN)):
+                for epi in epis:
+                    if epi.endswith("w") and not words:
+                        continue
+                    if epi[0] == "4" and off:
+                        continue                     # an fp32 C is 16-byte aligned by contract
+                    tags.add(nt_plan(m, n, k, kn, epi, off, n + pad, forced))
     return tags
 
 
@@ -351,7 +340,7 @@ def normal_ratio(got, ref, scale, bf16):
 
 # ------------------------------------------------------------------------------------------ the gate words' lane -> element map
 def decode_gate_words(words, m, n):
-    """(M, N) bool from the words epilogue 2 writes, by the map documented at kBitsFit (csrc/gemm_nt.hip:537-542, 513, 129): word
+    """(M, N) bool from the words epilogue 2 writes, by the map documented at kBitsFit (csrc/gemm_nt.hip:505-510, 481, 126): word
     (tile_m * (N / BN) + tile_n) * 64 WM WN + tid, tid = 64 (wm * WN + wn) + 16 g + r; bit (i * TN + j) * 4 + e <=> row
     tile_m BM + wm (BM / WM) + 16 i + r, column tile_n BN + wn (BN / WN) + 16 j + 4 g + e.  -> (mask, are all bits
     from 4 TM TN upwards clear)."""

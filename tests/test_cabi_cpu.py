@@ -32,6 +32,43 @@ def test_library_exports_every_declared_symbol():
     assert lib.rtts_version() == 1
 
 
+def test_library_sources_read_no_environment():
+    """the library reads no environment variable, on a launch path or anywhere else -- test-only choices
+    arrive through the rtts_debug_set_* exports."""
+    csrc = os.path.join(ROOT, "reformer-tts_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert len(files) >= 20
+    assert [f for f in files if "getenv" in open(os.path.join(csrc, f)).read()] == []
+
+
+def test_debug_setters_refuse_what_they_do_not_know():
+    """Host-only calls: rtts_debug_set_gemm_tn_tiles takes 0 and 1; rtts_debug_set_gemm_mode no longer takes the launch forms
+    0..3 (it keeps 9..12 and 20..22).  A refusal returns -1 and leaves a message that names the value."""
+    import __graft_entry__
+    __graft_entry__.build()
+    from reformer_tts_amd import _lib
+    lib = _lib.load()
+    try:
+        assert lib.rtts_debug_set_gemm_tn_tiles(1) == 0
+        assert lib.rtts_debug_set_gemm_tn_tiles(0) == 0
+        for bad in (2, -1):
+            assert lib.rtts_debug_set_gemm_tn_tiles(bad) == -1
+            msg = lib.rtts_last_error().decode()
+            assert "rtts_debug_set_gemm_tn_tiles" in msg and f"got {bad}" in msg
+        with pytest.raises(_lib.RttsError, match="rtts_debug_set_gemm_tn_tiles"):
+            _lib.call("rtts_debug_set_gemm_tn_tiles", 2)
+        for mode in (0, 1, 2, 3):
+            assert lib.rtts_debug_set_gemm_mode(mode) == -1
+            msg = lib.rtts_last_error().decode()
+            assert "rtts_debug_set_gemm_mode" in msg and f"got {mode}" in msg
+        for mode in (10, 11, 12, 9, 21, 22, 20):
+            assert lib.rtts_debug_set_gemm_mode(mode) == 0
+    finally:
+        lib.rtts_debug_set_gemm_tn_tiles(0)
+        lib.rtts_debug_set_gemm_mode(9)
+        lib.rtts_debug_set_gemm_mode(20)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from reformer_tts_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

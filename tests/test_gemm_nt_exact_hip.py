@@ -26,17 +26,17 @@ term alone for fp32) -- fractional bits, which the integers cannot exercise.
 The reference's gated product SELECTS (gate open ? product : +0.0), as the kernel does: product * mask would hold -0.0 under a closed
 gate and a negative product -- an artefact of the multiplication, and the comparison here is of bits.
 
-PATH TAGS COVERED (format: gemm_nt_plan's docstring).  All 198 tags of gemm_nt_plan.reachable_plain_tags() -- the list is
+PATH TAGS COVERED (format: gemm_nt_plan's docstring).  All 156 tags of gemm_nt_plan.reachable_plain_tags() -- the list is
 ``sorted(gemm_nt_plan.all_case_tags())`` -- that is, for each layout and each of its epilogues (NT: 0 1 2 2w 4 4b 4a; KN: 0 3 3w 4 4b
 4a; no words on 256 x 256), with every bf16 epilogue in the store forms st0, st1 and st2 and every fp32 one in stf:
   256x256<4,2> NST2 form0        192x128<4,2> NST4 form0        192x128<4,2> NST2 form0 (512 and 1024 tiles)
-  192x128<4,2> NST2 form2 (two tiles per workgroup) and NST4 form2 (four)        256x128<4,2> NST3 form0
-  96x64<2,2> NST4 form0          128x64<2,2> NST4 form0
+  256x128<4,2> NST3 form0        96x64<2,2> NST4 form0          128x64<2,2> NST4 form0
   192x128<4,2> NST4 form0 KN epi5 (the large grid and the small-grid branch)       128x64<4,1> NST4 form0 KN epi5
 and the 18 group tags (form1, epi6, both layouts): 192x128 NST4 spread1 / NST2 spread1 / NST2 spread0 / NST4 spread0, 96x64 spread1 /
 spread0 (twice: three and four members), 128x64 spread1 / spread0.
 MEASURED on an MI355X (written down after the run, not targets):
-  cases: 41 (path, nk) cases with 18,704 checks between them, 18 group cases, 1 refusal case, 7 normal-input cases: 67 tests;
+  cases: 41 (path, nk) cases (18,704 checks between them while the three 1024-tile cases also ran the persistent launch forms
+  that are gone since, DESIGN.md 5f; those cases now run once), 18 group cases, 1 refusal case, 7 normal-input cases: 67 tests;
   wall time of this file: 4.0 s (pytest's total; the slowest test 0.6 s, the first one, which loads the kernels);
   normal-input pass, worst |err| / bound over the bf16 epilogues (and over the fp32 ones) per tile:
     256x256 0.983 (0.009)   192x128 NST4 0.979 (0.008)   192x128 NST2 0.985 (0.009)   256x128 0.982 (0.008)   96x64 0.979 (0.008)
@@ -192,7 +192,7 @@ def _grouped(members, kn):
 
 
 class _Modes:
-    """rtts_debug_set_gemm_mode for the length of a block; the library's picks (0, 9) again on the way out."""
+    """rtts_debug_set_gemm_mode (store forms 9..12) for the length of a block; the library's pick (9) again on the way out."""
 
     def __init__(self, *modes):
         self.modes = modes
@@ -204,7 +204,6 @@ class _Modes:
 
     def __exit__(self, *exc):
         from reformer_tts_amd import _lib
-        _lib.call("rtts_debug_set_gemm_mode", 0)
         _lib.call("rtts_debug_set_gemm_mode", 9)
         return False
 
@@ -236,7 +235,7 @@ def _expected_bf16(o):
             "3h": e["gated_h"].to(bf), "3w": e["gated_h"].to(bf)}
 
 
-def _run_plain(chk, dev, o, mode=0):
+def _run_plain(chk, dev, o):
     """Every epilogue of a plain problem in every placement of C.  -> number of launches."""
     from reformer_tts_amd import _lib
     m, n, k, e = o.m, o.n, o.k, o.e
@@ -251,9 +250,9 @@ def _run_plain(chk, dev, o, mode=0):
     for name, off, pad, dbg in P.PLACEMENTS:
         pl = _Place(dev, m, n, name, off, pad)
         forced = dbg - 10 if dbg >= 10 else -1
-        with _Modes(mode, dbg):
+        with _Modes(dbg):
             def tag(kn, epi, win):
-                t = P.nt_plan(m, n, k, kn, epi, win.ptr, win.ld, mode, forced)
+                t = P.nt_plan(m, n, k, kn, epi, win.ptr, win.ld, forced)
                 if epi[0] != "4":
                     assert t.endswith("st" + P.EXPECTED_STORE[name]), (t, name)
                 return f"{t} | {name}"
@@ -333,8 +332,8 @@ def _run_delta(chk, dev, o):
     for name, off, pad, dbg in P.PLACEMENTS:
         pl = _Place(dev, m, n, name, off, pad)
         forced = dbg - 10 if dbg >= 10 else -1
-        with _Modes(0, dbg):
-            tag = f"{P.nt_plan(m, n, k, True, '5', pl.c16.ptr, pl.c16.ld, 0, forced)} T={t} | {name}"
+        with _Modes(dbg):
+            tag = f"{P.nt_plan(m, n, k, True, '5', pl.c16.ptr, pl.c16.ld, forced)} T={t} | {name}"
             assert tag.split(" T=")[0].endswith("st" + P.EXPECTED_STORE[name])
             _single(o, True, "0", pl.c16)
             plain, clean = pl.c16.take()
@@ -363,8 +362,7 @@ def test_gemm_nt_exact_on_integers(gpu, name, nk):
         if t is not None:
             _run_delta(chk, gpu, o)
         else:
-            for mode in c.get("modes", (0,)):
-                launches += _run_plain(chk, gpu, o, mode)
+            launches += _run_plain(chk, gpu, o)
         del o
     torch.cuda.synchronize()
     print(f"\n[gemm_nt exact {name} nk={nk}] {chk.n} checks, {len(chk.bad)} failed")

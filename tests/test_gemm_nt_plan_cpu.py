@@ -52,11 +52,6 @@ def test_case_list_reaches_every_plain_path():
                 tag = P.nt_plan(m, n, 64 * nk, True, "5" if "delta" in c else "0")
                 want_nst = 4 if "delta" in c else c["nst"]
                 assert tag.startswith(f"{c['tile'][0]}x{c['tile'][1]}<") and f" NST{want_nst} form0 " in tag, (name, m, n, nk, tag)
-    m, n = P.CASES["192x128_persistent"]["shapes"][0]
-    for nk in P.CASES["192x128_persistent"]["nks"]:
-        assert " NST2 form2 " in P.nt_plan(m, n, 64 * nk, False, "0", mode=2) and " NST4 form2 " in P.nt_plan(m, n, 64 * nk, False, "0", mode=3)
-    assert (P.persistent_walk(m, n, 2), P.persistent_walk(m, n, 3)) == (2, 4)
-    assert " NST2 form0 " in P.nt_plan(m, n, 192, False, "0", mode=2), "below the ring depth the persistent form is not taken"
     assert "<4,1>" in P.nt_plan(512, 128, 64, True, "5") and "<4,1>" in P.nt_plan(384, 256, 64, True, "5")
     for mn in ((192, 128), (576, 256)):
         assert P.nt_plan(*mn, 64, True, "5").startswith("192x128<4,2> NST4"), mn

@@ -16,8 +16,6 @@ Two references in every case, both in float64 on the same bf16 operands:
 Each run also checks that nothing outside C's (N, K) window -- its padding columns (ldc > K), guard bands before and after it,
 the slab workspace beyond what the call was given -- changed (a NaN bit pattern there), and that two runs of a normal-input
 group are bitwise equal."""
-import os
-
 import pytest
 import torch
 
@@ -40,14 +38,14 @@ def gpu():
 
 # ------------------------------------------------------------------------------------------ the dispatcher, restated
 def tn_plan(shapes, ws_floats, small_tiles=False):
-    """Restates the host logic of ``rtts_gemm_tn_grouped`` (csrc/gemm_tn.hip:445-516, from ``bool big = ...`` to the launches):
-    256 x 256 tiles when no RTTS_GEMM_TN_SMALL_TILES, every N and K % 256 == 0 and the group reaches RTTS_GEMM_TN_BIG_MIN_GFLOP
-    (default 40); one split target ``want`` for the group (the smallest power of two with tiles x 2 want > 320 resp. 640); per
+    """Restates the host logic of ``rtts_gemm_tn_grouped`` (csrc/gemm_tn.hip:446-513, from ``bool big = ...`` to the launches):
+    256 x 256 tiles (the ring kernel) unless rtts_debug_set_gemm_tn_tiles(1) is in force (``small_tiles``), when every N and
+    K % 256 == 0 and the group reaches 40 GFLOP; one split target ``want`` for the group (the smallest power of two with tiles x 2 want > 320 resp. 640); per
     problem split doubles up to ``want`` while split x 2 <= (M / 64) / 4, then halves while the slab workspace cannot hold it
     (``ws_floats`` None = slab_ws NULL).  ``shapes``: (M, N, K) per problem -> (kernel, [split per problem], slab floats used).
     If the dispatcher changes, test_case_list_covers_every_dispatch_path fails here instead of a path going untested."""
     big = not small_tiles and all(n % 256 == 0 and k % 256 == 0 for _, n, k in shapes)
-    if sum(2 * m * n * k for m, n, k in shapes) < int(os.environ.get("RTTS_GEMM_TN_BIG_MIN_GFLOP", "40")) * 10 ** 9:
+    if sum(2 * m * n * k for m, n, k in shapes) < 40 * 10 ** 9:
         big = False
     bt = 256 if big else 128
     tiles = sum((n // bt) * (k // bt) for _, n, k in shapes)
@@ -64,8 +62,7 @@ def tn_plan(shapes, ws_floats, small_tiles=False):
         if split > 1:
             used += n * k * split
         splits.append(split)
-    kernel = ("ring" if os.environ.get("RTTS_GEMM_TN_NO_RING") is None else "tile256") if big else "tile128"
-    return kernel, splits, used
+    return ("ring" if big else "tile128"), splits, used
 
 
 def P(m, n, k, acc=1, pa=0, pb=0, pc=0):
@@ -80,7 +77,7 @@ _WS_GROUP = [P(3072, 512, 512, 1), P(3072, 512, 512, 0), P(3072, 512, 512, 1)]  
 # a group the ring kernel takes (45 GFLOP, every N, K % 256 == 0) that also holds an M = 64 problem (two 32-row ring stages:
 # fewer than the three the ring keeps in flight) and an M = 128 one (four stages: the counted waits 2, 2, 1, 0)
 _RING_GROUP = [P(12288, 1024, 512, 1), P(12288, 2048, 512, 0), P(12288, 512, 512, 1), P(64, 256, 256, 1), P(128, 512, 256, 1)]
-# (name, problems, workspace floats | FULL | None, RTTS_GEMM_TN_SMALL_TILES)
+# (name, problems, workspace floats | FULL | None, rtts_debug_set_gemm_tn_tiles(1) in force)
 CASES = [
     ("t128_split1", [P(256, 128, 128, 0)], FULL, False),
     ("t128_split16_rem11", [P(64 * 75, 128, 128, 1)], FULL, False),        # 75 stages over 16 runs: the first 11 one stage longer
@@ -208,8 +205,9 @@ def _operands(problems, ints, seed, dev, row_scale=False):
     return out
 
 
-def _launch(ops, ws):
-    """One rtts_gemm_tn_grouped call over ``ops`` -> (results as float64, C and workspace untouched outside the windows)."""
+def _launch(ops, ws, small=False):
+    """One rtts_gemm_tn_grouped call over ``ops`` (``small``: under rtts_debug_set_gemm_tn_tiles(1), the library's pick again on
+    the way out) -> (results as float64, C and workspace untouched outside the windows)."""
     from reformer_tts_amd import _lib
     dev = ops[0][0].device
     cbufs = [_CBuf(a.shape[1], b.shape[1], pc, c0) for a, b, c0, _, pc in ops]
@@ -220,8 +218,12 @@ def _launch(ops, ws):
     for e, (a, b, _, acc, _), cb in zip(arr, ops, cbufs):
         e.a, e.lda, e.b, e.ldb, e.c, e.ldc = a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), cb.c.data_ptr(), cb.ld
         e.M, e.N, e.K, e.accumulate = a.shape[0], a.shape[1], b.shape[1], acc
-    _lib.call("rtts_gemm_tn_grouped", arr, len(ops), None if wsb is None else wsb.data_ptr(), 0 if ws is None else ws,
-              torch.cuda.current_stream().cuda_stream)
+    _lib.call("rtts_debug_set_gemm_tn_tiles", int(small))
+    try:
+        _lib.call("rtts_gemm_tn_grouped", arr, len(ops), None if wsb is None else wsb.data_ptr(), 0 if ws is None else ws,
+                  torch.cuda.current_stream().cuda_stream)
+    finally:
+        _lib.call("rtts_debug_set_gemm_tn_tiles", 0)
     torch.cuda.synchronize()
     clean = all(cb.untouched() for cb in cbufs) and (wsb is None or bool((wsb[ws:] == NAN_BITS).all()))
     return [cb.c.double() for cb in cbufs], clean
@@ -243,24 +245,20 @@ def _ratio(got, ref, scale):
     return ((got - ref).abs() / scale).max().item()
 
 
-def _run_case(problems, ws, small, monkeypatch):
-    if small:
-        monkeypatch.setenv("RTTS_GEMM_TN_SMALL_TILES", "1")        # read by the library on every call
-    else:
-        monkeypatch.delenv("RTTS_GEMM_TN_SMALL_TILES", raising=False)
+def _run_case(problems, ws, small):
     kernel, splits, _, ws_f = _plan(problems, ws, small)
     return kernel, splits, ws_f
 
 
 # ------------------------------------------------------------------------------------------ the cases
 @pytest.mark.parametrize("name,problems,ws,small", CASES, ids=_IDS)
-def test_gemm_tn_exact_on_integers(gpu, monkeypatch, name, problems, ws, small):
+def test_gemm_tn_exact_on_integers(gpu, name, problems, ws, small):
     """Bit-exact against the float64 product of integer operands (see the module docstring for why every path must be)."""
     for m, *_ in problems:
         assert m * 16 + 64 < 2 ** 24, "partial sums must stay exact in fp32"
-    kernel, splits, ws_f = _run_case(problems, ws, small, monkeypatch)
+    kernel, splits, ws_f = _run_case(problems, ws, small)
     ops = _operands(problems, True, 1, gpu)
-    got, clean = _launch(ops, ws_f)
+    got, clean = _launch(ops, ws_f, small)
     bad = []
     for i, (g, (ref, _)) in enumerate(zip(got, _refs(ops))):
         if not torch.equal(g, ref):
@@ -274,13 +272,13 @@ def test_gemm_tn_exact_on_integers(gpu, monkeypatch, name, problems, ws, small):
 
 
 @pytest.mark.parametrize("name,problems,ws,small", CASES, ids=_IDS)
-def test_gemm_tn_float64_bound_and_determinism(gpu, monkeypatch, name, problems, ws, small):
+def test_gemm_tn_float64_bound_and_determinism(gpu, name, problems, ws, small):
     """bf16 N(0,1) operands: max |got - ref| / (|dY|^T |X| + |C0|) <= 2^-16 per problem, two runs bitwise equal.  At the largest
     M of the case list the same criterion must reject the reference with one token row's outer product removed."""
-    kernel, splits, ws_f = _run_case(problems, ws, small, monkeypatch)
+    kernel, splits, ws_f = _run_case(problems, ws, small)
     ops = _operands(problems, False, 2, gpu)
-    got1, clean1 = _launch(ops, ws_f)
-    got2, clean2 = _launch(ops, ws_f)
+    got1, clean1 = _launch(ops, ws_f, small)
+    got2, clean2 = _launch(ops, ws_f, small)
     refs = _refs(ops)
     ratios = [_ratio(g, r, s) for g, (r, s) in zip(got1, refs)]
     print(f"\n[gemm_tn {name}] {kernel}, splits {splits}: max |err| / scale {max(ratios):.3e} (bound {BOUND:.3e} = 2^-16)")
@@ -299,12 +297,12 @@ def test_gemm_tn_float64_bound_and_determinism(gpu, monkeypatch, name, problems,
 
 
 @pytest.mark.parametrize("name", ["t128_split16_rem11", "ring_group_short_runs"])
-def test_gemm_tn_float64_bound_with_rows_scaled(gpu, monkeypatch, name):
+def test_gemm_tn_float64_bound_with_rows_scaled(gpu, name):
     """Token rows of dY and X scaled by 2^-6 / 1 / 2^6 (out of step): the elementwise bound holds where magnitudes mix."""
     _, problems, ws, small = next(c for c in CASES if c[0] == name)
-    kernel, splits, ws_f = _run_case(problems, ws, small, monkeypatch)
+    kernel, splits, ws_f = _run_case(problems, ws, small)
     ops = _operands(problems, False, 3, gpu, row_scale=True)
-    got, clean = _launch(ops, ws_f)
+    got, clean = _launch(ops, ws_f, small)
     ratios = [_ratio(g, r, s) for g, (r, s) in zip(got, _refs(ops))]
     print(f"\n[gemm_tn {name}, rows scaled 2^+-6] {kernel}, splits {splits}: max |err| / scale {max(ratios):.3e} (bound {BOUND:.3e})")
     assert clean
@@ -373,7 +371,6 @@ def test_product_groups_replayed_exactly(gpu, monkeypatch):
     """The launches a decoder layer's and an encoder block's backward make, replayed with fresh integer operands of the same
     shapes and strides (slab workspace of the product's size): bit-exact, nothing outside C touched."""
     from reformer_tts_amd import engine
-    monkeypatch.delenv("RTTS_GEMM_TN_SMALL_TILES", raising=False)
     groups = _product_groups(gpu, monkeypatch)
     n = 0
     for where, launches in groups.items():
