@@ -267,6 +267,31 @@ int rtts_sum_slabs(const void* part, int nslabs, int64_t n, void* out, void* str
  * ReformerTTS.forward reformer_tts.py:103-143).  Envelope of rtts_xattn_fwd. */
 int rtts_xattn_probs_mean(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
                           const float* lse, int B, int H, int Tq, int Tk, int dh, float* a, int64_t ld_a, void* stream);
+/* Guided attention loss as a term of the TRAINING loss (Tachibana et al.; DC-TTS, ESPnet).  Not in the reference: it adds to
+ * the cross-attention of reference reformer_tts/model/reformer.py:161-186, which only collects the matrices in eval mode.
+ *   P = the probabilities of rtts_xattn_fwd before their dropout;  W[b,t,k] = 1 - exp(-(k / K_b - t / T_b)^2 / (2 sigma^2)) for
+ *   t < T_b and k < K_b, else 0 (the w of rtts_align_stats, table column [5]);  rows[b,h,t] = sum_k P W (0 for t >= T_b);
+ *   loss = sum_{b,h,t} rows / (H sum_b T_b): the mean off-diagonal mass per valid frame, in [0, 1].
+ *   n_frames, n_keys i32 (B) on the device: T_b, K_b.  A slot with T_b outside 1..Tq or K_b outside 1..Tk counts in neither
+ *   sum; if none counts, the loss and c are 0.
+ * rtts_xattn_guide_rows: rows f32 (B*H, Tq) from q, kv, kvalid and the lse of rtts_xattn_fwd; one fixed summation order.
+ * rtts_xattn_guide_fold: out f64 (B+1): out[b] = sum_{h,t} rows / (H T_b) (0 for a slot that does not count), out[B] = the loss;
+ *   c_dev f32 (1) = c = coef / (H sum_b T_b), coef = the weight the loss term carries into the backward.  f64 sums in a fixed
+ *   order, one launch: a second call gives the same bits.
+ * rtts_xattn_bwd_guided: rtts_xattn_bwd with dS = P o (keep o dP + c W - (delta + c rows)) / sqrt(dh): the gradient of
+ *   sum(o . dout) + coef * loss.  dv is that of rtts_xattn_bwd; the guided term is not multiplied by the dropout keep-scale.
+ * Envelope of rtts_xattn_fwd.  A null pointer (kvalid, seed_dev and dq_chunks aside), a bad stride or sigma <= 0 is rejected
+ * by the argument's name before any launch; nothing is read by the host, so all three can be captured. */
+int rtts_xattn_guide_rows(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const float* lse,
+                          const int32_t* n_frames, const int32_t* n_keys, int B, int H, int Tq, int Tk, int dh, double sigma,
+                          float* rows, void* stream);
+int rtts_xattn_guide_fold(const float* rows, const int32_t* n_frames, const int32_t* n_keys, int B, int H, int Tq, int Tk,
+                          double coef, double* out, float* c_dev, void* stream);
+int rtts_xattn_bwd_guided(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid,
+                          const void* dout, int64_t ld_dout, const float* lse, const float* delta,
+                          int B, int H, int Tq, int Tk, int dh, void* dq, int64_t ld_dq, void* dkv_part,
+                          float drop_p, uint32_t seed, const uint32_t* seed_dev, void* dq_chunks, const float* guide_rows,
+                          const float* c_dev, const int32_t* n_frames, const int32_t* n_keys, double sigma, void* stream);
 
 /* ---- dense shared-QK attention (use_full_attn / T <= full_attn_thres of the LSH layer) -------------------
  * What reformer_pytorch's LSHSelfAttention computes on its FullQKAttention branch; the layer is built at reference

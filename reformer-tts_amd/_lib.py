@@ -91,6 +91,10 @@ SIGNATURES = {
     "rtts_xattn_key_chunks": [_i32],
     "rtts_xattn_bwd_key_chunks": [_i32, _i32],
     "rtts_xattn_probs_mean": [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
+    "rtts_xattn_guide_rows": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp],
+    "rtts_xattn_guide_fold": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp],
+    "rtts_xattn_bwd_guided": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _f32, _u32, _vp, _vp,
+                              _vp, _vp, _vp, _vp, C.c_double, _vp],
     "rtts_sum_slabs": [_vp, _i32, _i64, _vp, _vp],
     "rtts_full_attn_max_t": [_i32],
     "rtts_full_attn_fwd": [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _f32, _u32, _vp, _vp],

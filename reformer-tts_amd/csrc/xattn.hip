@@ -223,14 +223,50 @@ __global__ __launch_bounds__(256) void xattn_fwd_kernel(const bf16_t* __restrict
 // DH = 128 is instantiated for TK = 128 only (rtts_xattn_bwd_key_chunks): four waves of 32 keys hold dK and dV in 2 x 64 fp32 per
 // lane, the accumulator count of a 64-key wave at DH = 64, and the images are K 32 KB + Q, dout 2 x 32 KB + dS^T 32 KB + 1 KB of
 // lse / delta = 129 KB of the CU's 160 KB (TK = 256 would need 64 + 64 + 64 KB).  DH = 64: 65 KB (TK = 128), 129 KB (TK = 256).
-template <int DH, int TK, bool DROP>
+//
+// GUIDE (training with a guided attention loss, rtts_xattn_bwd_guided): the loss c sum P o W is linear in P, so its gradient is
+// one more term of the dS line, dS = P o (keep o dP + c W - (delta + c rows)) / sqrt(dh), with rows = rowsum(P o W) from
+// rtts_xattn_guide_rows and c from rtts_xattn_guide_fold.  GUIDE = false compiles every guided statement away under `if constexpr`
+// and its argument is an empty struct: the unguided kernels keep their statements and their register, LDS and occupancy figures.
+template <bool GUIDE> struct XaGuide {};
+template <> struct XaGuide<true> {     // arguments of the guided form only
+    const float* __restrict__ rows;    // (B * H, Tq) rowsum(P o W)
+    const float* __restrict__ c_dev;   // c = coef / (H sum_b T_b)
+    const int32_t* __restrict__ n_frames;   // T_b
+    const int32_t* __restrict__ n_keys;     // K_b
+    float g;                           // 1 / (sqrt(2) sigma): w = 1 - exp(-((k / K - t / T) g)^2)
+};
+// does slot b count?  T_b in 1..Tq and K_b in 1..Tk
+__device__ __forceinline__ bool xg_slot(const int32_t* __restrict__ n_frames, const int32_t* __restrict__ n_keys, int b, int Tq, int Tk,
+                                        int& T, int& K) {
+    T = n_frames[b];
+    K = n_keys[b];
+    return T >= 1 && T <= Tq && K >= 1 && K <= Tk;
+}
+// w(t, k) = 1 - exp(-y), y = (k g / K - t g / T)^2, from kk = k g / K, t and sT = g / T: one fma and one exp2.  Near the diagonal
+// (y < 1/4) 1 - exp(-y) cancels -- its absolute error stays 2^-24 while w goes to 0, and a sharp, well aligned row is all such
+// cells -- so there the series y - y^2/2 + ... - y^6/720 stands in (next term y^7/5040: 2^-24 relative at y = 1/4).  The rows
+// kernel and the backward share this function: c (W - rows) must cancel to the last bit where a row is one-hot.
+__device__ __forceinline__ float xg_w(float kk, float t, float sT) {
+    const float dd = __builtin_fmaf(t, -sT, kk);
+    const float y = dd * dd;
+    const float far = 1.f - __builtin_amdgcn_exp2f(y * -1.4426950408889634f);
+    float near = __builtin_fmaf(y, -1.f / 720.f, 1.f / 120.f);
+    near = __builtin_fmaf(y, near, -1.f / 24.f);
+    near = __builtin_fmaf(y, near, 1.f / 6.f);
+    near = __builtin_fmaf(y, near, -0.5f);
+    near = __builtin_fmaf(y, near, 1.f);
+    return y < 0.25f ? y * near : far;
+}
+
+template <int DH, int TK, bool DROP, bool GUIDE>
 __global__ __launch_bounds__(TK * 2) void xattn_bwd_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
                                                        int64_t ld_kv, const uint8_t* __restrict__ kvalid,
                                                        const bf16_t* __restrict__ dout, int64_t ld_do, const float* __restrict__ lse,
                                                        const float* __restrict__ delta, int H, int Tq, int TKtot, bf16_t* __restrict__ dq,
                                                        int64_t ld_dq, size_t dq_chunk_stride, bf16_t* __restrict__ dkv_part, int B,
                                                        uint32_t seed, const uint32_t* __restrict__ seed_dev, uint32_t thresh,
-                                                       float dscale) {
+                                                       float dscale, const XaGuide<GUIDE> gd) {
     // blockIdx.y = key chunk: this workgroup owns keys [kc0, kc0 + TK) of TKtot.  P = exp(s - lse) needs only the forward's
     // global lse, so the chunks are independent: dK/dV of the chunk are complete for this query block, dQ is the chunk's
     // share (dq_chunk_stride elements between the chunks' partial dQ arrays; one chunk: dq itself)
@@ -286,9 +322,22 @@ __global__ __launch_bounds__(TK * 2) void xattn_bwd_kernel(const bf16_t* __restr
                                                  (RTTS_LDS void*)(Os + pl * QPL + rowb * 128), 16, 0, 0););
         }
     }
+    // GUIDE: this sample's T_b, K_b and c (0 for a slot that does not count: every guided term is then exactly 0)
+    float gc = 0.f, gsT = 0.f, gsK = 0.f;
+    int gT = 0, gK = 0;
+    if constexpr (GUIDE) {
+        if (xg_slot(gd.n_frames, gd.n_keys, b, Tq, TKtot, gT, gK)) {
+            gc = gd.c_dev[0];
+            gsT = gd.g / (float)gT;
+            gsK = gd.g / (float)gK;
+        } else {
+            gT = gK = 0;
+        }
+    }
     for (int j = tid; j < XA_QB; j += NTHR) {
         qlse[j] = lse[(size_t)bh * Tq + qb * XA_QB + j] * 1.4426950408889634f;   // base-2 softmax: exp2(s * c - lse * log2 e)
-        qdel[j] = delta[(size_t)bh * Tq + qb * XA_QB + j];
+        if constexpr (GUIDE) qdel[j] = delta[(size_t)bh * Tq + qb * XA_QB + j] + gc * gd.rows[(size_t)bh * Tq + qb * XA_QB + j];
+        else qdel[j] = delta[(size_t)bh * Tq + qb * XA_QB + j];
     }
     int myrow[KT2];
 #pragma unroll
@@ -304,6 +353,17 @@ __global__ __launch_bounds__(TK * 2) void xattn_bwd_kernel(const bf16_t* __restr
         }
         kvl[k2] = kvalid ? (int)kvalid[(size_t)b * TKtot + kc0 + myrow[k2]] : 1;
     }
+    // GUIDE: the lane's key is a constant of the kernel: k g / K_b, and c (0 for a key at or past K_b)
+    float gkk[KT2], gck[KT2];
+    if constexpr (GUIDE) {
+#pragma unroll
+        for (int k2 = 0; k2 < KT2; ++k2) {
+            gkk[k2] = (float)(kc0 + myrow[k2]) * gsK;
+            gck[k2] = (kc0 + myrow[k2]) < gK ? gc : 0.f;
+        }
+    }
+    const float gt0 = (float)(qb * XA_QB + 4 * hh);      // GUIDE: first query of the lane's register groups
+    const int gtn = gT - qb * XA_QB - 4 * hh;            // GUIDE: queries below this count (t < T_b)
     __syncthreads();
 
     f32x16 dvacc[KT2][NP][2], gacc[KT2][NP][2];
@@ -371,7 +431,14 @@ __global__ __launch_bounds__(TK * 2) void xattn_bwd_kernel(const bf16_t* __restr
                                                                          (uint32_t)TKtot + (uint32_t)(kc0 + myrow[k2]), thresh, dscale)
                                               : 1.f;
                     pp[i] = p * keep;
-                    ds[i] = p * (pacc[i] * keep - dl[j]) * SC;
+                    if constexpr (GUIDE) {
+                        // + c W[t, k]; the guided term is not dropped out (the loss reads P before the dropout)
+                        const int tq = qt * 32 + 8 * g + j;
+                        const float gw = tq < gtn ? gck[k2] * xg_w(gkk[k2], gt0 + (float)tq, gsT) : 0.f;
+                        ds[i] = p * ((pacc[i] * keep + gw) - dl[j]) * SC;
+                    } else {
+                        ds[i] = p * (pacc[i] * keep - dl[j]) * SC;
+                    }
                 }
             }
 #pragma unroll
@@ -464,6 +531,7 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(const bf16_t* __restrict
 
 static RttsLdsState g_xa_lds[2][4][2];   // [dh == 128][kernel][chunk == 256]
 static RttsLdsState g_xp_lds;
+static RttsLdsState g_xg_lds[2][2][2];   // guided backward: [dh == 128][dropout][chunk == 256]
 extern "C" int rtts_sum_slabs(const void* part, int nslabs, int64_t n, void* out, void* stream);
 
 static int xa_check(const char* fn, int B, int H, int Tq, int Tk, int dh, int64_t ld_q, int64_t ld_kv) {
@@ -520,22 +588,21 @@ extern "C" int rtts_xattn_fwd(const void* q, int64_t ld_q, const void* kv, int64
     return 0;
 }
 
-extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const void* dout,
-                              int64_t ld_dout, const float* lse, const float* delta, int B, int H, int Tq, int Tk, int dh, void* dq,
-                              int64_t ld_dq, void* dkv_part, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* dq_chunks,
-                              void* stream) {
-    RTTS_ENTER(stream);
-    RTTS_REQUIRE(q && kv && dout && lse && delta && dq && dkv_part && drop_p >= 0.f && drop_p < 1.f, "rtts_xattn_bwd: bad arguments");
-    if (xa_check("rtts_xattn_bwd", B, H, Tq, Tk, dh, ld_q, ld_kv)) return -1;
-    RTTS_REQUIRE(ld_dout >= (int64_t)H * dh && ld_dout % 8 == 0 && ld_dq >= (int64_t)H * dh && ld_dq % 8 == 0,
-                 "rtts_xattn_bwd: bad strides");
+// rtts_xattn_bwd (gd == nullptr) and rtts_xattn_bwd_guided: one set of checks, one grid, one LDS size
+static int xa_bwd_launch(const char* fn, const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const void* dout,
+                         int64_t ld_dout, const float* lse, const float* delta, int B, int H, int Tq, int Tk, int dh, void* dq,
+                         int64_t ld_dq, void* dkv_part, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* dq_chunks,
+                         const XaGuide<true>* gd, void* stream) {
+    RTTS_REQUIRE(q && kv && dout && lse && delta && dq && dkv_part && drop_p >= 0.f && drop_p < 1.f, "%s: bad arguments", fn);
+    if (xa_check(fn, B, H, Tq, Tk, dh, ld_q, ld_kv)) return -1;
+    RTTS_REQUIRE(ld_dout >= (int64_t)H * dh && ld_dout % 8 == 0 && ld_dq >= (int64_t)H * dh && ld_dq % 8 == 0, "%s: bad strides", fn);
     RTTS_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dkv_part) & 15) == 0,
-                 "rtts_xattn_bwd: buffers must be 16-byte aligned");
+                 "%s: buffers must be 16-byte aligned", fn);
     const int chunk = xa_bwd_chunk(Tk, dh), nchunks = Tk / chunk;
     // more than one key chunk: each chunk's workgroups write their share of dQ to dq_chunks (nchunks, B*Tq, H*dh) bf16 and
     // the shares are summed into dq (compact rows) by the slab-sum kernel
     RTTS_REQUIRE(nchunks == 1 || (dq_chunks && ld_dq == (int64_t)H * dh && ((uintptr_t)dq_chunks & 15) == 0),
-                 "rtts_xattn_bwd: T_k=%d is worked in %d key chunks: needs dq_chunks (%d x B*T_q x H*dh bf16) and ld_dq == H*dh", Tk, nchunks,
+                 "%s: T_k=%d is worked in %d key chunks: needs dq_chunks (%d x B*T_q x H*dh bf16) and ld_dq == H*dh", fn, Tk, nchunks,
                  nchunks);
     const dim3 grid(B * H * (Tq / XA_QB), nchunks);
     const size_t dq_stride = nchunks > 1 ? (size_t)B * Tq * H * dh : 0;
@@ -543,17 +610,224 @@ extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64
     const size_t lds = (size_t)chunk * (2 * dh) + 2 * (size_t)XA_QB * (2 * dh) + (size_t)chunk * (XA_QB * 2) + XA_QB * 8;
 #define GO(DH_, TK_)                                                                                                      \
     do {                                                                                                                  \
-        auto kern = drop_p > 0.f ? xattn_bwd_kernel<DH_, TK_, true> : xattn_bwd_kernel<DH_, TK_, false>;                  \
-        RTTS_ENSURE_LDS("rtts_xattn_bwd", kern, lds, g_xa_lds[DH_ == 128][1 + (drop_p > 0.f)][TK_ == 256]);               \
-        hipLaunchKernelGGL(kern, grid, dim3(TK_ * 2), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
-                           kvalid, (const bf16_t*)dout, ld_dout, lse, delta, H, Tq, Tk, dq_dst, ld_dq, dq_stride, (bf16_t*)dkv_part, B, \
-                           seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p));                               \
+        if (gd) {                                                                                                         \
+            auto kern = drop_p > 0.f ? xattn_bwd_kernel<DH_, TK_, true, true> : xattn_bwd_kernel<DH_, TK_, false, true>;  \
+            RTTS_ENSURE_LDS(fn, kern, lds, g_xg_lds[DH_ == 128][drop_p > 0.f][TK_ == 256]);                               \
+            hipLaunchKernelGGL(kern, grid, dim3(TK_ * 2), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
+                               kvalid, (const bf16_t*)dout, ld_dout, lse, delta, H, Tq, Tk, dq_dst, ld_dq, dq_stride, (bf16_t*)dkv_part, B, \
+                               seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p), *gd);                                 \
+        } else {                                                                                                          \
+            auto kern = drop_p > 0.f ? xattn_bwd_kernel<DH_, TK_, true, false> : xattn_bwd_kernel<DH_, TK_, false, false>; \
+            RTTS_ENSURE_LDS(fn, kern, lds, g_xa_lds[DH_ == 128][1 + (drop_p > 0.f)][TK_ == 256]);                         \
+            hipLaunchKernelGGL(kern, grid, dim3(TK_ * 2), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q, (const bf16_t*)kv, ld_kv, \
+                               kvalid, (const bf16_t*)dout, ld_dout, lse, delta, H, Tq, Tk, dq_dst, ld_dq, dq_stride, (bf16_t*)dkv_part, B, \
+                               seed, seed_dev, rtts_drop_thresh(drop_p), 1.f / (1.f - drop_p), XaGuide<false>{});        \
+        }                                                                                                                 \
     } while (0)
     if (dh == 128) GO(128, 128); else if (chunk == 256) GO(64, 256); else GO(64, 128);
 #undef GO
-    RTTS_LAUNCH_CHECK("rtts_xattn_bwd");
+    RTTS_LAUNCH_CHECK(fn);
     if (nchunks > 1) return rtts_sum_slabs(dq_chunks, nchunks, (int64_t)dq_stride, dq, stream);
     return 0;
+}
+
+extern "C" int rtts_xattn_bwd(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const void* dout,
+                              int64_t ld_dout, const float* lse, const float* delta, int B, int H, int Tq, int Tk, int dh, void* dq,
+                              int64_t ld_dq, void* dkv_part, float drop_p, uint32_t seed, const uint32_t* seed_dev, void* dq_chunks,
+                              void* stream) {
+    RTTS_ENTER(stream);
+    return xa_bwd_launch("rtts_xattn_bwd", q, ld_q, kv, ld_kv, kvalid, dout, ld_dout, lse, delta, B, H, Tq, Tk, dh, dq, ld_dq, dkv_part,
+                         drop_p, seed, seed_dev, dq_chunks, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------ guided attention loss (training)
+// loss = sum_{b,h,t} rows / (H sum_b T_b), rows[b,h,t] = sum_k P[b,h,t,k] W[b,t,k]: the guided-attention weight of Tachibana et
+// al. that rtts_align_stats reports (table column [5]), as a term of the training loss.  Not in the reference, whose
+// MultiheadAttentionWrapper (reformer_tts/model/reformer.py:161-186) only collects the matrices in eval mode.
+//
+// rows: the forward's dataflow (lane = query, S^T = K Q^T, P = exp2(s c - lse log2 e)), one workgroup per (b, h, 128-query block),
+// the 128-key chunks walked in ascending order (K of chunk c + 1 arrives by DMA while chunk c is worked); a lane adds its keys in
+// ascending order and the two half-waves fold once at the end: one fixed order, no atomics.  Chunks wholly past K_b are skipped.
+// LDS: 2 x 128 keys x 2 DH bytes + 1 KB of validity words: 33 KB at DH = 64, 65 KB at DH = 128.
+#define XG_KC 128
+template <int DH>
+__global__ __launch_bounds__(256) void xattn_guide_rows_kernel(const bf16_t* __restrict__ q, int64_t ld_q, const bf16_t* __restrict__ kv,
+                                                               int64_t ld_kv, const uint8_t* __restrict__ kvalid, const float* __restrict__ lse,
+                                                               const int32_t* __restrict__ n_frames, const int32_t* __restrict__ n_keys,
+                                                               int H, int Tq, int Tk, float g, float* __restrict__ rows) {
+    constexpr int NKT = XG_KC / 32;
+    constexpr int NP = xa_dh<DH>::NP, NKS = xa_dh<DH>::NKS, PLANE = XG_KC * 128;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];     // 2 x [NP][XG_KC][128 B] swizzled (at_off), 2 x kval
+    const int nqb = Tq / XA_QB;
+    const uint32_t wi = xcd_remap(blockIdx.x, gridDim.x);
+    const int bh = wi / nqb, qb = wi % nqb;
+    const int b = bh / H, h = bh % H;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, hh = lane >> 5;
+    const int qrow = qb * XA_QB + wave * 32 + r;
+    float* out = rows + (size_t)bh * Tq + qrow;
+    int T, K;
+    if (!xg_slot(n_frames, n_keys, b, Tq, Tk, T, K) || qb * XA_QB >= T) {     // the whole workgroup: nothing to add up
+        if (hh == 0) *out = 0.f;
+        return;
+    }
+    const int nkc = (K + XG_KC - 1) / XG_KC;
+    const bf16_t* kbase = kv + (size_t)b * Tk * ld_kv + (size_t)h * DH;
+    int* kval = reinterpret_cast<int*>(smem + 2 * NP * PLANE);
+
+    auto stage_k = [&](int c, int buf) {
+        constexpr int ITERS = XG_KC * 8 / 256;
+        unsigned char* dst = smem + buf * (NP * PLANE);
+#pragma unroll
+        for (int it = 0; it < ITERS; ++it) {
+            const int rowb = it * 32 + wave * 8;
+            const int row = rowb + (lane >> 3);
+            const int lp = (lane & 7) ^ at_sw(row);
+            XA_PLANES(NP,
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kbase + pl * 64 + (size_t)(c * XG_KC + row) * ld_kv + lp * 8),
+                                                 (RTTS_LDS void*)(dst + pl * PLANE + rowb * 128), 16, 0, 0););
+        }
+        for (int j = tid; j < XG_KC; j += 256) kval[buf * XG_KC + j] = kvalid ? (int)kvalid[(size_t)b * Tk + c * XG_KC + j] : 1;
+    };
+    stage_k(0, 0);
+
+    constexpr float kLog2e = 1.4426950408889634f;
+    bf16x8 qf[NKS];
+    const bf16_t* qptr = q + ((size_t)b * Tq + qrow) * ld_q + (size_t)h * DH;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qptr + ks * 16 + 8 * hh);
+    // P = exp2((s c - lse) log2 e) with the difference taken FIRST and c the forward's own fp32 scale (its lse is the normaliser of
+    // exactly those logits): at logits near 80 the one-fma form exp2(s c log2 e - lse log2 e) rounds the exponent at the size of
+    // lse log2 e (2^-18 absolute, 3e-6 of P), which a sum of P itself, unlike P V rounded to bf16, would show
+    const float lrow = lse[(size_t)bh * Tq + qrow];
+    const float sT = g / (float)T, sK = g / (float)K;
+    const float tq = (float)qrow;
+    float acc = 0.f;
+#pragma unroll 1
+    for (int c = 0; c < nkc; ++c) {
+        __syncthreads();            // K of chunk c is in LDS, and every wave is done with the buffer chunk c - 1 read
+        if (c + 1 < nkc) stage_k(c + 1, (c + 1) & 1);
+        const unsigned char* Ks = smem + (c & 1) * (NP * PLANE);
+        const int* kvc = kval + (c & 1) * XG_KC;
+        const int k0 = c * XG_KC + 4 * hh;               // the lane's first key of the chunk
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+            f32x16 s = {0};
+            XA_PLANES(NP,
+                _Pragma("unroll")
+                for (int ks = 0; ks < 4; ++ks) {
+                    const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + pl * PLANE + at_off(kt * 32 + r, ks * 2 + hh));
+                    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[pl * 4 + ks], s, 0, 0, 0);
+                });
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const int4 kvv = *reinterpret_cast<const int4*>(kvc + kt * 32 + 8 * g4 + 4 * hh);
+                const int vv[4] = {kvv.x, kvv.y, kvv.z, kvv.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int key = k0 + kt * 32 + 8 * g4 + j;
+                    const float ex = __builtin_fmaf(s[4 * g4 + j], xa_dh<DH>::scale, -lrow);
+                    const float p = (vv[j] && key < K) ? __builtin_amdgcn_exp2f(ex * kLog2e) : 0.f;
+                    acc = __builtin_fmaf(p, xg_w((float)key * sK, tq, sT), acc);
+                }
+            }
+        }
+    }
+    acc = rtts_xhalf_sum(acc);
+    if (hh == 0) *out = qrow < T ? acc : 0.f;
+}
+
+// out[b] = sum_{h,t} rows / (H T_b) (0 for a slot that does not count), out[B] = the loss, c_dev = coef / (H sum_b T_b).  One
+// workgroup: thread i adds elements i, i + 1024, ... of a sample in f64, the 1024 sums fold in a fixed tree, the samples in order.
+#define XG_FOLD_THREADS 1024
+__global__ __launch_bounds__(XG_FOLD_THREADS) void xattn_guide_fold_kernel(const float* __restrict__ rows, const int32_t* __restrict__ n_frames,
+                                                                          const int32_t* __restrict__ n_keys, int B, int H, int Tq, int Tk,
+                                                                          double coef, double* __restrict__ out, float* __restrict__ c_dev) {
+    __shared__ double red[XG_FOLD_THREADS];
+    const int tid = threadIdx.x;
+    double total = 0.0, frames = 0.0;
+    for (int b = 0; b < B; ++b) {
+        int T, K;
+        const bool ok = xg_slot(n_frames, n_keys, b, Tq, Tk, T, K);
+        double s = 0.0;
+        if (ok)
+            for (int i = tid; i < H * T; i += XG_FOLD_THREADS) s += (double)rows[((size_t)b * H + i / T) * Tq + i % T];
+        red[tid] = s;
+        __syncthreads();
+        for (int o = XG_FOLD_THREADS / 2; o > 0; o >>= 1) {
+            if (tid < o) red[tid] += red[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            out[b] = ok ? red[0] / ((double)H * T) : 0.0;
+            if (ok) {
+                total += red[0];
+                frames += (double)T;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out[B] = frames > 0.0 ? total / ((double)H * frames) : 0.0;
+        c_dev[0] = frames > 0.0 ? (float)(coef / ((double)H * frames)) : 0.f;
+    }
+}
+
+static RttsLdsState g_xg_rows_lds;
+// 1 / (sqrt(2) sigma): w = 1 - exp(-x^2 / (2 sigma^2)) = 1 - exp(-(x g)^2)
+static inline float xg_g(double sigma) { return (float)(0.7071067811865476 / sigma); }
+#define XG_NAMED(fn, p) RTTS_REQUIRE((p) != nullptr, "%s: %s is a null pointer", fn, #p)
+
+extern "C" int rtts_xattn_guide_rows(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const float* lse,
+                                     const int32_t* n_frames, const int32_t* n_keys, int B, int H, int Tq, int Tk, int dh, double sigma,
+                                     float* rows, void* stream) {
+    RTTS_ENTER(stream);
+    const char* fn = "rtts_xattn_guide_rows";
+    XG_NAMED(fn, q); XG_NAMED(fn, kv); XG_NAMED(fn, lse); XG_NAMED(fn, n_frames); XG_NAMED(fn, n_keys); XG_NAMED(fn, rows);
+    RTTS_REQUIRE(sigma > 0.0 && sigma <= 1.7e308, "%s: sigma must be positive and finite (got %g)", fn, sigma);
+    if (xa_check(fn, B, H, Tq, Tk, dh, ld_q, ld_kv)) return -1;
+    RTTS_REQUIRE((((uintptr_t)q | (uintptr_t)kv) & 15) == 0, "%s: q and kv must be 16-byte aligned", fn);
+    const size_t nwg = (size_t)B * H * (Tq / XA_QB);
+    RTTS_REQUIRE(nwg <= 0x7fffffff, "%s: grid too large", fn);
+    const size_t lds = 2 * (size_t)XG_KC * (2 * dh) + 2 * XG_KC * 4;
+    if (dh == 128) {
+        RTTS_ENSURE_LDS(fn, xattn_guide_rows_kernel<128>, lds, g_xg_rows_lds);
+        hipLaunchKernelGGL(xattn_guide_rows_kernel<128>, dim3((unsigned)nwg), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q,
+                           (const bf16_t*)kv, ld_kv, kvalid, lse, n_frames, n_keys, H, Tq, Tk, xg_g(sigma), rows);
+    } else {
+        hipLaunchKernelGGL(xattn_guide_rows_kernel<64>, dim3((unsigned)nwg), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q, ld_q,
+                           (const bf16_t*)kv, ld_kv, kvalid, lse, n_frames, n_keys, H, Tq, Tk, xg_g(sigma), rows);
+    }
+    RTTS_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+extern "C" int rtts_xattn_guide_fold(const float* rows, const int32_t* n_frames, const int32_t* n_keys, int B, int H, int Tq, int Tk,
+                                     double coef, double* out, float* c_dev, void* stream) {
+    RTTS_ENTER(stream);
+    const char* fn = "rtts_xattn_guide_fold";
+    XG_NAMED(fn, rows); XG_NAMED(fn, n_frames); XG_NAMED(fn, n_keys); XG_NAMED(fn, out); XG_NAMED(fn, c_dev);
+    RTTS_REQUIRE(coef == coef && coef >= -1.7e308 && coef <= 1.7e308, "%s: coef must be finite (got %g)", fn, coef);
+    if (xa_check(fn, B, H, Tq, Tk, 64, (int64_t)H * 64, (int64_t)2 * H * 64)) return -1;      // the shape part of the envelope
+    hipLaunchKernelGGL(xattn_guide_fold_kernel, dim3(1), dim3(XG_FOLD_THREADS), 0, (hipStream_t)stream, rows, n_frames, n_keys, B, H, Tq, Tk,
+                       coef, out, c_dev);
+    RTTS_LAUNCH_CHECK(fn);
+    return 0;
+}
+
+extern "C" int rtts_xattn_bwd_guided(const void* q, int64_t ld_q, const void* kv, int64_t ld_kv, const uint8_t* kvalid, const void* dout,
+                                     int64_t ld_dout, const float* lse, const float* delta, int B, int H, int Tq, int Tk, int dh, void* dq,
+                                     int64_t ld_dq, void* dkv_part, float drop_p, uint32_t seed, const uint32_t* seed_dev,
+                                     void* dq_chunks, const float* guide_rows, const float* c_dev, const int32_t* n_frames,
+                                     const int32_t* n_keys, double sigma, void* stream) {
+    RTTS_ENTER(stream);
+    const char* fn = "rtts_xattn_bwd_guided";
+    XG_NAMED(fn, q); XG_NAMED(fn, kv); XG_NAMED(fn, dout); XG_NAMED(fn, lse); XG_NAMED(fn, delta); XG_NAMED(fn, dq); XG_NAMED(fn, dkv_part);
+    XG_NAMED(fn, guide_rows); XG_NAMED(fn, c_dev); XG_NAMED(fn, n_frames); XG_NAMED(fn, n_keys);
+    RTTS_REQUIRE(sigma > 0.0 && sigma <= 1.7e308, "%s: sigma must be positive and finite (got %g)", fn, sigma);
+    const XaGuide<true> gd{guide_rows, c_dev, n_frames, n_keys, xg_g(sigma)};
+    return xa_bwd_launch(fn, q, ld_q, kv, ld_kv, kvalid, dout, ld_dout, lse, delta, B, H, Tq, Tk, dh, dq, ld_dq, dkv_part, drop_p, seed,
+                         seed_dev, dq_chunks, &gd, stream);
 }
 
 // ------------------------------------------------------------------------------ head-averaged probabilities (eval)

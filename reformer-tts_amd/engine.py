@@ -977,7 +977,7 @@ class XAttnExec:
         return residual(acc, g, self.mha.out_proj.bias, 1.0, next_norm, out=_keep_streams(keep_streams, slot, acc, inp, xn, mean, rstd, fresh_acc))
 
     def backward(self, acc, inp, d_acc, d_inp, b, t, keys_bf16=None, kvalid=None, dkeys=None, pre=None, next_norm=None,
-                 pre_cast=None, next_cast=None, slot=None, d_src=None, join=None, **_):
+                 pre_cast=None, next_cast=None, slot=None, d_src=None, join=None, guide=None, guide_slot=None, **_):
         slot = self._own_slot if slot is None else slot
         if "pdrop" not in slot:
             raise RuntimeError("XAttnExec.backward: no forward state for this call (backward run twice, or without its forward)")
@@ -1007,9 +1007,24 @@ class XAttnExec:
         # > 256 keys (heads of 128: > 128 keys): worked in chunks, each with its share of dQ
         nkc = _lib.load().rtts_xattn_bwd_key_chunks(tk, e // h)
         dq_chunks = torch.empty(nkc, b * t, e, dtype=torch.bfloat16, device=dev) if nkc > 1 else None
-        _lib.call("rtts_xattn_bwd", q.data_ptr(), e, kv.data_ptr(), 2 * e, None if kvalid is None else kvalid.data_ptr(),
-                  do.data_ptr(), e, lse.data_ptr(), delta.data_ptr(), b, h, t, tk, e // h, dq.data_ptr(), e, part.data_ptr(),
-                  float(dp), dseed, seed_base(dev).data_ptr(), None if dq_chunks is None else dq_chunks.data_ptr(), _s())
+        bwd_args = (q.data_ptr(), e, kv.data_ptr(), 2 * e, None if kvalid is None else kvalid.data_ptr(),
+                    do.data_ptr(), e, lse.data_ptr(), delta.data_ptr(), b, h, t, tk, e // h, dq.data_ptr(), e, part.data_ptr(),
+                    float(dp), dseed, seed_base(dev).data_ptr(), None if dq_chunks is None else dq_chunks.data_ptr())
+        if guide is None:
+            _lib.call("rtts_xattn_bwd", *bwd_args, _s())
+        else:
+            # guided attention loss: rows = rowsum(P o W) and c = coef / (H sum T_b) from this call's q, kv and lse, then the
+            # backward with the term folded into dS; the layer's [per-utterance mass.., loss] stays in guide["out"][guide_slot]
+            nf, nk, sigma = guide["n_frames"], guide["n_keys"], float(guide["sigma"])
+            rows = torch.empty(b * h, t, dtype=torch.float32, device=dev)
+            c = torch.empty(1, dtype=torch.float32, device=dev)
+            _lib.call("rtts_xattn_guide_rows", q.data_ptr(), e, kv.data_ptr(), 2 * e, None if kvalid is None else kvalid.data_ptr(),
+                      lse.data_ptr(), nf.data_ptr(), nk.data_ptr(), b, h, t, tk, e // h, sigma, rows.data_ptr(), _s())
+            _lib.call("rtts_xattn_guide_fold", rows.data_ptr(), nf.data_ptr(), nk.data_ptr(), b, h, t, tk, float(guide["coef"]),
+                      guide["out"][guide_slot].data_ptr(), c.data_ptr(), _s())
+            if guide.get("scale") is not None:        # the loss scale of a captured step is a device word (1 / micro-batches)
+                c.mul_(guide["scale"])
+            _lib.call("rtts_xattn_bwd_guided", *bwd_args, rows.data_ptr(), c.data_ptr(), nf.data_ptr(), nk.data_ptr(), sigma, _s())
         dkv = torch.empty(b * tk, 2 * e, dtype=torch.bfloat16, device=dev)
         _lib.call("rtts_sum_slabs", part.data_ptr(), nqb, dkv.numel(), dkv.data_ptr(), _s())
         gb, gw = _grad(m.in_proj_bias), _grad(m.in_proj_weight)
@@ -1134,6 +1149,10 @@ def _step_kwargs(kind, kwargs, extra, cache):
         out.update(extra)
         if kwargs.get("collect_attention"):
             out["collect_attention"] = True
+        if kwargs.get("guide") is None:
+            out.pop("guide", None)                    # the guide context is for the selected layers only
+        else:
+            out["guide_slot"] = kwargs["guide_slot"]
     return out, None
 
 
@@ -1169,6 +1188,9 @@ class FusedStackFn(torch.autograd.Function):
                     kv = ~kpm if kv is None or kv.shape != kpm.shape or kv.device != kpm.device else kv
                     kv = kv.contiguous().view(torch.uint8) if kv.dtype == torch.bool else kv.to(torch.uint8).contiguous()
                 extra = dict(keys_bf16=kb, kvalid=kv)
+                guide = next((k["guide"] for k in kwargs_list if "key" in k and k.get("guide") is not None), None)
+                if guide is not None:                             # guided attention loss: read by XAttnExec.backward
+                    extra["guide"] = guide
             steps, mask_cache = [], {}
             for (kind, f, g), kwargs in zip(prog, kwargs_list):
                 kw, kwg = _step_kwargs(kind, kwargs, extra, mask_cache)

@@ -5,7 +5,7 @@ through ``dacite``; only the ``model:`` and ``experiment.tts_training:`` section
 from __future__ import annotations
 
 from dataclasses import asdict, dataclass, field, fields, is_dataclass
-from typing import Optional
+from typing import List, Optional
 
 
 @dataclass
@@ -129,6 +129,13 @@ class TTSTrainingConfig:
     # projections; "stash" keeps the streams too and recomputes nothing (~1 GB more at the baseline shapes, of 288 GB).  A mode
     # whose estimated footprint does not fit the free HBM is lowered, with one log line (``Trainer.resolve_recompute``).
     recompute: str = "stash"
+    # this package's addition: guided attention loss (Tachibana et al.; DC-TTS, ESPnet) on the decoder's cross-attention, as a
+    # term of the training loss: weight * mean over the valid frames of the attention mass off the diagonal, the ``guided`` score
+    # of ``evaluation.alignment_scores`` with the same ``sigma``.  0 = off (nothing that runs changes).  ``layers``: decoder
+    # layer indices, None = all.  Runs inside the explicit executors only (``Trainer`` raises otherwise).
+    guided_attention_weight: float = 0.0
+    guided_attention_sigma: float = 0.2
+    guided_attention_layers: Optional[List[int]] = None
 
 
 def _merge(dc, overrides: dict):

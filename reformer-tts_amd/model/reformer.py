@@ -137,6 +137,10 @@ class ReformerDec(nn.Module):
     always collects, as the reference does."""
 
     collect_attention = True
+    # guided attention loss (``Trainer``, tts_training.guided_attention_weight > 0): dict(n_frames, n_keys int32 (B,) on the device,
+    # sigma, coef, scale (device scalar or None), layers (decoder layer indices), out f64 (len(layers), B + 1)) for the next
+    # training forward, else None.  It reaches the selected layers' cross-attention executor the way the key padding mask does.
+    guide = None
 
     def __init__(self, dim: int, depth: int, ff_chunks: int, attn_kwargs: Dict, self_attn_kwargs: Dict, ff_kwargs: Dict):
         super().__init__()
@@ -165,6 +169,9 @@ class ReformerDec(nn.Module):
             kwargs["value"] = keys
             kwargs["key_padding_mask"] = key_padding_mask
             kwargs["collect_attention"] = self.collect_attention
+        if self.guide is not None and self.training:
+            for slot, layer in enumerate(self.guide["layers"]):
+                kwargs_list[2 + 6 * layer].update(guide=self.guide, guide_slot=slot, guide_layer=layer)
         for kwargs in kwargs_list[::6]:
             kwargs["input_mask"] = input_mask
         self.attention_matrices_.clear()

@@ -217,6 +217,10 @@ class ReversibleSequence(nn.Module):
         elif self.use_fused and x.is_cuda and not keys_ok:
             from .._lib import note_general_path
             note_general_path("decoder stack", f"{context.shape[1]} encoder keys: the cross-attention kernels take multiples of 128 up to 2048")
+        guided = next((k["guide_layer"] for k in kwargs_list if k.get("guide") is not None), None)
+        if guided is not None:
+            raise NotImplementedError(f"guided attention loss: decoder layer {guided}'s cross-attention would run on the general (autograd) "
+                                      "path, which has no guided term; it needs the explicit HIP executors (engine.XAttnExec)")
         y1, y2 = self.forward_halves(x, x, kwargs_list, context)
         return y1 + y2
 

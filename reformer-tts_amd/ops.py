@@ -936,3 +936,43 @@ def alignment_mas(mats, n_frames: torch.Tensor, n_keys: torch.Tensor, floor: flo
               _ptr(path), scores.data_ptr(), work.data_ptr(), work.numel(), _stream())
     TIMING.stop(ev, 0.0)
     return dur, path, scores
+
+
+def xattn_guide_loss(q: torch.Tensor, kv: torch.Tensor, kvalid: Optional[torch.Tensor], lse: torch.Tensor, n_frames: torch.Tensor,
+                     n_keys: torch.Tensor, heads: int, sigma: float = 0.2, coef: float = 1.0,
+                     rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Guided attention loss of one ``rtts_xattn_fwd`` call (its q (B*T_q, H*dh) bf16, kv (B*T_k, 2*H*dh) bf16, kvalid u8 (B, T_k) or
+    None and lse f32 (B*H, T_q)): ``rtts_xattn_guide_rows`` + ``rtts_xattn_guide_fold``.  ``n_frames`` / ``n_keys`` int32 (B,) ON
+    THE DEVICE -> (rows f32 (B*H, T_q) = sum_k P W, out f64 (B + 1,) = per utterance mean off-diagonal mass and, last, the loss
+    sum rows / (H sum_b T_b), c f32 (1,) = coef / (H sum_b T_b)): the operands ``rtts_xattn_bwd_guided`` takes.  W is the guided
+    attention weight of Tachibana et al., 1 - exp(-(k / K_b - t / T_b)^2 / (2 sigma^2)); the loss is the mean over ROWS (frames),
+    in [0, 1] -- ESPnet's guided attention loss averages over the T_b K_b cells instead, which is smaller by a factor of about K.
+    Nothing read back: capturable."""
+    if not float(sigma) > 0.0:
+        raise ValueError(f"xattn_guide_loss: sigma must be positive (got {sigma})")
+    for name, t, dt in (("q", q, torch.bfloat16), ("kv", kv, torch.bfloat16), ("lse", lse, torch.float32), ("n_frames", n_frames, torch.int32),
+                        ("n_keys", n_keys, torch.int32)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt):
+            raise _lib.RttsError(f"xattn_guide_loss runs on the GPU only: {name} must be a CUDA {dt} tensor "
+                                 f"(got {getattr(t, 'dtype', type(t).__name__)} on {getattr(t, 'device', 'the host')})")
+    b = int(n_frames.shape[0])
+    e = q.shape[-1]
+    if q.dim() != 2 or kv.dim() != 2 or kv.shape[1] != 2 * e or e % heads or q.shape[0] % b or kv.shape[0] % b or q.stride(1) != 1 or kv.stride(1) != 1:
+        raise ValueError(f"xattn_guide_loss: q must be (B*T_q, H*dh) and kv (B*T_k, 2*H*dh) with unit column strides "
+                         f"(got {tuple(q.shape)}, {tuple(kv.shape)}, B = {b}, H = {heads})")
+    tq, tk = q.shape[0] // b, kv.shape[0] // b
+    if tuple(lse.shape) != (b * heads, tq) or not lse.is_contiguous() or tuple(n_keys.shape) != (b,) or not n_frames.is_contiguous() \
+            or not n_keys.is_contiguous():
+        raise ValueError(f"xattn_guide_loss: lse must be contiguous ({b * heads}, {tq}) and n_frames, n_keys contiguous ({b},)")
+    if kvalid is not None and not (kvalid.is_cuda and kvalid.dtype == torch.uint8 and tuple(kvalid.shape) == (b, tk) and kvalid.is_contiguous()):
+        raise ValueError(f"xattn_guide_loss: kvalid must be a contiguous CUDA uint8 ({b}, {tk}) tensor")
+    dev = q.device
+    if rows is None:
+        rows = torch.empty(b * heads, tq, dtype=torch.float32, device=dev)
+    out = torch.empty(b + 1, dtype=torch.float64, device=dev)
+    c = torch.empty(1, dtype=torch.float32, device=dev)
+    _lib.call("rtts_xattn_guide_rows", q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), _ptr(kvalid), lse.data_ptr(), n_frames.data_ptr(),
+              n_keys.data_ptr(), b, heads, tq, tk, e // heads, float(sigma), rows.data_ptr(), _stream())
+    _lib.call("rtts_xattn_guide_fold", rows.data_ptr(), n_frames.data_ptr(), n_keys.data_ptr(), b, heads, tq, tk, float(coef), out.data_ptr(),
+              c.data_ptr(), _stream())
+    return rows, out, c

@@ -123,10 +123,55 @@ class Trainer:
         if self.recompute not in engine.RECOMPUTE_MODES:
             raise ValueError(f"tts_training.recompute = {self.recompute!r}: expected one of {engine.RECOMPUTE_MODES}")
         self._recompute_for = {}                         # padded batch shape -> the mode that fits the free HBM
+        self._guide = self.guided_attention_plan(model, cfg)     # (weight, sigma, decoder layers) or None
+        self.last_guided_attention = None                # (selected layers, B + 1) f64 on the device: [per-utterance mass.., loss]
         self._decorrelate_replicas()
         self._flatten()
         self._make_buckets()
         self._pending: List = []
+
+    @staticmethod
+    def guided_attention_plan(model, cfg):
+        """tts_training.guided_attention_{weight, sigma, layers} -> (weight, sigma, sorted decoder layer indices), or None with the
+        weight at 0.  Host logic only.  The term lives in the cross-attention executor's backward: a selected layer whose
+        cross-attention the executor does not take is refused here, by name, instead of training without the term."""
+        weight = float(getattr(cfg, "guided_attention_weight", 0.0) or 0.0)
+        if weight == 0.0:
+            return None
+        sigma = float(getattr(cfg, "guided_attention_sigma", 0.2))
+        if not (weight > 0.0 and sigma > 0.0):
+            raise ValueError(f"tts_training: guided_attention_weight must be >= 0 and guided_attention_sigma > 0 (got {weight}, {sigma})")
+        dec = model.dec.reformer
+        layers = getattr(cfg, "guided_attention_layers", None)
+        layers = list(range(dec.depth)) if layers is None else sorted({int(i) for i in layers})
+        if not layers or layers[0] < 0 or layers[-1] >= dec.depth:
+            raise ValueError(f"tts_training.guided_attention_layers = {layers}: expected decoder layer indices in 0..{dec.depth - 1}")
+        for i in layers:
+            withnorm = dec.layers.blocks[dec.block_len * i + 2].f.net
+            if not engine.XAttnExec.supported(withnorm):
+                m = withnorm.fn.layer
+                raise NotImplementedError(f"guided attention loss: decoder layer {i}'s cross-attention (embed_dim {m.embed_dim}, num_heads "
+                                          f"{m.num_heads}) is outside the explicit HIP executor (heads of 64 or 128, no bias_k / "
+                                          "add_zero_attn); the general (autograd) path has no guided term")
+        return weight, sigma, layers
+
+    def _guide_context(self, batch, scale):
+        """The decoder's guide context of one forward: T_b = the frames the loss mask counts (``loss_mask.mean(-1)`` as the
+        frame mask, ``wrappers.py:60``), K_b = the non-padding phonemes (as ``_alignment``), both int32 on the device and computed
+        there; coef = weight x the scale the loss carries into the backward (``scale``: a host number, or a device scalar of a
+        captured step, applied on the device)."""
+        weight, sigma, layers = self._guide
+        n_frames = (batch["loss_mask"].mean(dim=-1) != 0).sum(dim=1).to(torch.int32)
+        n_keys = (batch["phonemes"] != 0).sum(dim=1).to(torch.int32)
+        host = 1.0 if (scale is None or torch.is_tensor(scale)) else float(scale)
+        out = torch.zeros(len(layers), n_frames.shape[0] + 1, dtype=torch.float64, device=n_frames.device)
+        self.last_guided_attention = out
+        return dict(n_frames=n_frames, n_keys=n_keys, sigma=sigma, coef=weight * host, scale=scale if torch.is_tensor(scale) else None,
+                    layers=layers, out=out)
+
+    def guided_attention_loss(self):
+        """Mean over the selected layers of the last step's guided attention loss (device f64 scalar), or None with the weight at 0."""
+        return None if self.last_guided_attention is None else self.last_guided_attention[:, -1].mean()
 
     def _decorrelate_replicas(self):
         """Data-parallel replicas hold identical parameters but must draw their own randomness (seed + rank):
@@ -324,8 +369,10 @@ class Trainer:
         edges.SYNC_BN = self._sync_bn
         engine.set_recompute(self.resolve_recompute(batch))     # cached per shape: a capture (after its warm-up passes) asks nothing of the device
 
-    def forward_loss(self, batch, split: bool = False):
-        """``wrappers.py:53-72``: input frames [0, L-1), targets [1, L), mask = loss_mask.mean(-1)."""
+    def forward_loss(self, batch, split: bool = False, loss_scale=None):
+        """``wrappers.py:53-72``: input frames [0, L-1), targets [1, L), mask = loss_mask.mean(-1).  ``loss_scale``: what the caller
+        multiplies the loss by before its backward (a host number or a device scalar); only the guided attention term, which
+        enters in the decoder's backward and not through the returned loss, needs to be told."""
         self._apply_modes(batch)
         spec = self._frames(batch)[0]
         from ..model.lsh_attention import LSHSelfAttention
@@ -336,9 +383,13 @@ class Trainer:
         if spec.device.type == "cuda":
             from ..edges import ConvK5
             ConvK5.refresh_all(spec.device)          # every convolution's GEMM-layout weight copy, one launch
+        dec = self.model.dec.reformer
         try:
+            if self._guide is not None and self.model.training:
+                dec.guide = self._guide_context(batch, loss_scale)      # a stack that leaves the executors refuses it, by layer
             return self._forward_loss(batch, split)
         finally:
+            dec.guide = None
             LSHSelfAttention.rotation_pool = None
 
     def _forward_loss(self, batch, split: bool = False):
@@ -553,7 +604,7 @@ class Trainer:
         dec_seq.manual = {}
         try:
             engine.stamp("step: first kernel of the forward")
-            total, raw_l, post_l, stop_l = self.forward_loss(batch, split="overlap")
+            total, raw_l, post_l, stop_l = self.forward_loss(batch, split="overlap", loss_scale=loss_scale)
             engine.stamp("forward + loss done")
             if "call" not in dec_seq.manual:
                 raise RuntimeError("the decoder stack did not take the explicit executor: the overlapped step needs it")
@@ -619,7 +670,7 @@ class Trainer:
         total = None
         for i, batch in enumerate(batches):
             self._accumulating = i + 1 < n                     # all-reduce only with the last micro-batch
-            loss = self.forward_loss(batch)[0]
+            loss = self.forward_loss(batch, loss_scale=1.0 / n)[0]
             self._run_backward(loss * (1.0 / n))
             total = loss.detach() if total is None else total + loss.detach()
         self._accumulating = False
@@ -760,7 +811,7 @@ class Trainer:
                 losses.append(step(group))
                 group = []
                 if log_every and len(losses) % log_every == 0:
-                    print(f"step {self.global_step}: loss {float(losses[-1]):.4f}", flush=True)
+                    print(f"step {self.global_step}: loss {float(losses[-1]):.4f}{self._guided_log()}", flush=True)
         if group:                                              # a trailing partial group still makes a step
             losses.append(step(group))
         self.end_epoch()
@@ -801,11 +852,16 @@ class Trainer:
                 losses.append(step(group))
                 group = []
                 if log_every and len(losses) % log_every == 0:
-                    print(f"step {self.global_step}: loss {float(losses[-1]):.4f}", flush=True)
+                    print(f"step {self.global_step}: loss {float(losses[-1]):.4f}{self._guided_log()}", flush=True)
         if group:                                              # a trailing partial group still makes a step
             losses.append(step(group))
         self.end_epoch()
         return losses
+
+    def _guided_log(self) -> str:
+        """" guided_attention_loss x" for the log line of ``fit`` / ``fit_corpus`` (the last micro-batch's; read with the loss)."""
+        g = self.guided_attention_loss()
+        return "" if g is None else f" guided_attention_loss {float(g):.4f}"
 
     def _noise_seed(self, micro: int) -> int:
         """Seed word of the input noise of micro-batch ``micro`` of the optimizer step about to run."""
@@ -1041,7 +1097,7 @@ class Trainer:
             engine.WEIGHT_EPOCH[0] += 1
             if self.overlap_encoder:                     # the encoder as a parallel branch of the graph (train_step_overlapped)
                 return self.forward_backward_overlapped(bufs, self._acc_scale)[0].detach()
-            total = self.forward_loss(bufs)[0]
+            total = self.forward_loss(bufs, loss_scale=self._acc_scale)[0]
             self._run_backward(total * self._acc_scale)
             return total.detach()
 
@@ -1063,6 +1119,7 @@ class Trainer:
             with self._capturing(graph, **({} if pool is None else {"pool": pool})):
                 entry["out"] = micro()
             entry["graph"] = graph
+            entry["guided"] = self.last_guided_attention      # written by every replay of this graph (None with the weight at 0)
         finally:
             for seq, h in hooks:
                 seq.block_done_hook = h
@@ -1118,7 +1175,7 @@ class Trainer:
             corpus_seed = self._noise_seed(i) if isinstance(batch, _CorpusMicro) else None
             if entry is None:
                 self._accumulating = True                      # the exchange happens once, below
-                loss = self.forward_loss(batch if corpus_seed is None else batch.eager(corpus_seed))[0]
+                loss = self.forward_loss(batch if corpus_seed is None else batch.eager(corpus_seed), loss_scale=1.0 / n)[0]
                 self._run_backward(loss * (1.0 / n))
                 self._accumulating = False
                 loss = loss.detach()
@@ -1131,6 +1188,7 @@ class Trainer:
                     seed_base(self.device).add_(7919)          # micro-batches of one step must not repeat each other's masks
                 entry["graph"].replay()
                 loss = entry["out"].clone()
+                self.last_guided_attention = entry.get("guided")
             total = loss if total is None else total + loss
         if self.world > 1:
             dist.all_reduce(self.flat_g, group=self.pg)
